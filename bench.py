@@ -10,9 +10,15 @@ in HBM, random-init weights.  A step = zero_grad -> forward -> loss -> backward 
 clip(1.0) -> AdamW (main.py:91-108), bf16 MFMA compute with f32 accumulation and f32 master weights.
 Weak scaling: per-GPU batch fixed, sequences sharded over ranks, one RCCL gradient exchange per step.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract fields; what takes
+work of its own is added by --full (each part can still be dropped with its --no-* option):
   roofline      -- dominant MFMA kernel: algorithmic FLOPs / HIP-event time of its launches (one instrumented step)
+  secondary     -- the second north_star workload (cloud 128x128 seq-8) on the same model and ranks
+  side_stream   -- whether the weight-gradient stream still runs beside the main stream (a spin probe of the two)
   cpu_baseline  -- the CPU oracle's training step timed on this host's cores on a bounded sample (N=1 only)
+--dump-outputs DIR writes what the last timed step returned (train: loss, y_pred; rollout: y) as DIR/<name>.npy in float32.
+Weights and inputs come from fixed seeds, and with --dump-outputs the last training step starts again from the initial weights,
+so two runs or two builds with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -36,6 +42,7 @@ TRAFFIC_NOTE = (f"committed PMC passes (profiles/{TRAFFIC_FILE}: rocprofv3 --pmc
                 "this command, gfx950 correction applied); NOT measured in this run")
 TRAIN_GFLOP_PER_FRAME = {(64, True, 64): 39.79, (32, False, 64): 6.33, (64, True, 128): 159.17, (32, False, 128): 25.33,
                          (64, True, 256): 636.67}
+DUMP_MAX_VALUES = 1 << 23          # per array written by --dump-outputs (32 MiB in float32): a dump stays under 64 MB in all
 
 
 def parse():
@@ -63,6 +70,12 @@ def parse():
                          "(BASELINE.json configs[3])")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes work of its own beside the timed steps: the roofline step, the secondary workload, "
+                         "the side-stream probe and the CPU baseline (a plain run only sets up, warms up and times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them returned as DIR/<name>.npy in float32 (an array of "
+                         "more than 2^23 values as the values at a fixed, seeded set of indices)")
     ap.add_argument("--force-ddp", action="store_true", help="wrap in FlatDDP even for one rank (exercises the RCCL path)")
     ap.add_argument("--mode", default="train", choices=["train", "rollout"],
                     help="rollout = BASELINE.json config 5: stateful frame-by-frame inference, hipGraph-captured step")
@@ -70,7 +83,7 @@ def parse():
     ap.add_argument("--sync-wgrad", action="store_true",
                     help="keep weight-gradient GEMMs on the main stream for the whole run (the profile run: kernel durations "
                          "in a rocprofv3 trace are then free of side-stream overlap and agree with the roofline leg)")
-    ap.add_argument("--dump-launches", action="store_true", help="per-shape table of the instrumented step (stderr)")
+    ap.add_argument("--dump-launches", action="store_true", help="per-shape table of the instrumented step (stderr; needs --full)")
     ap.add_argument("--bf16-buckets", action="store_true", help="FlatDDP exchanges gradients as bf16 (half the bytes over xGMI)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="developer rehearsal of the N-rank flow on a 1-GPU box: every rank uses cuda:0 and the collectives go over "
@@ -78,7 +91,10 @@ def parse():
     ap.add_argument("--dry-launch", action="store_true",
                     help="start the ranks, rendezvous over gloo on the CPU, report what every rank saw and exit (no GPU work): "
                          "the CPU test of the launch contract")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.dump_launches and not a.full:
+        ap.error("--dump-launches times an instrumented step of its own: add --full")
+    return a
 
 
 def free_port() -> int:
@@ -183,6 +199,21 @@ def log(msg):
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+def dump_outputs(out_dir, **arrays) -> None:
+    """--dump-outputs: every tensor as ``out_dir/<name>.npy`` in float32.  An array of more than DUMP_MAX_VALUES values is
+    written as its values at DUMP_MAX_VALUES flat indices drawn from a fixed seed (sorted): the same indices in every run."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float().contiguous()
+        if t.numel() > DUMP_MAX_VALUES:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_MAX_VALUES))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    log(f"outputs of the last timed step: {', '.join(n + '.npy' for n in arrays)} in {out_dir}")
+
+
 def rollout_bench(a, U, dev, skip):
     """Inference-only autoregressive rollout (config 5): one frame per step, all recurrent state carried on the device."""
     model = U.TemporalUNetDualView(1, 1, base_ch=a.base_ch, lstm_layers=1, use_skip_lstm=skip).to(dev).eval()
@@ -198,7 +229,9 @@ def rollout_bench(a, U, dev, skip):
         y = sp.step(frames[i % 4])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    fwd_gf = {64: 13.264, 128: 53.06, 256: 212.22, 512: 848.89}.get(a.size) if (a.base_ch, skip) == (64, True) else None
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, y=y)
+    fwd_gf ={64: 13.264, 128: 53.06, 256: 212.22, 512: 848.89}.get(a.size) if (a.base_ch, skip) == (64, True) else None
     out = {"metric": f"inference frames/sec, {a.size}x{a.size} stateful rollout", "value": round(a.batch * n / dt, 2), "unit": "frames/s",
            "n_gpus": 1, "steps": n, "warmup": max(a.warmup, 3), "ms_per_step": round(dt / n * 1e3, 3), "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
@@ -226,13 +259,18 @@ def rollout_bench(a, U, dev, skip):
     emit(out)
 
 
-def run_workload(a, U, ops, dist, dev, world, rank, model, opt, ddp, *, size, seq, batch, steps, warmup, roofline, tag):
-    """Warm up, time ``steps`` training steps of one workload (barrier + synchronize on both sides, MAX over ranks) and, when
-    asked, price one extra instrumented step against the MFMA / HBM rooflines.  Returns a dict of measurements."""
+def run_workload(a, U, ops, dist, dev, world, rank, model, opt, ddp, *, size, seq, batch, steps, warmup, roofline, tag, dump=None):
+    """Warm up, time ``steps`` training steps of one workload (barrier + synchronize on both sides, MAX over ranks), write what
+    the last of them returned to ``dump`` (rank 0) and, when asked, price one extra instrumented step against the MFMA / HBM
+    rooflines.  Returns a dict of measurements."""
     skip = not a.no_skip_lstm
     data = U.SyntheticSequences(batch, seq, size, size, seed=1 + rank, kind="uniform", device=dev)
     x, y = data.x, data.y
 
+    # --dump-outputs: the last timed step starts again from the seeded initial weights.  Every step sums in float atomics, so
+    # two runs differ in the last bits, and training (AdamW, batch-statistics BatchNorm at random init) amplifies that far past
+    # rounding within a few steps; from the same weights and data one step's outputs agree to rounding.
+    init_p = opt.flat.flat_p.clone() if dump else None
     graphed = None
     if getattr(a, "graph", False) and ddp is None and opt.capturable:
         graphed = U.GraphedTrainStep(model, opt, x, y, None, False, warmup=2)
@@ -259,7 +297,10 @@ def run_workload(a, U, ops, dist, dev, world, rank, model, opt, ddp, *, size, se
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(steps):
-        loss, _ = step()
+        if init_p is not None and i == steps - 1:
+            opt.flat.flat_p.copy_(init_p)          # parameters are views of this buffer
+            ops.weights_changed()                  # packed weight panels must be rebuilt, as after an optimiser step
+        loss, y_pred = step()
         marks[i + 1].record()
     torch.cuda.synchronize()
     if world > 1:
@@ -274,6 +315,8 @@ def run_workload(a, U, ops, dist, dev, world, rank, model, opt, ddp, *, size, se
         dt = float(t)
     frames = batch * seq * world * steps
     log(f"{tag}: timed {steps} steps in {dt:.3f} s")
+    if dump and rank == 0:
+        dump_outputs(dump, loss=loss, y_pred=y_pred)
     res = {"value": frames / dt, "dt": dt, "ms_per_step": dt / steps * 1e3, "loss": float(loss),
            "per_step": [round(per_step[0], 2), round(per_step[len(per_step) // 2], 2), round(per_step[-1], 2)], "roofline": None}
     gf = TRAIN_GFLOP_PER_FRAME.get((a.base_ch, skip, size))
@@ -450,16 +493,18 @@ def main():
     log(f"model + data ready ({sum(p.numel() for p in model.parameters())} parameters); warm-up x{a.warmup}")
 
     head = run_workload(a, U, ops, dist, dev, world, rank, model, opt, ddp, size=a.size, seq=a.seq, batch=a.batch, steps=a.steps,
-                        warmup=a.warmup, roofline=not a.no_roofline, tag="headline")
-    # does the weight-gradient stream still run beside the main stream?  (the runtime maps streams to hardware queues; two on one
-    # queue serialise, which costs this step ~2.5 ms: recorded so that a slow run can be told from a slow box)
-    side = ops.side_stream(dev)
-    overlap = {"probes": ops._SIDE_STREAM_PROBES.get(str(dev)), "still_concurrent": bool(ops._streams_overlap(torch.cuda.current_stream(dev), side))}
+                        warmup=a.warmup, roofline=a.full and not a.no_roofline, tag="headline", dump=a.dump_outputs)
+    overlap = None
+    if a.full:
+        # does the weight-gradient stream still run beside the main stream?  (the runtime maps streams to hardware queues; two on
+        # one queue serialise, which costs this step ~2.5 ms: recorded so that a slow run can be told from a slow box)
+        side = ops.side_stream(dev)
+        overlap = {"probes": ops._SIDE_STREAM_PROBES.get(str(dev)), "still_concurrent": bool(ops._streams_overlap(torch.cuda.current_stream(dev), side))}
 
-    # The second north_star workload (cloud sequences 128x128 seq-8, preprocessing/build_sequences.py:15,108-131) on the same
-    # model, optimiser and ranks, right after the headline: 5 warm-up + 10 timed steps (~1.5 s of GPU time at N = 1).
+    # With --full, the second north_star workload (cloud sequences 128x128 seq-8, preprocessing/build_sequences.py:15,108-131) on
+    # the same model, optimiser and ranks, right after the headline: 5 warm-up + 10 timed steps (~1.5 s of GPU time at N = 1).
     second = None
-    if not a.no_secondary and (a.size, a.seq) == (64, 20) and a.mode == "train":
+    if a.full and not a.no_secondary and (a.size, a.seq) == (64, 20) and a.mode == "train":
         try:
             r2 = run_workload(a, U, ops, dist, dev, world, rank, model, opt, ddp, size=128, seq=8, batch=a.batch, steps=10, warmup=5,
                               roofline=not a.no_roofline, tag="secondary")
@@ -485,7 +530,8 @@ def main():
             "rccl_ranks": dist.get_world_size() if dist.is_initialized() else 1,
             **({"allreduce_bytes": exchange["allreduce_bytes"], "buckets": exchange["buckets"], "bucket_dtype": exchange["dtype"]} if exchange else {}),
             **({"rehearsal": "all ranks on cuda:0, collectives over gloo -- not a scaling measurement"} if a.rehearse_on_one_gpu else {}),
-            "final_loss": round(head["loss"], 5), "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2), "side_stream": overlap, "host_gc": "collected and frozen after warm-up",
+            "final_loss": round(head["loss"], 5), "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2), "host_gc": "collected and frozen after warm-up",
+            **({"side_stream": overlap} if overlap is not None else {}),
             "step_ms_min_median_max": head["per_step"],
             **({"hip_graph": "whole training step replayed as one captured HIP graph"} if (a.graph and opt.capturable) else {}),
         }
@@ -496,7 +542,7 @@ def main():
             out["roofline"] = head["roofline"]
         if second is not None:
             out["secondary"] = second
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.base_ch, skip, a.size, a.seq)
         emit(out)
     if world > 1 or a.force_ddp:
