@@ -724,6 +724,277 @@ __global__ __launch_bounds__(512, 1) void igemm_wgrad_p3_kernel(const uclstm_wgr
 #endif
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The same 256 x 256 tile with FOUR waves (one per SIMD), each owning 128 x 128 of it (256 accumulator registers per lane,
+// which the compiler keeps in AGPRs): per K-tile a wave reads (128 + 128) x 64 operand values for twice the MFMAs of the
+// 8-wave form, i.e. a third fewer fragment bytes per MFMA (768 -> 512 LDS cycles per K-tile and CU).  Operand handling, plane
+// layout, swizzle, tile order and epilogue contract are those of igemm_wgrad_p3_kernel; every output element sees the same
+// MFMA instruction with the same k order, so the two kernels agree bit for bit at equal splits.  What differs:
+//   * ownership stays INTERLEAVED over the halves as in the 8-wave form (rows mh*128 + wr*64 + 16 i, columns nh*128 + wc*64 +
+//     16 j): a wave's tile is four 64 x 64 quadrants (32 MFMA each, one per phase) and every half-tile is read in exactly one
+//     phase by every wave, which is what lets a half be re-staged right after that phase;
+//   * no second wave shares the SIMD, so the fragments of a half are read ONE PHASE BEFORE the quadrant that first needs them,
+//     interleaved with the MFMAs of the running quadrant.  Quadrant order (dY half, X half): (0,0) (0,1) (1,1) (1,0).  The last
+//     quadrant still uses X-lo when X-lo of the next K-tile is read, so that read goes to a fifth fragment set, copied at the
+//     top of the next K-tile (32 v_mov).  An 8-phase body with the quadrant order alternating by K-tile parity needs no fifth
+//     set, but the compiler then permutes the 256 accumulators through the loop back-edge (360 copies per iteration);
+//   * ONE barrier per phase.  Phase g: issue half g + LEAD (4 DMA instructions per wave), read half g + 2 between the 32 MFMA,
+//     wait until at most LEAD - 3 halves are in flight (half g + 3 has landed), [LEAD 9: lgkmcnt(0)], s_barrier.  DESIGN.md
+//     section 3 has the hazard table.
+// tr_frag128 for a loop that keeps LDS-DMA in flight across its reads: the __restrict__ parameter gives the inlined reads
+// alias-scope metadata, without which the compiler drains every DMA (s_waitcnt vmcnt(0)) before each LDS read it cannot tell
+// apart from the DMA's destination.  The order of DMA and reads is kept by hand (counted vmcnt + barrier).
+__device__ __forceinline__ act16x8 tr_frag128_nowait(const unsigned char* __restrict__ p) {
+    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)(p));
+    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)(p + 16 * 128));
+    typedef __attribute__((ext_vector_type(8))) short short8v;
+    const short8v v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    return __builtin_bit_cast(act16x8, v);
+}
+
+// at most NH half-tiles (4 DMA instructions of this wave each) stay in flight
+template <int NH>
+__device__ __forceinline__ void p3w_wait_halves() {
+    static_assert(NH == 5 || NH == 6, "vmcnt immediate");
+    if constexpr (NH == 6) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
+}
+
+template <int NSRC, int LEAD>
+__global__ __launch_bounds__(256, 1) void igemm_wgrad_p3w_kernel(const uclstm_wgrad_desc d, const WDerived dv, const P2 p2) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(LEAD == 8 || LEAD == 9, "eight half-tile slots: a half is re-staged one (9) or two (8) phases after its reads");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 1;     // along panel rows
+    const int wc = wave & 1;      // along K columns
+    const int l15 = lane & 15;
+    const int lq = lane >> 4;
+
+    const int per_split = dv.n_kt * dv.n_nt;
+    const int lid = xcd_remap(blockIdx.x, per_split * d.splits);
+    const int sp = lid / per_split;
+    const int rr = lid - sp * per_split;
+    int nt, kts;
+    grouped_tile(rr, dv.n_nt, dv.n_kt, 4, nt, kts);
+    int kt = kts;
+    if (dv.kt_per_tap > 0) {
+        const int ntaps = d.ktap * d.ktap;
+        const int cg = kts / ntaps;
+        kt = (kts - cg * ntaps) * dv.kt_per_tap + cg;
+    }
+    const int n0 = nt * 256;
+    const int kbase = kt * 256;
+
+    const long m_begin = (long)sp * dv.chunk;
+    const long m_end = min(dv.M, m_begin + dv.chunk);
+    const int KT = m_begin < dv.M ? (int)((m_end - m_begin) / TP) : 0;      // block-uniform
+    if (KT == 0) return;
+    const int total_halves = 4 * KT;
+
+    const uclstm_seg G = d.seg[0];
+    const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc((void*)G.ptr, 0, p2.ybytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsx0 =
+        __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)d.src[0].ptr - p2.xbias[0]), 0, p2.xbytes[0], 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsx1 =
+        NSRC > 1 ? __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)d.src[1].ptr - p2.xbias[1]), 0, p2.xbytes[1], 0x00020000)
+                 : rsx0;
+
+    // ---- staging role: DMA instruction (plane i, row half hh) of a half fills rows 32*hh + 8*wave + (lane>>3) of its plane i.
+    // The two row halves share the per-lane offsets: rows 32.. are rows 0..31 of a stage that begins 32 pixels later (scalar
+    // offset and tap validity taken at pixel mb + 32; 32 is a multiple of W, or W of 32, so neither wraps inside a row half).
+    const int lrow = lane >> 3;
+    const int cp = lane & 7;
+    const int sc = 2 * ((cp >> 1) ^ ((lrow >> 1) & 3)) + (cp & 1);      // source 16-byte chunk stored at this position
+    const int r = 8 * wave + lrow;                                       // pixel row (0..31) inside the row half
+    const int Wm = d.W - 1, Hm = d.H - 1;
+    const int kseg = dv.kseg0 + dv.kseg1;
+    uint32_t yvoff[4], xvoff[4], kxj[4], kyj[4];
+    int xsrc[4];
+#pragma unroll
+    for (int pl = 0; pl < 4; ++pl) {
+        const int ny = n0 + pl * 64 + sc * 8;
+        const bool yok = ny < d.N && ny >= G.n_begin && ny < G.n_end;
+        yvoff[pl] = yok ? (uint32_t)(2 * (r * G.C + G.c_off + (ny - G.n_begin))) : OOB;
+        const int k0 = kbase + pl * 64;
+        const int xtap = (int)fdiv((uint32_t)k0, dv.dPerTap);
+        const int kr = k0 - xtap * kseg;
+        const int xs_ = (NSRC > 1 && kr >= dv.kseg0) ? 1 : 0;
+        const int xc = (xs_ ? kr - dv.kseg0 : kr) + sc * 8;
+        const uclstm_src S = d.src[xs_];
+        const bool xok = k0 < d.Ktot && xc < S.C;
+        const int tdy = xtap / d.ktap;
+        const int ddy = tdy - d.pad;
+        const int ddx = (xtap - tdy * d.ktap) - d.pad;
+        const int badx = ddx < 0 ? 0 : (ddx > 0 ? Wm : -1);
+        const int bady = ddy < 0 ? 0 : (ddy > 0 ? Hm : -1);
+        xsrc[pl] = xs_;
+        xvoff[pl] = xok ? (uint32_t)(2 * (r * S.C + (ddy * S.Ws + ddx) * S.C + xc) + (int)p2.xbias[xs_]) : OOB;
+        if (badx < 0) kxj[pl] = 0xffffffffu;
+        else if (d.W >= 64) kxj[pl] = (uint32_t)(badx - r);
+        else kxj[pl] = ((r & Wm) == badx) ? 0u : 0xffffffffu;
+        kyj[pl] = bady < 0 ? 0xffffffffu : (uint32_t)((bady - (r >> p2.lw)) & Hm);
+    }
+    const uint32_t ystep = (uint32_t)(2 * G.C), x0step = (uint32_t)(2 * d.src[0].C), x1step = (uint32_t)(2 * d.src[NSRC - 1].C);
+    const uint32_t mb0 = (uint32_t)m_begin;
+
+    // half-tile in LDS slot `slot` of K-tile `kt_`: 0 dY planes 0-1, 1 X planes 0-1, 2 X planes 2-3, 3 dY planes 2-3
+    // `valid` (wave-uniform) is false for halves past the end of the pixel range: they are issued all the same, out of range
+    // (zero fill into a slot nobody reads any more), so that the loop has no branches and one vmcnt count holds in every phase
+    auto issue_half = [&](int kt_, int slot, bool valid) {
+        unsigned char* dst = smem + (kt_ & 1) * P3_BUF + slot * P3_HALF + wave * 1024;
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            const uint32_t mb = mb0 + (uint32_t)kt_ * TP + 32u * hh;
+            if (slot == 0 || slot == 3) {
+                const uint32_t ysoff = mb * ystep;
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsy, (lds_ptr)(dst + i * PLANE + hh * 4096), 16, valid ? (slot == 0 ? yvoff[i] : yvoff[2 + i]) : OOB,
+                                                             ysoff, 0, 0);
+            } else {
+                const uint32_t sy = (mb >> p2.lw) & (uint32_t)Hm;
+                const uint32_t sx = mb & (uint32_t)Wm;
+                const uint32_t x0soff = mb * x0step, x1soff = mb * x1step;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int pl = (slot == 1 ? 0 : 2) + i;
+                    const bool ok = (sx != kxj[pl]) & (sy != kyj[pl]) & valid;
+                    const uint32_t off = ok ? xvoff[pl] : OOB;
+                    lds_ptr dp = (lds_ptr)(dst + i * PLANE + hh * 4096);
+                    const bool s1 = NSRC > 1 && xsrc[pl] != 0;          // wave-uniform: a select, not a branch
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(s1 ? rsx1 : rsx0, dp, 16, off, s1 ? x1soff : x0soff, 0, 0);
+                }
+            }
+        }
+    };
+
+    f32x4 acc[2][4][2][4];               // [mh][i][nh][j]
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[a][i][b][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    // transposing fragment reads: offsets inside a half (plane wr / wc of it; granule g of pixel row r at g ^ ((r>>1)&3))
+    const int trow = 4 * lq + (l15 >> 2);
+    const int tsw = (trow >> 1) & 3;
+    int goffA[4], goffB[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        goffA[a] = wr * PLANE + trow * 128 + ((a ^ tsw) << 5) + (l15 & 3) * 8;
+        goffB[a] = wc * PLANE + trow * 128 + ((a ^ tsw) << 5) + (l15 & 3) * 8;
+    }
+    act16x8 af[2][4][2], bfr[3][4][2];   // [mh | nh][16-wide tile][ks]; bfr[2]: X-lo of the NEXT K-tile
+    auto read_half = [&](int par, int slot, int bset) {
+        const unsigned char* hb = smem + par * P3_BUF + slot * P3_HALF;
+        if (slot == 0 || slot == 3) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) af[slot == 3][i][ks] = tr_frag128_nowait(hb + ks * 32 * 128 + goffA[i]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) bfr[bset][j][ks] = tr_frag128_nowait(hb + ks * 32 * 128 + goffB[j]);
+        }
+    };
+
+    // prologue: all eight slots issued, halves 0-2 landed, halves 0 and 1 read (they belong to "phases -2 and -1") and those
+    // reads retired by every wave before anything is staged over them (half 8 here with LEAD 9, else in phase 0)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) issue_half(q >> 2, q & 3, q < total_halves);
+    p3w_wait_halves<5>();
+    __builtin_amdgcn_s_barrier();
+    read_half(0, 0, 0);
+    read_half(0, 1, 2);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if constexpr (LEAD == 9) issue_half(2, 0, 8 < total_halves);
+
+    for (int kt_ = 0; kt_ < KT; ++kt_) {
+        const int par = kt_ & 1;
+        // X-lo was read into the spare set while the last quadrant still used the previous K-tile's
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) bfr[0][j][ks] = bfr[2][j][ks];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int g = 4 * kt_ + q;
+            const int mh = q >> 1;
+            const int nh = (q == 1 || q == 2) ? 1 : 0;
+            __builtin_amdgcn_sched_barrier(0);
+            issue_half(kt_ + ((q + LEAD) >> 2), (q + LEAD) & 3, g + LEAD < total_halves);
+            __builtin_amdgcn_sched_barrier(0);
+            // half g + 2 (past the end: a stale slot, never used)
+            if (q < 2) read_half(par, q + 2, 1);
+            else read_half(par ^ 1, q - 2, 2);
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        acc[mh][i][nh][j] = UCLSTM_MFMA_16x16x32(af[mh][i][ks], bfr[nh][j][ks], acc[mh][i][nh][j], 0, 0, 0);
+            // the 16 fragment reads go out between the first MFMAs, so that they have retired long before the barrier
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            }
+            __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            // half g + 3 has landed: halves g + 4 .. g + LEAD of this wave stay in flight
+            p3w_wait_halves<LEAD - 3>();
+            // LEAD 9 re-stages a half ONE phase after its reads: they are retired before the barrier
+            if constexpr (LEAD == 9) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the out-of-range halves of the last phases
+    __syncthreads();
+
+    // ---- accumulate into dWp: four passes of 64 panel rows, LDS-staged so that a wave instruction adds 64 consecutive floats
+    constexpr int AP = 256 + 4;
+    float* At = (float*)smem;                // [64 panel rows][AP] = 65 KiB
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+        const int mh = pass >> 1, pwr = pass & 1;
+        if (wr == pwr) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int nh = 0; nh < 2; ++nh)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            At[(i * 16 + lq * 4 + q) * AP + nh * 128 + wc * 64 + j * 16 + l15] = mh ? acc[1][i][nh][j][q] : acc[0][i][nh][j][q];
+        }
+        __syncthreads();
+        const int k = kbase + tid;
+        if (k < d.Ktot) {
+            for (int pr = 0; pr < 64; ++pr) {
+                const int n = n0 + mh * 128 + pwr * 64 + pr;
+                if (n < d.N) {
+                    float* dst = d.dwp + (long)sp * d.slab + (long)n * d.Ktot + k;
+                    if (d.slab > 0) *dst = At[pr * AP + tid];        // this pixel range's own slab (added up by the unpack kernel)
+                    else __hip_atomic_fetch_add(dst, At[pr * AP + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+        __syncthreads();
+    }
+#endif
+}
+
 // Splits for the one-block-per-CU kernel, two regimes (uclstm_wgrad_desc::overlapped):
 //  * stand-alone launch: whole rounds of the 256 CUs, every extra slab priced (written here, read back by the unpack);
 //  * launch that runs on a side stream next to the input-gradient chain: what the step needs from it is not a short kernel
@@ -1026,7 +1297,7 @@ bool wsrc_ok(const uclstm_src& s) {
 namespace {
 // plan_only: validate, choose kernel + splits and return the split count without launching (dwp may be null)
 // query: 0 = launch, 1 = return the pixel-range count (uclstm_igemm_wgrad_splits), 2 = return which kernel would run
-// (uclstm_igemm_wgrad_shape: 3 = 256 x 256 8-phase, 2 = 128 x 128, 1 = 64 x 256 for C_out <= 64, 0 = generic addressing)
+// (uclstm_igemm_wgrad_shape: 3 = 256 x 256, either wave count, 2 = 128 x 128, 1 = 64 x 256 for C_out <= 64, 0 = generic addressing)
 int32_t wgrad_run(const uclstm_wgrad_desc* dp, void* stream, int query) {
     const bool plan_only = query != 0;
     if (!dp) return UCLSTM_E_BADARG;
@@ -1102,7 +1373,7 @@ int32_t wgrad_run(const uclstm_wgrad_desc* dp, void* stream, int query) {
         p2.lh = ilog2(d.H);
     }
     static const bool no_p3 = [] { const char* e = getenv("UCLSTM_WGRAD_NO256"); return e && e[0] == '1'; }();
-    const bool big = fast && !no_p3 && d.N >= 256;              // 256 x 256 tile, 8-phase pipeline
+    const bool big = fast && !no_p3 && d.N >= 256;              // 256 x 256 tile (igemm_wgrad_p3w_kernel / igemm_wgrad_p3_kernel)
     static const bool no_192 = [] { const char* e = getenv("UCLSTM_WGRAD_NO192"); return e && e[0] == '1'; }();
     const int wn = (fast && d.N <= 64) ? ((!no_192 && d.Ktot % 192 == 0) ? 3 : 1) : 2;      // 3: 64 x 192 tile (no padding at K = 576 / 1152)
     const int tn = big ? 256 : (wn == 2 ? 128 : 64), tc = big ? 256 : (wn == 2 ? 128 : (wn == 3 ? 192 : 256));
@@ -1134,7 +1405,24 @@ int32_t wgrad_run(const uclstm_wgrad_desc* dp, void* stream, int query) {
             (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3_kernel<2, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
             (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3_kernel<1, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
             (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3_kernel<2, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
+            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3w_kernel<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
+            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3w_kernel<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
+            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3w_kernel<1, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
+            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3w_kernel<2, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
             attr3 = true;
+        }
+        // four waves x 128 x 128 is the default; UCLSTM_P3_WAVES=8 selects the 8-wave kernel (same tile, same plan, bit-identical
+        // slabs).  The deeper DMA ring of either kernel is its default, UCLSTM_P3_LEAD=6 the shallower one (8 of the 4-wave kernel)
+        static const bool waves8 = [] { const char* e = getenv("UCLSTM_P3_WAVES"); return e && e[0] == '8'; }();
+        if (!waves8) {
+            if (lead7) {
+                if (d.nsrc == 1) UCLSTM_LAUNCH((igemm_wgrad_p3w_kernel<1, 9>), dim3((unsigned)nblk), dim3(256), P3_SMEM, st, dd, dv, p2);
+                else UCLSTM_LAUNCH((igemm_wgrad_p3w_kernel<2, 9>), dim3((unsigned)nblk), dim3(256), P3_SMEM, st, dd, dv, p2);
+            } else {
+                if (d.nsrc == 1) UCLSTM_LAUNCH((igemm_wgrad_p3w_kernel<1, 8>), dim3((unsigned)nblk), dim3(256), P3_SMEM, st, dd, dv, p2);
+                else UCLSTM_LAUNCH((igemm_wgrad_p3w_kernel<2, 8>), dim3((unsigned)nblk), dim3(256), P3_SMEM, st, dd, dv, p2);
+            }
+            return UCLSTM_OK;
         }
         if (lead7) {
             if (d.nsrc == 1) UCLSTM_LAUNCH((igemm_wgrad_p3_kernel<1, 7>), dim3((unsigned)nblk), dim3(512), P3_SMEM, st, dd, dv, p2);
