@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define UCLSTM_ABI_VERSION 15
+#define UCLSTM_ABI_VERSION 16
 
 #define UCLSTM_OK            0
 #define UCLSTM_E_BADARG     -1   /* shape / alignment / null-pointer contract violated      */
@@ -369,7 +369,8 @@ int32_t uclstm_nhwc_to_nchw_f32(const float* a, float* out, int32_t n_img, int32
 /* ------------------------------------------------------------------------------------ */
 int32_t uclstm_outconv_fwd(const void* a, const float* w, const float* b, float* y,
                            int64_t n_img, int32_t HW, int32_t Cp, int32_t C, int32_t Co, void* stream);
-/* da bf16 [pixels][Cp]; dw [Co][C], db [Co] accumulate with atomics (caller zeroes). */
+/* da bf16 [pixels][Cp]; dw [Co][C], db [Co] accumulate with atomics (caller zeroes).  da NULL: no input gradient; dw or db
+ * NULL (frozen weight and bias): no parameter-gradient kernel. */
 int32_t uclstm_outconv_bwd(const void* a, const float* w, const float* dy, void* da, float* dw, float* db,
                            int64_t n_img, int32_t HW, int32_t Cp, int32_t C, int32_t Co, void* stream);
 
@@ -382,7 +383,7 @@ int32_t uclstm_outconv_bwd(const void* a, const float* w, const float* dy, void*
 int32_t uclstm_attention_fwd(const void* x, const float* w, void* out, float* att, float* desc, int32_t* argmax, int32_t n_img,
                              int32_t H, int32_t W, int32_t Cp, int32_t C, int32_t k, void* stream);
 /* dx bf16 = gradient w.r.t. x; dw f32 [2][k][k] = (dw_accumulate ? dw : 0) + weight gradient (deterministic block reductions);
- * scratch: f32 [3 * pixels + 2] work space. */
+ * scratch: f32 [3 * pixels + 2] work space.  dw NULL (frozen weight): the weight-gradient kernel is not launched. */
 int32_t uclstm_attention_bwd(const void* x, const void* dout, const float* w, const float* att, const float* desc,
                              const int32_t* argmax, void* dx, float* dw, int32_t dw_accumulate, float* scratch, int32_t n_img,
                              int32_t H, int32_t W, int32_t Cp, int32_t C, int32_t k, void* stream);
@@ -414,6 +415,25 @@ int32_t uclstm_adamw_step(float* p, float* m, float* v, const float* g, int64_t 
  * after the update.  Nothing about the launch depends on host state, so it can be captured in a HIP graph and replayed while a
  * scheduler changes lr between replays (one small host-to-device copy). */
 int32_t uclstm_adamw_step_dev(float* p, float* m, float* v, const float* g, int64_t n, const double* sumsq, float* hyper, void* stream);
+
+/* AdamW over parameter groups (per-group lr, betas, eps, weight_decay; ONE global gradient norm) in one sweep over the flat
+ * buffers, whatever the number of groups; hyper-parameters and the step count in DEVICE memory as for uclstm_adamw_step_dev,
+ * so the launch can be captured.  The flat layout is not sorted by group (it keeps the model's registration order), so
+ * groups interleave; two device tables say which element belongs where:
+ *   runs  = i64[n_runs][3] {begin, end, group}: half-open element ranges in ascending order, the first beginning at 0, each
+ *           beginning where the previous one ends, the last ending at n; 0 <= group < n_groups.  The CALLER checks this on the
+ *           host before the launch (the library cannot read a device table); neighbouring tensors of one group are one run.
+ *   hyper = f32[8 * (1 + n_groups)], 16-byte aligned: block 0 is global {max_norm (<= 0: no clipping), optimiser steps done
+ *           so far, reserved x 6}; block 1 + k belongs to group k {lr, beta1, beta2, eps, weight_decay, reserved x 3}.
+ * n_groups <= 1024.  sumsq as for uclstm_adamw_step (over ALL groups; may be NULL without clipping and scale_state).
+ * scale_state == NULL: bias corrections from hyper[1] + 1, computed as uclstm_adamw_step_dev does, and hyper[1] is
+ * incremented on the device after the sweep; with one run and one group the result equals uclstm_adamw_step_dev bit for bit.
+ * scale_state != NULL (DEVICE f32[3], layout below; sumsq required): the semantics of uclstm_adamw_step_scaled -- update
+ * on g / scale, clip on the unscaled norm, NOTHING is touched when *sumsq is not finite, the bias-correction step is
+ * scale_state[2] + 1 -- and hyper[1] is left alone: uclstm_loss_scale_update, still a launch of its own, counts the step. */
+int32_t uclstm_adamw_step_groups(float* p, float* m, float* v, const float* g, int64_t n, const double* sumsq,
+                                 const int64_t* runs, int32_t n_runs, float* hyper, int32_t n_groups,
+                                 const float* scale_state, void* stream);
 
 /* fp16 training (the _f16 twins below): the backward pass runs on loss * scale so that fp16 activation gradients stay out of
  * the subnormal range, and g holds scale x the true gradient.  scale_state = DEVICE f32[3] {scale, growth tracker, successful

@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UCLSTM_LIB") or os.path.join(HERE, "libuclstm.so")
 HEADER_PATH = os.path.join(HERE, "..", "include", "uclstm.h")
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 EPI_STORE, EPI_LSTM, EPI_ATOMIC = 0, 1, 2
 NMODE_IDENTITY, NMODE_LSTM, NMODE_TAPMAJOR = 0, 1, 2
 KMODE_IDENTITY, KMODE_GATES, KMODE_IM2COL = 0, 1, 2
@@ -143,6 +143,7 @@ _PROTOS = {
     "uclstm_sumsq": [_P, _L, _P, _P],
     "uclstm_adamw_step": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _F, _I, _P],
     "uclstm_adamw_step_dev": [_P, _P, _P, _P, _L, _P, _P, _P],
+    "uclstm_adamw_step_groups": [_P, _P, _P, _P, _L, _P, _P, _I, _P, _I, _P, _P],
     "uclstm_adamw_step_scaled": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _F, _P, _P],
     "uclstm_loss_scale_update": [_P, _P, _F, _F, _I, _P],
     "uclstm_dataset_transform": [_P, _P, _P, _P, _P, _L, _I, _I, _F, _F, _F, _I, _F, _F, _F, _P],

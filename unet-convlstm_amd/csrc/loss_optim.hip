@@ -193,6 +193,126 @@ __global__ void adamw_scaled_kernel(float* __restrict__ p, float* __restrict__ m
     }
 }
 
+// AdamW over parameter groups in ONE sweep.  runs = i64[n_runs][3] {begin, end, group}: ascending, gap-free, covering [0, n)
+// (the flat buffer keeps the model's registration order, so groups interleave).  hyper = f32[8 * (1 + n_groups)]: block 0 is
+// global {max_norm (<= 0: no clipping), steps done so far (exact up to 2^24), reserved x 6}, block 1 + k is group k
+// {lr, beta1, beta2, eps, weight_decay, reserved x 3}.  Every block first derives the groups' bias corrections into LDS (as
+// adamw_dev_kernel computes them).  A block then walks its grid-stride chunks in ascending order, so its run index only ever
+// moves forward: one binary search for the first chunk, after that a chunk inside the current run costs no table read at all,
+// and a lane reloads its six group values from LDS only where its group changes.  state (optional) = {scale, growth tracker,
+// successful steps}: the semantics of adamw_scaled_kernel, with the bias-correction step taken from state[2].
+__global__ void adamw_groups_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g,
+                                    int64_t n, const double* __restrict__ sumsq, const int64_t* __restrict__ runs, int n_runs,
+                                    const float* __restrict__ hyper, int n_groups, const float* __restrict__ state) {
+    // With one group the result must equal adamw_dev_kernel's bit for bit.  Which products of that kernel's update the compiler
+    // fuses into multiply-adds depends on the code around them, so here the fused ones are spelled out (they are the ones
+    // adamw_dev_kernel compiles to) and contraction is off for everything else.
+#pragma clang fp contract(off)
+    extern __shared__ float gh[];                                // [n_groups][8]: lr / bc1, b1, b2, eps, 1 - lr wd, 1 / sqrt(bc2), -, -
+    const float max_norm = hyper[0];
+    float coef = 1.f;
+    double step;
+    if (state) {
+        const double ss = *sumsq;
+        if (!(ss == ss) || ss > 1.0e300 || isinf(ss)) return;    // overflowed step: touch nothing (uniform over the grid)
+        const float inv_scale = 1.f / state[0];
+        step = (double)state[2] + 1.0;
+        coef = inv_scale;
+        if (max_norm > 0.f) {
+            const float total = (float)sqrt(ss) * inv_scale;
+            coef *= fminf(max_norm / (total + 1e-6f), 1.f);
+        }
+    } else {
+        step = (double)hyper[1] + 1.0;
+        if (sumsq && max_norm > 0.f) {
+            const float total = (float)sqrt(*sumsq);
+            coef = fminf(max_norm / (total + 1e-6f), 1.f);
+        }
+    }
+    for (int k = threadIdx.x; k < n_groups; k += NT) {
+        const float* h = hyper + 8 * (1 + k);
+        const float glr = h[0], gb1 = h[1], gb2 = h[2];
+        gh[8 * k + 0] = glr * (float)(1.0 / (1.0 - pow((double)gb1, step)));
+        gh[8 * k + 1] = gb1;
+        gh[8 * k + 2] = gb2;
+        gh[8 * k + 3] = h[3];
+        gh[8 * k + 4] = __builtin_fmaf(-glr, h[4], 1.f);                      // decoupled decay factor 1 - lr * wd
+        gh[8 * k + 5] = (float)(1.0 / sqrt(1.0 - pow((double)gb2, step)));
+    }
+    __syncthreads();
+    // A chunk is U * NT elements, lane t takes elements t, NT + t, ...: with one element per lane (adamw_dev_kernel's loop) the
+    // bytes in flight, 32 waves x 64 lanes x 16 B per CU, just cover HBM's latency; a full chunk issues all its 4 * U loads first.
+    constexpr int U = 4;
+    int64_t c0 = (int64_t)blockIdx.x * (U * NT);                 // first element of this block's current chunk
+    if (c0 >= n) return;
+    int r = 0;
+    for (int hi = n_runs - 1; r < hi;) {                         // last run whose begin <= c0
+        const int mid = (r + hi + 1) >> 1;
+        if (runs[3 * mid] <= c0) r = mid; else hi = mid - 1;
+    }
+    int64_t r_end = runs[3 * r + 1];
+    int r_grp = (int)runs[3 * r + 2];
+    int cur = -1;
+    float lr_bc1 = 0.f, b1 = 0.f, b2 = 0.f, eps = 1.f, decay = 1.f, inv_sqrt_bc2 = 0.f;
+    // A lane that walks the table waits for its table read with vmcnt(0), which also drains every store issued before: so a
+    // chunk's loads go out first, then all its lookups, then the updates and their stores (lookup in front of the loads was
+    // measured: +12 %, the previous chunk's stores had to land before anything new was in flight).
+    auto group_of = [&](int64_t i) {
+        int rt = r, grp = r_grp;
+        for (int64_t et = r_end; i >= et && rt + 1 < n_runs;) {  // only in a chunk that a run boundary crosses
+            ++rt;
+            et = runs[3 * rt + 1];
+            grp = (int)runs[3 * rt + 2];
+        }
+        return grp;
+    };
+    auto update = [&](int64_t i, int grp, float g_raw, float p_old, float m_old, float v_old) {
+        if (grp != cur) {
+            cur = grp;
+            const float* h = gh + 8 * min(max(grp, 0), n_groups - 1);
+            lr_bc1 = h[0], b1 = h[1], b2 = h[2], eps = h[3], decay = h[4], inv_sqrt_bc2 = h[5];
+        }
+        const float gi = g_raw * coef;
+        const float mi = __builtin_fmaf(1.f - b1, gi, b1 * m_old);
+        const float vi = b2 * v_old + ((1.f - b2) * gi) * gi;
+        const float denom = __builtin_fmaf(sqrtf(vi), inv_sqrt_bc2, eps);
+        p[i] = decay * p_old - (lr_bc1 * mi) / denom;
+        m[i] = mi;
+        v[i] = vi;
+    };
+    for (; c0 < n; c0 += (int64_t)gridDim.x * (U * NT)) {
+        while (c0 >= r_end && r + 1 < n_runs) {
+            ++r;
+            r_end = runs[3 * r + 1];
+            r_grp = (int)runs[3 * r + 2];
+        }
+        const int64_t i0 = c0 + threadIdx.x;
+        if (c0 + U * NT <= n) {                                  // a full chunk (uniform): no bounds test on the loads
+            float g_raw[U], p_old[U], m_old[U], v_old[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                g_raw[u] = g[i0 + u * NT];
+                p_old[u] = p[i0 + u * NT];
+                m_old[u] = m[i0 + u * NT];
+                v_old[u] = v[i0 + u * NT];
+            }
+            int grp[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) grp[u] = group_of(i0 + u * NT);
+#pragma unroll
+            for (int u = 0; u < U; ++u) update(i0 + u * NT, grp[u], g_raw[u], p_old[u], m_old[u], v_old[u]);
+        } else {                                                 // the buffer's last, partial chunk
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = i0 + u * NT;
+                if (i < n) update(i, group_of(i), g[i], p[i], m[i], v[i]);
+            }
+        }
+    }
+}
+__global__ void adamw_groups_advance_kernel(float* hyper) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) hyper[1] += 1.f;
+}
+
 __global__ void loss_scale_update_kernel(float* __restrict__ state, const double* __restrict__ sumsq, float growth, float backoff,
                                          int interval) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -308,6 +428,19 @@ extern "C" int32_t uclstm_adamw_step_scaled(float* p, float* m, float* v, const 
     if (!p || !m || !v || !g || n <= 0 || !sumsq || !scale_state) return UCLSTM_E_BADARG;
     UCLSTM_LAUNCH(adamw_scaled_kernel, dim3(grid_for(n, 2048)), dim3(NT), 0, (hipStream_t)stream, p, m, v, g, n, sumsq, max_norm, lr, beta1,
                   beta2, eps, weight_decay, scale_state);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_adamw_step_groups(float* p, float* m, float* v, const float* g, int64_t n, const double* sumsq,
+                                            const int64_t* runs, int32_t n_runs, float* hyper, int32_t n_groups,
+                                            const float* scale_state, void* stream) {
+    if (!p || !m || !v || !g || n <= 0 || !runs || n_runs <= 0 || !hyper || ((uintptr_t)hyper % 16) || n_groups <= 0 ||
+        n_groups > 1024 || (scale_state && !sumsq))
+        return UCLSTM_E_BADARG;
+    UCLSTM_LAUNCH(adamw_groups_kernel, dim3(grid_for((n + 3) / 4, 2048)), dim3(NT), (size_t)n_groups * 8 * sizeof(float), (hipStream_t)stream, p, m,
+                  v, g, n, sumsq, runs, n_runs, (const float*)hyper, n_groups, scale_state);
+    // with scale_state the step count is scale_state[2], advanced by uclstm_loss_scale_update
+    if (!scale_state) UCLSTM_LAUNCH(adamw_groups_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper);
     return UCLSTM_OK;
 }
 

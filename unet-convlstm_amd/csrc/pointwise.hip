@@ -2045,7 +2045,7 @@ extern "C" int32_t uclstm_attention_fwd(const void* x, const float* w, void* out
 extern "C" int32_t uclstm_attention_bwd(const void* x, const void* dout, const float* w, const float* att, const float* desc,
                                         const int32_t* argmax, void* dx, float* dw, int32_t dw_accumulate, float* scratch, int32_t n_img,
                                         int32_t H, int32_t W, int32_t Cp, int32_t C, int32_t k, void* stream) {
-    if (!aligned16(x) || !aligned16(dout) || !aligned16(dx) || !w || !att || !desc || !argmax || !dw || !scratch || n_img <= 0 || H <= 0 ||
+    if (!aligned16(x) || !aligned16(dout) || !aligned16(dx) || !w || !att || !desc || !argmax || !scratch || n_img <= 0 || H <= 0 ||
         W <= 0 || Cp <= 0 || (Cp % 8) || C <= 0 || C > Cp || k < 1 || !(k & 1) || k > 15 || ((uintptr_t)scratch % 8))
         return UCLSTM_E_BADARG;
     const int64_t pixels = (int64_t)n_img * H * W, chunks = pixels * (Cp / 8);
@@ -2056,7 +2056,7 @@ extern "C" int32_t uclstm_attention_bwd(const void* x, const void* dout, const f
     UCLSTM_LAUNCH(attn_bwd_dpre_kernel, dim3((unsigned)std::min<int64_t>((pixels + 3) / 4, 4096)), dim3(256), 0, st, (const uint4*)x,
                   (const uint4*)dout, att, dpre, pixels, Cp);
     UCLSTM_LAUNCH(attn_bwd_ddesc_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, dpre, w, ddesc, pixels, H, W, k);
-    UCLSTM_LAUNCH(attn_bwd_dw_kernel, dim3(2 * k * k), dim3(256), 0, st, dpre, desc, dw, pixels, H, W, k, dw_accumulate);
+    if (dw) UCLSTM_LAUNCH(attn_bwd_dw_kernel, dim3(2 * k * k), dim3(256), 0, st, dpre, desc, dw, pixels, H, W, k, dw_accumulate);
     UCLSTM_LAUNCH(attn_bwd_dx_kernel, dim3(ew_grid(chunks)), dim3(NT), 0, st, (const uint4*)dout, att, ddesc, argmax, (uint4*)dx, chunks,
                   make_fastdiv(Cp / 8), C);
     return UCLSTM_OK;

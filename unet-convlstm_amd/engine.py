@@ -213,7 +213,10 @@ class GraphedTrainStep:
     count from device memory (``FusedAdamW(capturable=True)``); the weight-gradient / BatchNorm side stream forks from and joins
     the capturing stream through events; the look-ahead panel packing uses a persistent job table.  Inputs are copied into
     static buffers; ``loss`` / ``y_pred`` are static outputs (valid until the next call).  Shapes, ``use_mask`` and the model's
-    mode are fixed at capture; ``clip_norm`` / lr changes reach the device through ``optimizer.sync_hyper()`` before a replay.
+    mode are fixed at capture; ``clip_norm`` / lr changes (of every parameter group) reach the device through
+    ``optimizer.sync_hyper()`` before a replay.  fp16 compute (``ops.compute_dtype(torch.float16)`` around construction and
+    calls, ``FusedAdamW(loss_scale=..., capturable=True)``): the loss scale, the overflow test, the skipped step and the scale
+    update all live on the device, so an overflowed replay leaves parameters and moments alone without the host knowing.
     Data-parallel training keeps the eager step (its collectives are launched from backward hooks)."""
 
     def __init__(self, model, optimizer, x, y, mask=None, use_mask: bool = True, clip_norm: Optional[float] = 1.0, warmup: int = 3):

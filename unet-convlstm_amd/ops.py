@@ -1319,7 +1319,8 @@ class ConvBNReLU(_GradAwareFunction):
                 if head_b is not None:
                     grad_written(head_b)
             else:
-                d_head_w, d_head_b = dwh, (dbh if head_b is not None else None)
+                d_head_w = dwh if ctx.needs_input_grad[15] else None
+                d_head_b = dbh if (head_b is not None and ctx.needs_input_grad[16]) else None
         elif ctx.pool and dp is not None and ctx.pool_fused:
             # pooling fused: the gradient of the activation is (skip gradient) + scatter(dp), formed inside the BatchNorm kernels
             dsk = None if da is None else da.contiguous()
@@ -1356,8 +1357,19 @@ class ConvBNReLU(_GradAwareFunction):
         # training: the conv bias feeds BatchNorm, which removes any per-channel constant -- its gradient is analytically 0.
         # With frozen statistics it is the column sum of dz.
         bias_grad = (lambda: colsum(dz)[:Co].contiguous()) if not training else (lambda: torch.zeros((Co,), dtype=F32, device=dev))
+        # a frozen parameter (requires_grad False: fine-tuning) gets nothing launched for it; weight, bias, gamma and beta are
+        # independent of each other
+        need_w, need_b, need_gamma, need_beta = ctx.needs_input_grad[2:6]
+        need_b = need_b and has_bias
         g_gamma, g_beta = direct_grad(gamma), direct_grad(beta)
-        if g_gamma is not None and g_beta is not None:
+        if not (need_gamma and need_beta):
+            dgamma = dbeta = None
+            if need_gamma or need_beta:
+                tot = sums.sum(dim=0)
+                dbeta = tot[:Co, 0].contiguous() if need_beta else None
+                dgamma = tot[:Co, 1].contiguous() if need_gamma else None
+            dbias = bias_grad() if need_b else None
+        elif g_gamma is not None and g_beta is not None:
             # one kernel accumulates straight into the attached gradient buffers (instead of sum + 2 copies + 2 accumulates).
             # Nothing in the backward pass waits for it: with the weight-gradient stream in use it goes there (18 small
             # dependent launches off the main stream; joined with the weight gradients at the end of backward).
@@ -1377,7 +1389,7 @@ class ConvBNReLU(_GradAwareFunction):
                 grad_written(beta)
             dgamma = dbeta = None
             dbias = None
-            if has_bias:
+            if need_b:
                 g_bias = direct_grad(bias)
                 if g_bias is not None:
                     if not training:
@@ -1389,10 +1401,12 @@ class ConvBNReLU(_GradAwareFunction):
             tot = sums.sum(dim=0)
             dbeta = tot[:Co, 0].contiguous()
             dgamma = tot[:Co, 1].contiguous()
-            dbias = bias_grad() if has_bias else None
+            dbias = bias_grad() if need_b else None
 
         dy_seg = [(dz, 0, Cop, 0, 1, 0, 0)]
-        if im2col:
+        if not need_w:
+            dweight = None
+        elif im2col:
             pd = im2col_pack_desc(Co, Ci_total, x0.shape[3])
             dweight = wgrad_into_param(weight, pd, [x0, dz], lambda: igemm_wgrad([SrcView(x0)], dy_seg, pd.N, pd.Ktot, (H, W), n_img,
                                                                                  ktap=1, pad=0))
@@ -1502,8 +1516,11 @@ class ConvT2x2(_GradAwareFunction):
         N, h, w, _ = x.shape
         pd = convt_pack_desc(Ci, Co)
         segs = [(du, t * Cop, (t + 1) * Cop, 0, 2, t // 2, t % 2) for t in range(4)]
-        dweight = wgrad_into_param(weight, pd, [x, du], lambda: igemm_wgrad([SrcView(x)], segs, pd.N, pd.Ktot, (h, w), N, ktap=1, pad=0))
-        dbias = bias_grad_from_colsum(du, bias, Co) if ctx.has_bias else None
+        dweight = dbias = None
+        if ctx.needs_input_grad[1]:          # not for a frozen weight
+            dweight = wgrad_into_param(weight, pd, [x, du], lambda: igemm_wgrad([SrcView(x)], segs, pd.N, pd.Ktot, (h, w), N, ktap=1, pad=0))
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            dbias = bias_grad_from_colsum(du, bias, Co)
         dx = None
         if ctx.needs_input_grad[0]:
             dd = convt_dgrad_pack_desc(Ci, Co)
@@ -1539,11 +1556,18 @@ class OutConv1x1(_GradAwareFunction):
         N, H, W, Cp = a.shape
         Co, Ci = weight.shape[0], weight.shape[1]
         da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        if not (need_w or need_b):
+            # weight and bias frozen: the library skips the dw / db kernel when given no buffers for them
+            if da is not None:
+                L.check(_k(a).uclstm_outconv_bwd(_p(a), _p(weight), _p(dy), _p(da), None, None, N, H * W, Cp, Ci, Co, _stream()),
+                        "outconv_bwd")
+            return da, None, None
         # the kernel ADDS its block sums into dw / db: with attached f32 gradients it adds straight into them (no zero-fill,
         # no accumulate kernels); the weight is a view [Co, Ci] of the parameter [Co, Ci, 1, 1], so is its gradient
         gw = direct_grad(weight)
         gb = direct_grad(bias) if ctx.has_bias else None
-        direct = gw is not None and (gb is not None or not ctx.has_bias) and gw.is_contiguous()
+        direct = need_w and gw is not None and (gb is not None or not ctx.has_bias) and gw.is_contiguous() and (need_b or not ctx.has_bias)
         dw = gw if direct else torch.zeros((Co, Ci), dtype=F32, device=a.device)
         db = gb if (direct and ctx.has_bias) else torch.zeros((Co,), dtype=F32, device=a.device)
         L.check(_k(a).uclstm_outconv_bwd(_p(a), _p(weight), _p(dy), _p(da), _p(dw), _p(db), N, H * W, Cp, Ci, Co, _stream()),
@@ -1553,7 +1577,7 @@ class OutConv1x1(_GradAwareFunction):
             if ctx.has_bias:
                 grad_written(bias)
             return da, None, None
-        return da, dw.view_as(weight), (db if ctx.has_bias else None)
+        return da, (dw.view_as(weight) if need_w else None), (db if need_b else None)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1589,8 +1613,9 @@ class SpatialAttn(_GradAwareFunction):
         k = weight.shape[-1]
         dx = torch.empty_like(x)
         scratch = torch.empty((3 * N * H * W + 2,), dtype=F32, device=x.device)
-        g = direct_grad(weight)
-        dw = g if g is not None else torch.empty_like(weight)
+        need_w = ctx.needs_input_grad[1]
+        g = direct_grad(weight) if need_w else None
+        dw = g if g is not None else (torch.empty_like(weight) if need_w else None)          # None (frozen weight): no dw kernel
         L.check(_k(x).uclstm_attention_bwd(_p(x), _p(dout), _p(weight), _p(att), _p(desc), _p(arg), _p(dx), _p(dw), int(g is not None),
                                            _p(scratch), N, H, W, Cp, ctx.channels, k, _stream()), "attention_bwd")
         if g is not None:
@@ -1742,12 +1767,14 @@ class ConvLSTMSeq(torch.autograd.Function):
         dg_flat = dgates.view(T * B, H, W, 4 * Hdp)
         x_flat = x_all.reshape(T * B, H, W, Cxp)
         hprev_flat = h_hist[:T].reshape(T * B, H, W, Hdp)
-        ud = lstm_wgrad_unpack_desc(Hd, Cx, ks)
-        dweight = wgrad_into_param(weight, ud, [x_all, h_hist, dgates],
-                                   lambda: igemm_wgrad([SrcView(x_flat), SrcView(hprev_flat)], [(dg_flat, 0, 4 * Hdp, 0, 1, 0, 0)],
-                                                       ud.N, ud.Ktot, (H, W), T * B, ktap=ks, pad=ks // 2))
+        dweight = None
+        if ctx.needs_input_grad[3]:          # a frozen gate weight launches neither the weight-gradient GEMM nor its un-pack
+            ud = lstm_wgrad_unpack_desc(Hd, Cx, ks)
+            dweight = wgrad_into_param(weight, ud, [x_all, h_hist, dgates],
+                                       lambda: igemm_wgrad([SrcView(x_flat), SrcView(hprev_flat)], [(dg_flat, 0, 4 * Hdp, 0, 1, 0, 0)],
+                                                           ud.N, ud.Ktot, (H, W), T * B, ktap=ks, pad=ks // 2))
         dbias = None
-        if has_bias:
+        if has_bias and ctx.needs_input_grad[4]:
             if Hdp == Hd:           # dgates columns are (gate, hidden channel) = the bias order of train/unet.py:29
                 dbias = bias_grad_from_colsum(dg_flat, bias, 4 * Hd)
             else:

@@ -8,9 +8,46 @@ reduction and one AdamW sweep that reads the clip coefficient on device, no host
 from __future__ import annotations
 
 import ctypes as C
-from typing import Iterable, List, Optional
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import torch
+
+
+def build_run_table(sizes: Sequence[int], groups: Sequence[int]) -> List[Tuple[int, int, int]]:
+    """Run table of ``uclstm_adamw_step_groups`` for tensors of ``sizes`` elements laid out one after the other, tensor ``i``
+    belonging to parameter group ``groups[i]``: ``(begin, end, group)`` element ranges in ascending order that cover
+    ``[0, sum(sizes))`` without a gap; neighbouring tensors of the same group are one run.  Pure bookkeeping, no device."""
+    if len(sizes) != len(groups):
+        raise ValueError("build_run_table: one group index per tensor")
+    runs: List[Tuple[int, int, int]] = []
+    off = 0
+    for n, g in zip(sizes, groups):
+        n, g = int(n), int(g)
+        if n <= 0 or g < 0:
+            raise ValueError("build_run_table: sizes must be positive and group indices non-negative")
+        if runs and runs[-1][2] == g:
+            runs[-1] = (runs[-1][0], off + n, g)
+        else:
+            runs.append((off, off + n, g))
+        off += n
+    return runs
+
+
+def check_run_table(runs: Sequence[Sequence[int]], n: int, n_groups: int) -> None:
+    """Raise ``ValueError`` unless ``runs`` is what the kernel may walk: non-empty runs, the first beginning at 0, each
+    beginning where the previous one ends, the last ending at ``n``, every group index in ``[0, n_groups)``.  The library
+    cannot check a device table, so this runs on the host before the table is uploaded."""
+    if not runs:
+        raise ValueError("run table: empty")
+    at = 0
+    for i, (b, e, g) in enumerate(runs):
+        if b != at or e <= b:
+            raise ValueError(f"run table: run {i} = [{b}, {e}) does not continue at {at} (runs must be sorted, non-empty and gap-free)")
+        if not 0 <= g < n_groups:
+            raise ValueError(f"run table: run {i} names group {g}, there are {n_groups}")
+        at = e
+    if at != n:
+        raise ValueError(f"run table: covers [0, {at}), the buffer has {n} elements")
 
 
 class FlatParams:
@@ -53,18 +90,38 @@ class FusedAdamW(torch.optim.Optimizer):
     Semantics equal ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` followed by
     ``torch.optim.AdamW.step()`` (main.py:106-108).  ``zero_grad`` keeps gradients as views of the
     flat buffer (``set_to_none`` is accepted and ignored).
+
+    ``params`` may be parameter groups with their own ``lr``, ``betas``, ``eps`` and ``weight_decay`` (``max_grad_norm`` stays
+    global: one norm over all trainable parameters).  All groups live in ONE flat buffer, laid out as ``order`` says (any
+    iterable of parameters, normally ``model.parameters()``: the layout of the single-group optimiser of that model, which
+    is what ``ddp.FlatDDP``'s bucket order is built on), else group after group.  Parameters with ``requires_grad=False`` are
+    left out.  More than one group, or ``capturable`` together with ``loss_scale``, runs ``uclstm_adamw_step_groups`` (one
+    sweep, a device table of runs, a device table of hyper-parameters); a single group keeps the entry points it always used.
     """
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm: Optional[float] = None,
                  loss_scale: Optional[float] = None, scale_growth: float = 2.0, scale_backoff: float = 0.5, scale_interval: int = 2000,
-                 capturable: bool = False):
+                 capturable: bool = False, order: Optional[Iterable[torch.nn.Parameter]] = None):
         params = list(params)
+        self._laid_out = False
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        if len(self.param_groups) != 1:
-            raise ValueError("FusedAdamW supports a single parameter group")
-        self.flat = FlatParams(self.param_groups[0]["params"])
+        group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
+        if order is None:
+            seq = [p for g in self.param_groups for p in g["params"]]
+        else:
+            seq = list(order)
+            if len({id(p) for p in seq}) != len(seq):
+                raise ValueError("FusedAdamW: a parameter appears twice in `order`")
+            if any(p.requires_grad and id(p) not in group_of for p in seq):
+                raise ValueError("FusedAdamW: a trainable parameter of `order` is in no parameter group")
+            missing = set(group_of) - {id(p) for p in seq}
+            if missing:
+                raise ValueError(f"FusedAdamW: {len(missing)} parameters of the groups are not in `order`")
+        self.flat = FlatParams(seq)
+        self._laid_out = True                       # the flat buffers exist: no add_param_group from here on
         if not self.flat.flat_p.is_cuda:
             raise RuntimeError("FusedAdamW needs HIP device parameters (no CPU path)")
+        self._tensor_groups = [group_of[id(p)] for p in self.flat.params]
         self.m = torch.zeros_like(self.flat.flat_p)
         self.v = torch.zeros_like(self.flat.flat_p)
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=self.flat.flat_p.device)
@@ -81,12 +138,41 @@ class FusedAdamW(torch.optim.Optimizer):
         # changed lr / max_grad_norm reaches the device through one small copy in sync_hyper(), outside the graph.
         self.capturable = bool(capturable)
         self.hyper = None
-        if self.capturable:
-            if loss_scale is not None:
-                raise ValueError("FusedAdamW(capturable=True) does not combine with loss scaling yet")
+        # Parameter groups, and a captured step with loss scaling: uclstm_adamw_step_groups.  ``runs`` = i64 [n_runs, 3]
+        # (begin, end, group) over the flat buffer, ``group_hyper`` = f32 [1 + groups, 8]: row 0 {max_norm, steps done}, row
+        # 1 + k {lr, beta1, beta2, eps, weight_decay} of group k (include/uclstm.h).  Also in eager mode: one implementation.
+        self.uses_groups = len(self.param_groups) > 1 or (self.capturable and loss_scale is not None)
+        self.runs = self.group_hyper = None
+        if self.uses_groups:
+            dev = self.flat.flat_p.device
+            table = build_run_table([p.numel() for p in self.flat.params], self._tensor_groups)
+            check_run_table(table, self.flat.numel, len(self.param_groups))
+            self.runs = torch.tensor(table, dtype=torch.int64).to(dev)
+            self.group_hyper = torch.zeros((1 + len(self.param_groups), 8), dtype=torch.float32, device=dev)
+            self._last_scale = torch.ones((), dtype=torch.float32, device=dev)
+            self._hyper_host = (None, None)
+            self.sync_hyper()
+        elif self.capturable:
             self.hyper = torch.zeros(8, dtype=torch.float32, device=self.flat.flat_p.device)
             self._hyper_host = None
             self.sync_hyper()
+
+    def add_param_group(self, param_group) -> None:
+        if getattr(self, "_laid_out", False):
+            raise RuntimeError("FusedAdamW.add_param_group: the flat buffers are laid out once, in __init__; build a new optimiser")
+        super().add_param_group(param_group)
+
+    def _group_values(self):
+        return tuple((float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+                     for g in self.param_groups)
+
+    def steps_done(self) -> int:
+        """Optimiser steps applied so far (with loss scaling: the successful ones).  Reads the device where the count lives."""
+        if self.uses_groups:
+            return int((self.group_hyper[0, 1] if self.scale_state is None else self.scale_state[2]).item())
+        if self.capturable:
+            return int(self.hyper[6].item())
+        return int(self.step_count)
 
     def _hyper_values(self):
         g = self.param_groups[0]
@@ -95,7 +181,18 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def sync_hyper(self) -> None:
         """Push lr / betas / eps / weight_decay / max_grad_norm to the device if they changed (capturable mode; never inside a
-        capture).  The device-side step count is left alone."""
+        capture).  The device-side step count is left alone.  With parameter groups: every group's values."""
+        if self.uses_groups:
+            vals, mx = self._group_values(), float(self.max_grad_norm or 0.0)
+            if (vals, mx) != self._hyper_host:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("FusedAdamW.sync_hyper() inside a graph capture: hyper-parameters must be synchronised before")
+                if vals != self._hyper_host[0]:
+                    self.group_hyper[1:, :5].copy_(torch.tensor(vals, dtype=torch.float32))
+                if mx != self._hyper_host[1]:
+                    self.group_hyper[0, :1].copy_(torch.tensor([mx], dtype=torch.float32))
+                self._hyper_host = (vals, mx)
+            return
         if not self.capturable:
             return
         vals = self._hyper_values()
@@ -112,11 +209,13 @@ class FusedAdamW(torch.optim.Optimizer):
     # otherwise a save / load / resume would silently restart Adam.
     def state_dict(self):
         sd = super().state_dict()
-        if self.capturable:
-            self.step_count = int(self.hyper[6].item())          # the device-side count is the truth in capturable mode
+        if self.capturable or self.uses_groups:
+            self.step_count = self.steps_done()                  # the device-side count is the truth in capturable mode
         sd["fused"] = {"exp_avg": self.m.detach().clone(), "exp_avg_sq": self.v.detach().clone(), "step": int(self.step_count),
                        "numel": int(self.flat.numel),
-                       "scale_state": None if self.scale_state is None else self.scale_state.detach().clone()}
+                       "scale_state": None if self.scale_state is None else self.scale_state.detach().clone(),
+                       # the layout of the flat buffers: a state saved with another grouping or order must not be loaded
+                       "sizes": [int(p.numel()) for p in self.flat.params], "tensor_groups": list(self._tensor_groups)}
         return sd
 
     def load_state_dict(self, state_dict) -> None:
@@ -125,11 +224,19 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError("FusedAdamW.load_state_dict: no 'fused' entry (not a FusedAdamW state_dict)")
         if int(fused["numel"]) != self.flat.numel:
             raise ValueError(f"FusedAdamW.load_state_dict: {fused['numel']} parameters saved, {self.flat.numel} here")
+        if "tensor_groups" in fused:
+            if (list(fused["tensor_groups"]) != list(self._tensor_groups)
+                    or list(fused["sizes"]) != [int(p.numel()) for p in self.flat.params]):
+                raise ValueError("FusedAdamW.load_state_dict: the state was saved with another parameter grouping / layout")
+        elif len(self.param_groups) != 1:
+            raise ValueError("FusedAdamW.load_state_dict: a single-group state cannot be loaded into parameter groups")
         super().load_state_dict({k: v for k, v in state_dict.items() if k != "fused"})
         self.m.copy_(fused["exp_avg"])
         self.v.copy_(fused["exp_avg_sq"])
         self.step_count = int(fused["step"])
-        if self.capturable:
+        if self.uses_groups:
+            self.group_hyper[0, 1] = float(self.step_count)
+        elif self.capturable:
             self.hyper[6] = float(self.step_count)
         if fused.get("scale_state") is not None and self.scale_state is not None:
             self.scale_state.copy_(fused["scale_state"])
@@ -153,6 +260,26 @@ class FusedAdamW(torch.optim.Optimizer):
         f = self.flat
         f.attach_grads()
         self.step_count += 1
+        if self.uses_groups:
+            if not torch.cuda.is_current_stream_capturing():
+                self.sync_hyper()
+            self.sumsq.zero_()
+            L.check(L.lib.uclstm_sumsq(C.c_void_p(f.flat_g.data_ptr()), f.numel, C.c_void_p(self.sumsq.data_ptr()), _stream()), "sumsq")
+            state = None
+            if self.scale_state is not None:
+                self._last_scale.copy_(self.scale_state[0])      # a buffer of its own: the scale update below overwrites the state
+                state = C.c_void_p(self.scale_state.data_ptr())
+            L.check(L.lib.uclstm_adamw_step_groups(C.c_void_p(f.flat_p.data_ptr()), C.c_void_p(self.m.data_ptr()), C.c_void_p(self.v.data_ptr()),
+                                                   C.c_void_p(f.flat_g.data_ptr()), f.numel, C.c_void_p(self.sumsq.data_ptr()),
+                                                   C.c_void_p(self.runs.data_ptr()), int(self.runs.shape[0]),
+                                                   C.c_void_p(self.group_hyper.data_ptr()), len(self.param_groups), state, _stream()),
+                    "adamw_step_groups")
+            if state is not None:
+                gr, bo, it = self._scale_cfg
+                L.check(L.lib.uclstm_loss_scale_update(state, C.c_void_p(self.sumsq.data_ptr()), gr, bo, it, _stream()), "loss_scale_update")
+            from . import ops
+            ops.weights_changed()
+            return None
         if self.scale_state is not None:
             self.sumsq.zero_()
             self._last_scale = self.scale_state[0].clone()
