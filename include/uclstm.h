@@ -461,6 +461,58 @@ int32_t uclstm_dataset_transform(const float* x_raw, const float* y_raw, float* 
 int32_t uclstm_metric_sums(const float* y_pred, const float* y, const float* mask, double* sums, int64_t n, float y_scale,
                            float trans_min, float trans_max, void* stream);
 
+/* Evaluation report of train/get_metrics.py:117-358 and test.py:333-351 in one pass over f32 y_pred / y / mask (mask may be
+ * NULL; a pixel counts when mask != 0).  Each tensor is [B][T] frames of P = C*H*W contiguous elements, addressed as
+ * base + b * stride_b + t * stride_t (elements, >= 0): the model's stacked output, a transposed view of a [T,B,...] buffer, is
+ * read in place.  16-byte loads are used when P % 4 == 0 and every base and stride is a multiple of 4 elements.
+ * Prediction and target are de-normalised in f32 (train/unet.py NPZSequenceDataset.denormalize): yt = (v + 1) / 2 *
+ * (trans_max - trans_min) + trans_min, then by `transform`; d = pred - target.
+ *   table      f64 [uclstm_eval_stats_rows(P, B*T)][UCLSTM_EVAL_ROW], WRITTEN (not accumulated) by this call: frame f = b*T + t
+ *              owns rows f*cpf .. (f+1)*cpf - 1 (cpf = rows / (B*T)), one per chunk of the plane; a row is
+ *              {n, sum|d|, sum d^2, sum d, sum gt, sum gt^2, sum pred, sum pred^2, min gt, max gt, min pred, max pred, min d,
+ *              max d, 0, 0}; a row without a valid pixel holds n = 0, min = +inf, max = -inf.  Rows depend on the inputs only
+ *              (no floating-point atomics): summing the rows of a frame in index order is bitwise reproducible.
+ *   hist       u64 [3][bins], ACCUMULATED: np.histogram(x, bins, range) counts of gt and pred over [hist_lo, hist_hi] and of d
+ *              over [err_lo, err_hi] (outside: dropped; x == upper edge: last bin).
+ *   dig_count  u64 [n_edges + 1], ACCUMULATED: counts of np.digitize(gt, edges), edges[i] = dig_lo + i * dig_w, i < n_edges
+ *              (index 0: below the first edge, n_edges: at or above the last).
+ *   scatter    f32 [n_edges + 1][K][2] (8-byte aligned; NULL when K == 0): per digitize bin a uniform sample of up to K
+ *              (gt, pred) pairs over everything added so far -- the pixel with ticket t (its rank in the bin, from dig_count)
+ *              goes to slot t while t < K, afterwards to slot j = hash(seed, bin, t) reduced to [0, t] when j < K (reservoir
+ *              sampling).  Slots [0, min(dig_count[bin], K)) are filled; which pairs survive depends on the order in which
+ *              blocks arrive.  hist, dig_count and scatter must be zeroed by the caller before the first call.
+ * Counters that fit 60 KiB of LDS (3 * bins + 3 * (n_edges + 1) words) are kept per block and flushed once; larger
+ * configurations count with one global integer atomic per pixel and counter (correct, slow). */
+#define UCLSTM_EVAL_ROW         16
+#define UCLSTM_EVAL_NONE         0
+#define UCLSTM_EVAL_ASINH        1
+#define UCLSTM_EVAL_SIGNED_LOG   2
+typedef struct {
+    const float* y_pred; int64_t pred_stride_b, pred_stride_t;
+    const float* y;      int64_t y_stride_b, y_stride_t;
+    const float* mask;   int64_t mask_stride_b, mask_stride_t;
+    int32_t B, T;
+    int64_t P;
+    int32_t transform;                 /* UCLSTM_EVAL_* */
+    float y_scale, trans_min, trans_max;
+    double* table;
+    int32_t bins, n_edges;
+    double hist_lo, hist_hi, err_lo, err_hi;
+    double dig_lo, dig_w;
+    uint64_t* hist;
+    uint64_t* dig_count;
+    float* scatter;
+    uint64_t seed;
+    int32_t K, reserved_;
+} uclstm_eval_desc;
+/* UCLSTM_E_BADARG before any launch for: a NULL descriptor / y_pred / y / table / hist / dig_count (or scatter with K > 0),
+ * P <= 0, B or T <= 0, bins outside [1, 4096], hi <= lo, dig_w <= 0, n_edges outside [2, 65536], K < 0, an unknown transform,
+ * a negative stride, B*T*P >= 2^31 or >= 2^24 rows. */
+int32_t uclstm_eval_stats(const uclstm_eval_desc* d, void* stream);
+/* Rows of `table` one uclstm_eval_stats call over `frames` frames of P elements writes (a function of P and frames only), or
+ * UCLSTM_E_BADARG. */
+int64_t uclstm_eval_stats_rows(int64_t P, int64_t frames);
+
 /* Scheduling aid, no reference counterpart: one wavefront that busy-waits `microseconds` of the constant 100 MHz wall clock on
  * `stream`.  The host layer uses it to find out whether two HIP streams really execute concurrently (streams that the
  * runtime multiplexes onto the same hardware queue serialise; which streams collide changes when e.g. an RCCL

@@ -88,6 +88,22 @@ class PackJob(C.Structure):
                 ("div", C.c_uint32 * 15), ("pad_", C.c_int32)]
 
 
+class EvalDesc(C.Structure):
+    _fields_ = [("y_pred", C.c_void_p), ("pred_stride_b", C.c_int64), ("pred_stride_t", C.c_int64),
+                ("y", C.c_void_p), ("y_stride_b", C.c_int64), ("y_stride_t", C.c_int64),
+                ("mask", C.c_void_p), ("mask_stride_b", C.c_int64), ("mask_stride_t", C.c_int64),
+                ("B", C.c_int32), ("T", C.c_int32), ("P", C.c_int64),
+                ("transform", C.c_int32), ("y_scale", C.c_float), ("trans_min", C.c_float), ("trans_max", C.c_float),
+                ("table", C.c_void_p), ("bins", C.c_int32), ("n_edges", C.c_int32),
+                ("hist_lo", C.c_double), ("hist_hi", C.c_double), ("err_lo", C.c_double), ("err_hi", C.c_double),
+                ("dig_lo", C.c_double), ("dig_w", C.c_double),
+                ("hist", C.c_void_p), ("dig_count", C.c_void_p), ("scatter", C.c_void_p),
+                ("seed", C.c_uint64), ("K", C.c_int32), ("reserved_", C.c_int32)]
+
+
+EVAL_ROW = 16
+EVAL_NONE, EVAL_ASINH, EVAL_SIGNED_LOG = 0, 1, 2
+
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> argtypes (restype int32 unless listed in _RESTYPES)
@@ -148,13 +164,16 @@ _PROTOS = {
     "uclstm_loss_scale_update": [_P, _P, _F, _F, _I, _P],
     "uclstm_dataset_transform": [_P, _P, _P, _P, _P, _L, _I, _I, _F, _F, _F, _I, _F, _F, _F, _P],
     "uclstm_metric_sums": [_P, _P, _P, _P, _L, _F, _F, _F, _P],
+    "uclstm_eval_stats": [C.POINTER(EvalDesc), _P],
+    "uclstm_eval_stats_rows": [_L, _L],
     "uclstm_stream_spin": [_I, _P],
     "uclstm_abi_version": [],
     "uclstm_build_arch": [],
     "uclstm_source_hash": [],
     "uclstm_last_error_string": [],
 }
-_RESTYPES = {"uclstm_build_arch": C.c_char_p, "uclstm_source_hash": C.c_char_p, "uclstm_last_error_string": C.c_char_p, "uclstm_bn_bwd_reduce_rows": C.c_int64, "uclstm_bn_pool_bwd_rows": C.c_int64}
+_RESTYPES = {"uclstm_build_arch": C.c_char_p, "uclstm_source_hash": C.c_char_p, "uclstm_last_error_string": C.c_char_p, "uclstm_bn_bwd_reduce_rows": C.c_int64, "uclstm_bn_pool_bwd_rows": C.c_int64,
+             "uclstm_eval_stats_rows": C.c_int64}
 
 
 # entry points that exist twice: name (bfloat16) and name_f16 (IEEE binary16), identical signatures (include/uclstm.h)

@@ -1,0 +1,355 @@
+// Evaluation statistics of train/get_metrics.py:117-358 and test.py:333-351 in ONE pass over (y_pred, y, mask): de-normalise,
+// per-(frame, chunk) f64 sums and min/max rows, three np.histogram-style histograms, the np.digitize count of the target and
+// the "up to K points per target bin" scatter sample as a reservoir.  Traffic: 8 B (12 B with a mask) per pixel, read once; what
+// bounds the kernel is recorded in DESIGN.md section 3 and profiles/eval_report.txt.
+//
+// Reproducibility: a block owns one chunk of one frame (the chunk size depends on nothing but this file), every thread owns
+// fixed pixels of it, and the row is reduced in a fixed order and written with plain stores -- no floating-point atomic
+// anywhere.  Counts are integers: LDS u32 counters per block, flushed with 64-bit integer atomics (sums of integers do not
+// depend on the order).  Only WHICH pairs the reservoir keeps depends on the arrival order of blocks.
+#include "common.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int PPT = 8;                           // pixels per thread
+constexpr int CHUNK = NT * PPT;                  // pixels of one frame per block: 2048 (a 512 x 512 frame is 128 blocks)
+constexpr int ROW = UCLSTM_EVAL_ROW;             // doubles per table row
+constexpr size_t LDS_BUDGET = 60 * 1024;         // counters beyond this live in global memory (per-pixel integer atomics)
+
+struct Args {
+    const float* yp;
+    const float* y;
+    const float* mask;
+    int64_t yp_sb, yp_st, y_sb, y_st, m_sb, m_st;
+    FastDiv dT, dCpf;                            // frame -> (b, t), block -> (frame, chunk)
+    int P;
+    int transform;
+    float yscale, tmin, trange;
+    double* table;
+    int bins;
+    double h_lo, h_hi, h_step, h_norm;           // np.histogram: edges lo + i * step (last = hi), first guess (x - lo) * norm
+    double e_lo, e_hi, e_step, e_norm;
+    unsigned long long* hist;                    // [3][bins]
+    double d_lo, d_w, d_inv_w, d_last;           // np.digitize over edges lo + i * w, i < n_edges
+    int n_edges;
+    unsigned long long* dig;                     // [n_edges + 1]
+    int K;
+    unsigned long long seed;
+    float2* scatter;                             // [n_edges + 1][K]
+};
+
+__device__ __forceinline__ float denorm(float v, const Args& a) {
+    const float yt = (v + 1.f) * 0.5f * a.trange + a.tmin;      // as metric_sums_kernel
+    if (a.transform == UCLSTM_EVAL_ASINH) return sinhf(yt) * a.yscale;
+    if (a.transform == UCLSTM_EVAL_SIGNED_LOG) {
+        const float s = (yt > 0.f) ? 1.f : ((yt < 0.f) ? -1.f : 0.f);
+        return s * expm1f(fabsf(yt)) * a.yscale;
+    }
+    return yt;
+}
+
+// np.histogram(x, bins, range=(lo, hi)): -1 when x is outside [lo, hi] (or NaN); x == hi belongs to the last bin.  numpy
+// guesses the bin from (x - lo) * norm and then corrects it against the edges themselves; so does this.
+__device__ __forceinline__ int hist_bin(float xf, double lo, double hi, double step, double norm, int bins) {
+    const double x = (double)xf;
+    if (!(x >= lo && x <= hi)) return -1;
+    int k = (int)((x - lo) * norm);
+    k = min(k, bins - 1);
+    const double e0 = lo + (double)k * step;
+    const double e1 = (k + 1 == bins) ? hi : lo + (double)(k + 1) * step;
+    if (x < e0 && k > 0) --k;
+    else if (x >= e1 && k + 1 < bins) ++k;
+    return k;
+}
+
+// np.digitize(x, edges): number of edges <= x, 0 .. n_edges (NaN sorts behind the last edge)
+__device__ __forceinline__ int digitize_bin(float xf, const Args& a) {
+    const double x = (double)xf;
+    if (x < a.d_lo) return 0;
+    if (!(x < a.d_last)) return a.n_edges;
+    int k = (int)((x - a.d_lo) * a.d_inv_w);                     // edges[k] <= x < edges[k + 1], up to rounding of the quotient
+    k = min(max(k, 0), a.n_edges - 2);
+    if (x < a.d_lo + (double)k * a.d_w) --k;
+    else if (x >= a.d_lo + (double)(k + 1) * a.d_w) ++k;
+    return k + 1;
+}
+
+// counter[bin] += 1 for every lane with act, returning the lane's rank (the counter before its own increment) when RANK.
+// Cloud data is skewed -- most lanes of a wave hit ONE bin, and 64 LDS atomics on one address are executed one after the
+// other -- so up to TRIES times the bin of the first pending lane is looked at: a group of >= 8 lanes is added by its leader
+// as one atomic and ranked by lane order; smaller groups and whatever is left take one atomic per lane.  Must be called by
+// whole waves (act = false for lanes with nothing to add).
+template <bool RANK, int TRIES>
+__device__ __forceinline__ uint32_t count_in_lds(uint32_t* cnt, int bin, bool act) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    bool pending = act;
+    uint32_t rank = 0;
+#pragma unroll
+    for (int t = 0; t < TRIES; ++t) {
+        const uint64_t todo = __ballot(pending);
+        if (!todo) break;
+        const int lead = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)todo) - 1);
+        const int cand = __builtin_amdgcn_readlane(bin, lead);
+        const bool mine = pending && bin == cand;
+        const uint64_t m = __ballot(mine);
+        const int n = __popcll(m);
+        if (n >= 8) {
+            uint32_t base = 0;
+            if (lane == lead) base = atomicAdd(cnt + cand, (uint32_t)n);
+            if (RANK) {
+                base = __builtin_amdgcn_readlane(base, lead);
+                if (mine) rank = base + (uint32_t)__popcll(m & lt);
+            }
+        } else if (mine) {
+            rank = atomicAdd(cnt + bin, 1u);
+        }
+        pending = pending && !mine;
+    }
+    if (pending) rank = atomicAdd(cnt + bin, 1u);
+    return rank;
+}
+
+// counter-based hash of (seed, bin, ticket): splitmix64's finaliser over the mixed key
+__device__ __forceinline__ uint64_t hash3(uint64_t seed, uint32_t bin, uint64_t t) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (t + 1) + 0xD1B54A32D192ED03ull * (uint64_t)(bin + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// Reservoir sampling (algorithm R) with the ticket as the item index: the first K tickets of a bin fill its slots, ticket
+// t >= K replaces slot j = hash mod (t + 1) when j < K.  The reduction of the 64-bit hash to [0, t] is the high half of
+// hash * (t + 1): the same uniform slot as a remainder, without a 64-bit division per pixel.  One 8-byte store per pair.
+// Stores of one launch land in any order: a replacement that hashed to slot j < K can be overtaken by the FILL of ticket j
+// from another block of the same launch and is then lost, so while a bin's first K tickets are still in flight the sample
+// leans slightly towards them; it is exactly uniform over the pixels of later launches (stream order), approximately within
+// the launch that fills the bin.
+__device__ __forceinline__ void scatter_store(const Args& a, int bin, uint64_t t, float gt, float pr) {
+    uint64_t slot = t;
+    if (t >= (uint64_t)a.K) slot = __umul64hi(hash3(a.seed, (uint32_t)bin, t), t + 1);
+    if (slot < (uint64_t)a.K) a.scatter[(int64_t)bin * a.K + (int64_t)slot] = make_float2(gt, pr);
+}
+
+template <bool VEC, bool LDS>
+__global__ __launch_bounds__(NT) void eval_stats_kernel(const Args a) {
+    extern __shared__ uint32_t sm[];             // LDS: hist gt | pred | err [bins], digitize [nd], bases lo | hi [nd]
+    __shared__ double red_s[4][8];
+    __shared__ float red_m[4][6];
+    const int nd = a.n_edges + 1;
+    uint32_t* h_gt = sm;
+    uint32_t* h_pr = sm + a.bins;
+    uint32_t* h_er = sm + 2 * a.bins;
+    uint32_t* dg = sm + 3 * a.bins;
+    uint32_t* base_lo = dg + nd;
+    uint32_t* base_hi = base_lo + nd;
+    if (LDS) {
+        for (int i = threadIdx.x; i < 3 * a.bins + nd; i += NT) sm[i] = 0u;
+        __syncthreads();
+    }
+
+    const uint32_t frame = fdiv(blockIdx.x, a.dCpf);
+    const int chunk = (int)(blockIdx.x - frame * a.dCpf.d);
+    const uint32_t b = fdiv(frame, a.dT);
+    const uint32_t t = frame - b * a.dT.d;
+    const int p0 = chunk * CHUNK;
+    const float* yp = a.yp + (int64_t)b * a.yp_sb + (int64_t)t * a.yp_st + p0;
+    const float* yy = a.y + (int64_t)b * a.y_sb + (int64_t)t * a.y_st + p0;
+    const float* mk = a.mask ? a.mask + (int64_t)b * a.m_sb + (int64_t)t * a.m_st + p0 : nullptr;
+    const int left = a.P - p0;                   // pixels of this chunk: > 0, the last chunk of a frame may be partial
+
+    float vp[PPT], vy[PPT];
+    bool ok[PPT];
+    if (VEC) {                                   // P % 4 == 0, bases and strides 16-byte aligned: a quad is inside or outside
+#pragma unroll
+        for (int q = 0; q < PPT / 4; ++q) {
+            const int o = (q * NT + (int)threadIdx.x) * 4;
+            const bool in = o < left;
+            float4 p4 = make_float4(0.f, 0.f, 0.f, 0.f), y4 = p4, m4 = make_float4(1.f, 1.f, 1.f, 1.f);
+            if (in) {
+                p4 = *(const float4*)(yp + o);
+                y4 = *(const float4*)(yy + o);
+                if (mk) m4 = *(const float4*)(mk + o);
+            }
+            vp[4 * q + 0] = p4.x, vp[4 * q + 1] = p4.y, vp[4 * q + 2] = p4.z, vp[4 * q + 3] = p4.w;
+            vy[4 * q + 0] = y4.x, vy[4 * q + 1] = y4.y, vy[4 * q + 2] = y4.z, vy[4 * q + 3] = y4.w;
+            ok[4 * q + 0] = in && m4.x != 0.f, ok[4 * q + 1] = in && m4.y != 0.f;
+            ok[4 * q + 2] = in && m4.z != 0.f, ok[4 * q + 3] = in && m4.w != 0.f;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < PPT; ++q) {
+            const int o = q * NT + (int)threadIdx.x;
+            const bool in = o < left;
+            vp[q] = in ? yp[o] : 0.f;
+            vy[q] = in ? yy[o] : 0.f;
+            ok[q] = in && (mk ? mk[o] != 0.f : true);
+        }
+    }
+
+    double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // n, |d|, d^2, d, gt, gt^2, pred, pred^2
+    const float inf = __builtin_inff();
+    float mn_g = inf, mx_g = -inf, mn_p = inf, mx_p = -inf, mn_d = inf, mx_d = -inf;
+    int dbin[PPT];
+    uint32_t rank[PPT];
+    uint64_t ticket[PPT];                        // !LDS only
+#pragma unroll
+    for (int q = 0; q < PPT; ++q) {
+        const float pr = denorm(vp[q], a), gt = denorm(vy[q], a);
+        const float df = pr - gt;
+        vp[q] = pr, vy[q] = gt;
+        const bool v = ok[q];
+        if (v) {
+            const double d = (double)df, g = (double)gt, p = (double)pr;
+            s[0] += 1.0, s[1] += fabs(d), s[2] += d * d, s[3] += d;
+            s[4] += g, s[5] += g * g, s[6] += p, s[7] += p * p;
+            mn_g = fminf(mn_g, gt), mx_g = fmaxf(mx_g, gt);
+            mn_p = fminf(mn_p, pr), mx_p = fmaxf(mx_p, pr);
+            mn_d = fminf(mn_d, df), mx_d = fmaxf(mx_d, df);
+        }
+        const int bg = v ? hist_bin(gt, a.h_lo, a.h_hi, a.h_step, a.h_norm, a.bins) : -1;
+        const int bp = v ? hist_bin(pr, a.h_lo, a.h_hi, a.h_step, a.h_norm, a.bins) : -1;
+        const int be = v ? hist_bin(df, a.e_lo, a.e_hi, a.e_step, a.e_norm, a.bins) : -1;
+        dbin[q] = v ? digitize_bin(gt, a) : -1;
+        if (LDS) {
+            count_in_lds<false, 2>(h_gt, bg, bg >= 0);
+            count_in_lds<false, 1>(h_pr, bp, bp >= 0);
+            count_in_lds<false, 1>(h_er, be, be >= 0);
+            rank[q] = count_in_lds<true, 2>(dg, dbin[q], v);
+        } else {
+            if (bg >= 0) atomicAdd(a.hist + bg, 1ull);
+            if (bp >= 0) atomicAdd(a.hist + a.bins + bp, 1ull);
+            if (be >= 0) atomicAdd(a.hist + 2 * a.bins + be, 1ull);
+            ticket[q] = v ? atomicAdd(a.dig + dbin[q], 1ull) : 0ull;
+        }
+    }
+
+    // the chunk's row: lanes -> wave (xor shuffles), waves -> block in wave order
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        mn_g = fminf(mn_g, __shfl_xor(mn_g, o, 64)), mx_g = fmaxf(mx_g, __shfl_xor(mx_g, o, 64));
+        mn_p = fminf(mn_p, __shfl_xor(mn_p, o, 64)), mx_p = fmaxf(mx_p, __shfl_xor(mx_p, o, 64));
+        mn_d = fminf(mn_d, __shfl_xor(mn_d, o, 64)), mx_d = fmaxf(mx_d, __shfl_xor(mx_d, o, 64));
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) red_s[wave][k] = s[k];
+        red_m[wave][0] = mn_g, red_m[wave][1] = mx_g, red_m[wave][2] = mn_p;
+        red_m[wave][3] = mx_p, red_m[wave][4] = mn_d, red_m[wave][5] = mx_d;
+    }
+    __syncthreads();                             // also: every LDS counter of the chunk is final
+    if (threadIdx.x < ROW) {
+        const int k = threadIdx.x;
+        double v = 0.0;
+        if (k < 8) {
+            v = ((red_s[0][k] + red_s[1][k]) + red_s[2][k]) + red_s[3][k];
+        } else if (k < 14) {
+            const int j = k - 8;
+            const float m0 = red_m[0][j], m1 = red_m[1][j], m2 = red_m[2][j], m3 = red_m[3][j];
+            v = (double)((j & 1) ? fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)) : fminf(fminf(m0, m1), fminf(m2, m3)));
+        }
+        a.table[(int64_t)blockIdx.x * ROW + k] = v;
+    }
+
+    if (LDS) {
+        for (int i = threadIdx.x; i < 3 * a.bins; i += NT) {
+            const uint32_t c = sm[i];
+            if (c) atomicAdd(a.hist + i, (unsigned long long)c);
+        }
+        // one reservation per (block, non-empty target bin): tickets base .. base + c - 1 belong to this block
+        for (int i = threadIdx.x; i < nd; i += NT) {
+            const uint32_t c = dg[i];
+            if (!c) continue;
+            if (a.K > 0) {
+                const unsigned long long base = atomicAdd(a.dig + i, (unsigned long long)c);
+                base_lo[i] = (uint32_t)base;
+                base_hi[i] = (uint32_t)(base >> 32);
+            } else {
+                atomicAdd(a.dig + i, (unsigned long long)c);
+            }
+        }
+        if (a.K > 0) {
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < PPT; ++q) {
+                const int bin = dbin[q];
+                if (bin < 0) continue;
+                const uint64_t base = ((uint64_t)base_hi[bin] << 32) | base_lo[bin];
+                scatter_store(a, bin, base + rank[q], vy[q], vp[q]);
+            }
+        }
+    } else if (a.K > 0) {
+#pragma unroll
+        for (int q = 0; q < PPT; ++q)
+            if (dbin[q] >= 0) scatter_store(a, dbin[q], ticket[q], vy[q], vp[q]);
+    }
+}
+
+int64_t rows_for(int64_t P, int64_t frames) { return frames * ((P + CHUNK - 1) / CHUNK); }
+
+}  // namespace
+
+extern "C" int64_t uclstm_eval_stats_rows(int64_t P, int64_t frames) {
+    if (P <= 0 || frames <= 0 || P >= ((int64_t)1 << 31) || frames >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    return rows_for(P, frames);
+}
+
+extern "C" int32_t uclstm_eval_stats(const uclstm_eval_desc* d, void* stream) {
+    if (!d || !d->y_pred || !d->y || !d->table || !d->hist || !d->dig_count) return UCLSTM_E_BADARG;
+    if (d->P <= 0 || d->B <= 0 || d->T <= 0) return UCLSTM_E_BADARG;
+    if (d->bins < 1 || d->bins > 4096 || !(d->hist_hi > d->hist_lo) || !(d->err_hi > d->err_lo)) return UCLSTM_E_BADARG;
+    if (!(d->dig_w > 0.0) || !(d->dig_lo == d->dig_lo) || d->n_edges < 2 || d->n_edges > 65536) return UCLSTM_E_BADARG;
+    if (d->K < 0 || (d->K > 0 && (!d->scatter || ((uintptr_t)d->scatter % 8)))) return UCLSTM_E_BADARG;
+    if (d->transform != UCLSTM_EVAL_NONE && d->transform != UCLSTM_EVAL_ASINH && d->transform != UCLSTM_EVAL_SIGNED_LOG)
+        return UCLSTM_E_BADARG;
+    if (d->transform != UCLSTM_EVAL_NONE && d->y_scale == 0.f) return UCLSTM_E_BADARG;
+    if (d->pred_stride_b < 0 || d->pred_stride_t < 0 || d->y_stride_b < 0 || d->y_stride_t < 0 ||
+        (d->mask && (d->mask_stride_b < 0 || d->mask_stride_t < 0)))
+        return UCLSTM_E_BADARG;
+    const int64_t lim = (int64_t)1 << 31;
+    if (d->P >= lim) return UCLSTM_E_BADARG;
+    const int64_t frames = (int64_t)d->B * d->T;
+    if (frames >= lim || frames * d->P >= lim) return UCLSTM_E_BADARG;
+    const int64_t cpf = (d->P + CHUNK - 1) / CHUNK;
+    const int64_t rows = frames * cpf;
+    if (rows * NT >= ((int64_t)1 << 32)) return UCLSTM_E_BADARG;        // one block per row, in grid.x
+
+    Args a;
+    a.yp = d->y_pred, a.y = d->y, a.mask = d->mask;
+    a.yp_sb = d->pred_stride_b, a.yp_st = d->pred_stride_t, a.y_sb = d->y_stride_b, a.y_st = d->y_stride_t;
+    a.m_sb = d->mask ? d->mask_stride_b : 0, a.m_st = d->mask ? d->mask_stride_t : 0;
+    a.dT = make_fastdiv((uint32_t)d->T), a.dCpf = make_fastdiv((uint32_t)cpf);
+    a.P = (int)d->P;
+    a.transform = d->transform;
+    a.yscale = d->y_scale, a.tmin = d->trans_min, a.trange = d->trans_max - d->trans_min;
+    a.table = d->table;
+    a.bins = d->bins;
+    a.h_lo = d->hist_lo, a.h_hi = d->hist_hi, a.h_step = (d->hist_hi - d->hist_lo) / d->bins, a.h_norm = d->bins / (d->hist_hi - d->hist_lo);
+    a.e_lo = d->err_lo, a.e_hi = d->err_hi, a.e_step = (d->err_hi - d->err_lo) / d->bins, a.e_norm = d->bins / (d->err_hi - d->err_lo);
+    a.hist = (unsigned long long*)d->hist;
+    a.d_lo = d->dig_lo, a.d_w = d->dig_w, a.d_inv_w = 1.0 / d->dig_w, a.d_last = d->dig_lo + (double)(d->n_edges - 1) * d->dig_w;
+    a.n_edges = d->n_edges;
+    a.dig = (unsigned long long*)d->dig_count;
+    a.K = d->K, a.seed = d->seed, a.scatter = (float2*)d->scatter;
+
+    auto quad = [](const float* p, int64_t sb, int64_t st) { return !p || (((uintptr_t)p % 16) == 0 && sb % 4 == 0 && st % 4 == 0); };
+    const bool vec = d->P % 4 == 0 && quad(d->y_pred, a.yp_sb, a.yp_st) && quad(d->y, a.y_sb, a.y_st) && quad(d->mask, a.m_sb, a.m_st);
+    const size_t lds = ((size_t)3 * d->bins + (size_t)3 * (d->n_edges + 1)) * sizeof(uint32_t);
+    const bool in_lds = lds <= LDS_BUDGET;
+    const dim3 grid((unsigned)rows), block(NT);
+    hipStream_t s = (hipStream_t)stream;
+    if (in_lds) {
+        if (vec) UCLSTM_LAUNCH((eval_stats_kernel<true, true>), grid, block, lds, s, a);
+        else UCLSTM_LAUNCH((eval_stats_kernel<false, true>), grid, block, lds, s, a);
+    } else {
+        if (vec) UCLSTM_LAUNCH((eval_stats_kernel<true, false>), grid, block, 0, s, a);
+        else UCLSTM_LAUNCH((eval_stats_kernel<false, false>), grid, block, 0, s, a);
+    }
+    return UCLSTM_OK;
+}

@@ -341,3 +341,211 @@ def evaluate(model, loader, device, dataset_obj, use_mask=True):
         met.add(dataset_obj, y, y_pred, mask, use_mask)
     mae, rmse, me = met.result()
     return float(total) / max(n, 1), mae, rmse, me
+
+
+# ---------------------------------------------------------------------------------------------
+# evaluation report (train/get_metrics.py, test.py: the statistics, not the figures)
+# ---------------------------------------------------------------------------------------------
+_TRANSFORM_IDS = {None: 0, "none": 0, "asinh": 1, "signed_log": 2}
+
+
+class EvalReport:
+    """The statistics of the reference's evaluation scripts, accumulated on the device by ONE kernel per batch
+    (``uclstm_eval_stats``): global MAE / RMSE / bias / error std (train/get_metrics.py:188-191), MAE per time step
+    (``:281-297``), the three 100-bin histograms (``:317-358``), the ``np.digitize`` count of the target and the balanced
+    "up to ``points_per_bin`` random points per target bin" scatter sample (``:210-231``), and the per-frame sums behind
+    test.py:333-351.  The defaults are the reference's constants (get_metrics.py:55-59, :317, :354).
+
+    ``add`` launches and returns; ``result`` synchronises once.  ``y_pred`` may be the transposed view the model returns:
+    f32 tensors whose ``[C,H,W]`` planes are contiguous are read in place through their batch / time strides (the model's
+    output is such a tensor).  Any other input costs one extra pass before the kernel: a tensor of another dtype (a bf16 /
+    f16 output) is converted with ``.float()``, one whose planes are not contiguous is copied with ``.contiguous()``;
+    ``last_copies`` says how many of the last ``add``'s tensors took that path (0 = everything was read in place).  All sums are f64
+    and bitwise reproducible; which pairs the scatter sample keeps is not (the reference's ``np.random.choice`` is unseeded
+    too), its per-bin fill counts are exact.
+    """
+
+    ROW = 16
+    SUMS = ("n", "sum_abs", "sum_sq", "sum")          # the last axis of result()["per_sequence"]
+
+    def __init__(self, dataset_obj, hist_bins=100, hist_range=(-7.5, 7.5), err_range=(-3.0, 3.0), scatter_range=(-8.0, 8.0),
+                 scatter_bin_width=0.05, points_per_bin=1000, seed=0, device="cuda"):
+        tr = getattr(dataset_obj, "y_transform", None)
+        if tr not in _TRANSFORM_IDS:
+            raise ValueError(f"EvalReport: unknown y_transform {tr!r}")
+        self.transform = _TRANSFORM_IDS[tr]
+        self.y_scale = float(getattr(dataset_obj, "y_scale", 1.0))
+        self.trans_min, self.trans_max = float(dataset_obj.trans_min), float(dataset_obj.trans_max)
+        self.hist_bins = int(hist_bins)
+        self.hist_range = (float(hist_range[0]), float(hist_range[1]))
+        self.err_range = (float(err_range[0]), float(err_range[1]))
+        self.points_per_bin, self.seed = int(points_per_bin), int(seed)
+        self.scatter_edges = self.make_scatter_edges(scatter_range, scatter_bin_width)
+        if not (1 <= self.hist_bins <= 4096) or not (2 <= len(self.scatter_edges) <= 65536) or self.points_per_bin < 0:
+            raise ValueError("EvalReport: hist_bins in [1, 4096], 2..65536 scatter edges and points_per_bin >= 0 are required")
+        self.device = torch.device(device)
+        self._hist = self._dig = self._scatter = None          # device buffers, allocated by the first add()
+        self._tables = []                                      # per add(): (f64 [rows, ROW] device tensor, B, T)
+        self.last_pointers = None                              # (y_pred, y, mask) addresses handed to the library by the last add()
+        self.last_copies = 0                                   # how many of the last add()'s tensors were converted or copied first
+
+    @staticmethod
+    def make_scatter_edges(scatter_range, width) -> np.ndarray:
+        """get_metrics.py:210: ``np.arange(lo, hi + width, width)`` in f64 (321 edges for the defaults)."""
+        return np.arange(float(scatter_range[0]), float(scatter_range[1]) + float(width), float(width), dtype=np.float64)
+
+    @staticmethod
+    def _planes(t: torch.Tensor, what: str) -> torch.Tensor:
+        """f32 ``[B,T,C,H,W]`` device tensor whose frames are contiguous planes; anything else is converted / copied once."""
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ops.L.UclstmError(f"EvalReport.add: {what}: a HIP device tensor is required (this package has no CPU path)")
+        if t.dim() != 5:
+            raise ops.L.UclstmError(f"EvalReport.add: {what}: expected [B,T,C,H,W], got {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            t = t.float()
+        want, ok = 1, t.stride(0) >= 0 and t.stride(1) >= 0
+        for dim in (4, 3, 2):
+            ok = ok and (t.size(dim) == 1 or t.stride(dim) == want)
+            want *= t.size(dim)
+        return t if ok else t.contiguous()
+
+    def _describe(self, yp, yt, m):
+        """The descriptor of one launch over validated tensors, and the table it writes (buffers are allocated on first use)."""
+        from . import _lib as L
+        B, T = yt.shape[:2]
+        P = yt.shape[2] * yt.shape[3] * yt.shape[4]
+        dev = yt.device
+        if self._hist is None:
+            nd = len(self.scatter_edges) + 1
+            self._hist = torch.zeros((3, self.hist_bins), dtype=torch.int64, device=dev)
+            self._dig = torch.zeros(nd, dtype=torch.int64, device=dev)
+            self._scatter = torch.zeros((nd, max(self.points_per_bin, 1), 2), dtype=torch.float32, device=dev)
+        rows = int(L.lib.uclstm_eval_stats_rows(P, B * T))
+        if rows <= 0:
+            raise L.UclstmError(f"EvalReport.add: bad plane / frame count ({P}, {B * T})")
+        table = torch.empty((rows, self.ROW), dtype=torch.float64, device=dev)
+        d = L.EvalDesc()
+        d.y_pred, d.pred_stride_b, d.pred_stride_t = yp.data_ptr(), yp.stride(0), yp.stride(1)
+        d.y, d.y_stride_b, d.y_stride_t = yt.data_ptr(), yt.stride(0), yt.stride(1)
+        if m is not None:
+            d.mask, d.mask_stride_b, d.mask_stride_t = m.data_ptr(), m.stride(0), m.stride(1)
+        d.B, d.T, d.P = B, T, P
+        d.transform, d.y_scale, d.trans_min, d.trans_max = self.transform, self.y_scale, self.trans_min, self.trans_max
+        d.table = table.data_ptr()
+        d.bins, d.n_edges = self.hist_bins, len(self.scatter_edges)
+        (d.hist_lo, d.hist_hi), (d.err_lo, d.err_hi) = self.hist_range, self.err_range
+        d.dig_lo, d.dig_w = float(self.scatter_edges[0]), float(self.scatter_edges[1] - self.scatter_edges[0])
+        d.hist, d.dig_count = self._hist.data_ptr(), self._dig.data_ptr()
+        d.scatter = self._scatter.data_ptr() if self.points_per_bin > 0 else None
+        d.seed, d.K = self.seed & 0xFFFFFFFFFFFFFFFF, self.points_per_bin
+        return d, table
+
+    @torch.no_grad()
+    def add(self, y, y_pred, mask=None, use_mask=False):
+        from . import _lib as L
+        yp, yt = self._planes(y_pred, "y_pred"), self._planes(y, "y")
+        m = self._planes(mask, "mask") if (use_mask and mask is not None) else None
+        self.last_copies = int(yp is not y_pred) + int(yt is not y) + int(m is not None and m is not mask)
+        if yp.shape != yt.shape or (m is not None and m.shape != yt.shape):
+            raise L.UclstmError(f"EvalReport.add: shapes differ: y_pred {tuple(yp.shape)}, y {tuple(yt.shape)}"
+                                + ("" if m is None else f", mask {tuple(m.shape)}"))
+        B, T = yt.shape[:2]
+        if self._tables and self._tables[0][2] != T:
+            raise L.UclstmError(f"EvalReport.add: sequences of {T} frames after sequences of {self._tables[0][2]}")
+        d, table = self._describe(yp, yt, m)
+        L.check(L.lib.uclstm_eval_stats(d, ops._stream()), "eval_stats")
+        self.last_pointers = (yp.data_ptr(), yt.data_ptr(), None if m is None else m.data_ptr())
+        self._tables.append((table, B, T))
+
+    def result(self) -> dict:
+        """One synchronisation: every buffer is copied to pinned host memory on the current stream, then reduced on the host."""
+        if not self._tables:
+            raise ops.L.UclstmError("EvalReport.result: nothing was added")
+        srcs = [t for t, _, _ in self._tables] + [self._hist, self._dig, self._scatter]
+        host = [torch.empty(s.shape, dtype=s.dtype, pin_memory=True) for s in srcs]
+        for h, s in zip(host, srcs):
+            h.copy_(s, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        tables = [h.numpy().reshape(B, T, -1, self.ROW) for h, (_, B, T) in zip(host, self._tables)]
+        hist, dig, scatter = (h.numpy() for h in host[len(tables):])
+        return self.reduce(tables, hist, dig, scatter, hist_range=self.hist_range, err_range=self.err_range,
+                           scatter_edges=self.scatter_edges, points_per_bin=self.points_per_bin)
+
+    @staticmethod
+    def reduce(tables, hist, dig_count, scatter, *, hist_range, err_range, scatter_edges, points_per_bin) -> dict:
+        """Raw tables -> report, on numpy arrays alone.  ``tables``: one f64 ``[B, T, chunks, ROW]`` array per ``add`` (rows as
+        ``uclstm_eval_stats`` writes them); ``hist`` ``[3, bins]``, ``dig_count`` ``[n_edges + 1]``, ``scatter``
+        ``[n_edges + 1, K, 2]``.  Rows are combined in a fixed order: chunks of a frame, then sequences, then time steps.
+        Standard deviations are population ones (``np.std``), from the f64 sums: sqrt(E[x^2] - E[x]^2)."""
+        frames = np.concatenate([np.asarray(t, dtype=np.float64).sum(axis=2) for t in tables], axis=0)       # [N, T, ROW] sums
+        lo = np.concatenate([np.asarray(t, dtype=np.float64)[..., 8:14:2].min(axis=2) for t in tables], axis=0)
+        hi = np.concatenate([np.asarray(t, dtype=np.float64)[..., 9:14:2].max(axis=2) for t in tables], axis=0)
+        per_t = frames.sum(axis=0)                                                                           # [T, ROW]
+        g = per_t.sum(axis=0)
+        n = float(g[0])
+
+        def mean_std(s1, s2):
+            if n <= 0:
+                return 0.0, 0.0
+            mu = s1 / n
+            return float(mu), float(math.sqrt(max(s2 / n - mu * mu, 0.0)))
+
+        def ratio(a, b, root=False):
+            out = np.divide(a, b, out=np.zeros_like(a), where=b > 0)
+            return np.sqrt(out) if root else out
+
+        mean_err, std_err = mean_std(g[3], g[2])
+        gt_mean, gt_std = mean_std(g[4], g[5])
+        pred_mean, pred_std = mean_std(g[6], g[7])
+        mn, mx = lo.min(axis=(0, 1)), hi.max(axis=(0, 1))
+        hist = np.asarray(hist).astype(np.int64)
+        dig_count = np.asarray(dig_count).astype(np.int64)
+        K = int(points_per_bin)
+        filled = np.minimum(dig_count, K)
+        sc = np.asarray(scatter)
+        sel = np.arange(sc.shape[1])[None, :] < filled[:, None] if K > 0 else np.zeros(sc.shape[:2], dtype=bool)
+        nt = per_t[:, 0]
+        return {
+            "n": n,
+            "mae": float(g[1] / n) if n > 0 else 0.0,
+            "rmse": float(math.sqrt(g[2] / n)) if n > 0 else 0.0,
+            "mean_err": mean_err, "std_err": std_err,
+            "gt_mean": gt_mean, "gt_std": gt_std, "gt_min": float(mn[0]), "gt_max": float(mx[0]),
+            "pred_mean": pred_mean, "pred_std": pred_std, "pred_min": float(mn[1]), "pred_max": float(mx[1]),
+            "err_min": float(mn[2]), "err_max": float(mx[2]),
+            "per_timestep": {"n": nt.copy(), "mae": ratio(per_t[:, 1], nt), "rmse": ratio(per_t[:, 2], nt, root=True),
+                             "mean_err": ratio(per_t[:, 3], nt)},
+            "per_sequence": frames[..., :4].copy(),
+            "hist_gt": hist[0], "hist_pred": hist[1], "hist_err": hist[2],
+            "hist_edges": np.linspace(hist_range[0], hist_range[1], hist.shape[1] + 1),
+            "err_edges": np.linspace(err_range[0], err_range[1], hist.shape[1] + 1),
+            "scatter_edges": np.asarray(scatter_edges, dtype=np.float64),
+            "gt_bin_count": dig_count,
+            "scatter_gt": sc[..., 0][sel], "scatter_pred": sc[..., 1][sel],
+            "scatter_bin": np.broadcast_to(np.arange(sc.shape[0])[:, None], sc.shape[:2])[sel],
+        }
+
+
+@torch.no_grad()
+def evaluate_report(model, loader, device, dataset_obj, use_mask=True, **report_kwargs):
+    """``evaluate()``'s loop with an ``EvalReport`` fed from the same ``y_pred``: returns ``(avg_loss, mae, rmse, me, report)``.
+    The first four are computed as ``evaluate`` computes them, from the same launches as the report (``report`` is the dict
+    of ``EvalReport.result``).  Against a SEPARATE ``evaluate()`` pass they agree as far as ``evaluate`` agrees with itself:
+    its loss and metric kernels add block partials with f64 atomics in arrival order, so two passes can differ in the last
+    bits (~1e-13 relative); the report's own sums do not have that freedom."""
+    model.eval()
+    total = torch.zeros((), dtype=torch.float64, device=device)
+    n = 0
+    met = _Metrics(device)
+    rep = EvalReport(dataset_obj, device=device, **report_kwargs)
+    for x, y, mask in loader:
+        x, y, mask = x.to(device, non_blocking=True), y.to(device, non_blocking=True), mask.to(device, non_blocking=True)
+        output, _ = model(x)
+        y_pred = _stack(output)
+        loss = compute_loss(y_pred, y, mask, use_mask)
+        total += loss.double() * x.size(0)
+        n += x.size(0)
+        met.add(dataset_obj, y, y_pred, mask, use_mask)
+        rep.add(y, y_pred, mask, use_mask)
+    mae, rmse, me = met.result()
+    return float(total) / max(n, 1), mae, rmse, me, rep.result()
