@@ -125,6 +125,52 @@ def test_argument_contracts_are_checked_before_launch():
         L.check(-1, "x")
 
 
+def test_fused_batchnorm_and_lstm_pointwise_contracts_are_checked_before_launch():
+    """The shape contracts of the kernels tests/test_gpu_pointwise_abi.py calls directly: every pointer is non-null and 16-byte
+    aligned (never dereferenced: nothing is launched), so UCLSTM_E_BADARG can only come from the shape."""
+    P = C.c_void_p(1 << 20)
+    for K in (L.lib, L.lib16):
+        #                  n_img H  W  Cp    groups
+        for geom in ((4, 5, 4, 8, 2),          # odd H
+                     (4, 4, 7, 8, 2),          # odd W
+                     (5, 4, 4, 8, 2),          # n_img % groups != 0
+                     (4, 4, 4, 12, 2),         # Cp % 8 != 0
+                     (4, 4, 4, 2056, 2)):      # Cp / 8 > 256: more chunk columns than threads
+            assert K.uclstm_bn_apply_relu_pool(P, P, P, P, P, *geom, None) == -1, geom
+            assert K.uclstm_bn_pool_bwd_reduce(P, P, P, P, P, P, P, P, P, *geom, None) == -1, geom
+            assert K.uclstm_bn_pool_bwd_apply(P, P, P, P, P, P, P, P, P, *geom, None) == -1, geom
+        #                  pixels ppg Cp   C
+        for geom in ((100, 50, 24, 24),        # 3 lanes per pixel: not a power of two
+                     (100, 50, 1024, 1024),    # 128 lanes: more than a wave
+                     (100, 50, 64, 65),        # C > Cp
+                     (100, 30, 64, 64)):       # pixels % pixels_per_group != 0
+            assert K.uclstm_bn_head_fwd(P, P, P, P, P, P, *geom, None) == -1, geom
+            assert K.uclstm_bn_head_bwd_reduce(P, P, P, P, P, P, P, P, P, P, P, *geom, None) == -1, geom
+            assert K.uclstm_bn_head_bwd_apply(P, P, P, P, P, P, P, P, P, *geom, None) == -1, geom
+        # f32 dh_b: at least one slab, and a slab stride of whole float4
+        assert K.uclstm_lstm_bwd_pointwise(P, P, P, P, P, 1, 0, 0, P, 0, P, 10, 8, None) == -1
+        assert K.uclstm_lstm_bwd_pointwise(P, P, P, P, P, 1, 3, 82, P, 0, P, 10, 8, None) == -1
+        assert K.uclstm_lstm_bwd_pointwise(P, P, P, P, P, 2, 3, 82, P, 0, P, 10, 8, None) == -1
+    for geom in ((4, 5, 4, 8, 2), (4, 4, 7, 8, 2), (5, 4, 4, 8, 2), (4, 4, 4, 12, 2), (4, 4, 4, 2056, 2)):
+        assert L.lib.uclstm_bn_pool_bwd_rows(*geom) == -1, geom
+    assert L.lib.uclstm_bn_pool_bwd_rows(4, 4, 4, 8, 2) == 2 and L.lib.uclstm_bn_pool_bwd_rows(2, 4, 4, 2048, 2) == 2
+
+
+def test_pool_backward_block_plan_of_the_parity_shapes():
+    """Rows of `partials` per group = min(ceil(windows per group / 32), max(1, 4096 // groups)) for every shape of the direct pool
+    tests: the block boundaries those shapes are chosen for (a block ending inside an image, a ragged last block, the cap, empty
+    trailing blocks) are really where the comments say."""
+    from test_gpu_pointwise_abi import POOL_SHAPES
+    for n_img, H, W, Cp, groups in POOL_SHAPES:
+        wpg = (n_img // groups) * (H // 2) * (W // 2)
+        rows = L.lib.uclstm_bn_pool_bwd_rows(n_img, H, W, Cp, groups)
+        assert rows > 0 and rows % groups == 0, (n_img, H, W, Cp, groups)
+        assert rows // groups == min(-(-wpg // 32), max(1, 4096 // groups)), (n_img, H, W, Cp, groups)
+    plan = {s: L.lib.uclstm_bn_pool_bwd_rows(*s) // s[4] for s in POOL_SHAPES}
+    assert plan[(4, 14, 6, 64, 2)] == 2 and plan[(2, 2, 66, 8, 1)] == 3 and plan[(1100, 20, 20, 8, 1100)] == 3
+    assert plan[(2, 700, 400, 8, 1)] == 4096                  # 140000 windows: 4000 blocks of 35, the last 96 empty
+
+
 def test_pack_descriptors_geometry():
     d = ops.conv_pack_desc(40, 24 + 8, [24, 8], [24, 8])
     assert (d.N, d.taps, d.kseg[0], d.kseg[1], d.Ktot) == (40, 9, 64, 64, 9 * 128)

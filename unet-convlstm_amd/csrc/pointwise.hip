@@ -23,6 +23,20 @@ __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
     for (int i = 0; i < 8; ++i) p.e[i] = f32_to_act(f[i]);
     return p.u;
 }
+// act16(a * b) as a kernel that STORES the product would leave it: one IEEE f32 multiplication, then one conversion (two
+// roundings).  The fp16 build otherwise selects v_fma_mixlo_f16 for some instances of this expression and v_mul_f32 + v_cvt_f16_f32
+// for others of the same kernel (bn_head_bwd_reduce_kernel: 8 of 40), and the two differ by one fp16 unit where the f32 product
+// lies next to an fp16 rounding boundary: the reduction then sums another da than the apply kernel subtracts it from, and than
+// outconv_bwd_da_kernel stores.  The empty asm makes the f32 product a value of its own; it emits nothing.  Call it BEFORE a select on
+// the ReLU mask, never inside one: the compiler does not speculate inline asm, and `mask ? act16_product(..) : 0` becomes a
+// divergent branch per element (62 instead of 22 branches and 228 B of scratch in the fp16 reduction).
+__device__ __forceinline__ float act16_product(float a, float b) {
+    float p = a * b;
+#ifdef UCLSTM_ACT_F16
+    asm("" : "+v"(p));
+#endif
+    return act_to_f32(f32_to_act(p));
+}
 __device__ __forceinline__ void load8f(const float* p, float (&f)[8]) {
     const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
     f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
@@ -782,7 +796,8 @@ __global__ void bn_head_bwd_reduce_kernel(const uint4* __restrict__ z, const flo
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const float yv = zv[i] * sc[i] + sh[i];
-                    const float g0 = yv > 0.f ? act_to_f32(f32_to_act(gq[u] * wr[i])) : 0.f;
+                    const float dap = act16_product(gq[u], wr[i]);        // before the select: see act16_product
+                    const float g0 = yv > 0.f ? dap : 0.f;
                     s1[i] += g0;
                     s2[i] += g0 * (zv[i] - mu[i]) * rs[i];
                     sw[i] += gq[u] * act_to_f32(f32_to_act(fmaxf(yv, 0.f)));
@@ -797,7 +812,8 @@ __global__ void bn_head_bwd_reduce_kernel(const uint4* __restrict__ z, const flo
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const float yv = zv[i] * sc[i] + sh[i];
-                const float g0 = yv > 0.f ? act_to_f32(f32_to_act(gd * wr[i])) : 0.f;
+                const float dap = act16_product(gd, wr[i]);
+                const float g0 = yv > 0.f ? dap : 0.f;
                 s1[i] += g0;
                 s2[i] += g0 * (zv[i] - mu[i]) * rs[i];
                 sw[i] += gd * act_to_f32(f32_to_act(fmaxf(yv, 0.f)));
@@ -868,8 +884,9 @@ __global__ void bn_head_bwd_apply_kernel(const uint4* __restrict__ z, const floa
         unpack8(zb, zw);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            oa[i] = ((zv[i] * sc[i] + sh[i] > 0.f) ? sc[i] * act_to_f32(f32_to_act(ga * wr[i])) : 0.f) + k1[i] * zv[i] + k0[i];
-            ob[i] = ((zw[i] * sc[i] + sh[i] > 0.f) ? sc[i] * act_to_f32(f32_to_act(gb * wr[i])) : 0.f) + k1[i] * zw[i] + k0[i];
+            const float da = act16_product(ga, wr[i]), db = act16_product(gb, wr[i]);       // before the selects: see act16_product
+            oa[i] = ((zv[i] * sc[i] + sh[i] > 0.f) ? sc[i] * da : 0.f) + k1[i] * zv[i] + k0[i];
+            ob[i] = ((zw[i] * sc[i] + sh[i] > 0.f) ? sc[i] * db : 0.f) + k1[i] * zw[i] + k0[i];
         }
         dz[ia] = pack8(oa);
         dz[ib] = pack8(ob);
@@ -880,8 +897,10 @@ __global__ void bn_head_bwd_apply_kernel(const uint4* __restrict__ z, const floa
         unpack8(z[ia], zv);
         const float ga = dy[p];
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-            oa[i] = ((zv[i] * sc[i] + sh[i] > 0.f) ? sc[i] * act_to_f32(f32_to_act(ga * wr[i])) : 0.f) + k1[i] * zv[i] + k0[i];
+        for (int i = 0; i < 8; ++i) {
+            const float da = act16_product(ga, wr[i]);
+            oa[i] = ((zv[i] * sc[i] + sh[i] > 0.f) ? sc[i] * da : 0.f) + k1[i] * zv[i] + k0[i];
+        }
         dz[ia] = pack8(oa);
     }
 }
