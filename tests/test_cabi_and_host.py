@@ -596,3 +596,191 @@ def test_store_split_k_long_k_rule_is_off_by_default_and_narrow_when_on(monkeypa
         assert ops.store_split_k(pixels, N, K // 64) == 1, (pixels, N, K)
     assert ops.store_split_k(256 * 64, 1024, 36864 // 64) == 1                        # 128 x 128 seq-8 B=32: 512 tiles = two exact rounds
     assert ops.store_split_k(1 * 16 * 16, 256, 2304 // 64) > 1                         # the old small-grid rule (batch-1 inference) still applies
+
+
+# ---------------------------------------------------------------------------------------------
+# the f64 reference, the dispatch plan and the argument contracts of tests/test_gpu_igemm_abi.py
+# ---------------------------------------------------------------------------------------------
+def _ref_conv(n_img, H, W, ktap, scale, pad, srcs, w, cs, N):
+    """tests/igemm_cases.py reference on NHWC f64 sources with a host-written panel -> [n_img][N][H][W]."""
+    import igemm_cases as IC
+    A = IC.gather_a(n_img, H, W, ktap, scale, pad, [(x.permute(0, 2, 3, 1).contiguous(), oy, ox) for x, oy, ox in srcs])
+    out, mag = IC.gemm_ref(A, IC.host_panel(w, cs, ktap, N))
+    assert bool((mag >= out.abs() - 1e-12).all())
+    return out.view(n_img, H, W, N).permute(0, 3, 1, 2)
+
+
+def test_igemm_f64_reference_equals_pytorch_convolutions():
+    """The host reference of the direct forward-GEMM tests against f64 F.conv2d / F.conv_transpose2d / F.pad: 3x3, two sources with
+    positive (pad) and negative (crop) offsets, 1x1, 5x5 / 7x7 on images smaller than the kernel, the ConvTranspose forward
+    segments (also onto a larger and a smaller destination) and the scale-2 gather with an even and an odd source."""
+    import torch.nn.functional as F
+    import igemm_cases as IC
+    torch.manual_seed(5)
+    dd = torch.float64
+    n, H, W = 3, 9, 11
+    x0 = torch.randn(n, 24, H, W, dtype=dd)
+    close = lambda a, b: torch.testing.assert_close(a, b, rtol=1e-12, atol=1e-12)
+    w = torch.randn(37, 24, 3, 3, dtype=dd)
+    close(_ref_conv(n, H, W, 3, 1, 1, [(x0, 0, 0)], w, [24], 40)[:, :37], F.conv2d(x0, w, padding=1))
+    assert bool((_ref_conv(n, H, W, 3, 1, 1, [(x0, 0, 0)], w, [24], 40)[:, 37:] == 0).all())
+    # second source smaller, placed at (1, 1): F.pad left/top 1, right 1, bottom 2 (train/unet.py:95-98)
+    w2 = torch.randn(37, 40, 3, 3, dtype=dd)
+    u = torch.randn(n, 16, H - 3, W - 2, dtype=dd)
+    close(_ref_conv(n, H, W, 3, 1, 1, [(x0, 0, 0), (u, 1, 1)], w2, [24, 16], 40)[:, :37],
+          F.conv2d(torch.cat((x0, F.pad(u, [1, 1, 1, 2])), 1), w2, padding=1))
+    # second source larger, offsets (-1, -2): the window [1, 1 + H) x [2, 2 + W) of it lies on the grid.  The header's rule is
+    # "zero outside [0, Hs) x [0, Ws)", so border taps read the source's real pixels around that window (a crop followed by a padded
+    # convolution would see zeros there): an unpadded convolution over the window grown by one pixel
+    u = torch.randn(n, 16, H + 2, W + 3, dtype=dd)
+    close(_ref_conv(n, H, W, 3, 1, 1, [(x0, 0, 0), (u, -1, -2)], w2, [24, 16], 40)[:, :37],
+          F.conv2d(x0, w2[:, :24], padding=1) + F.conv2d(u[:, :, 0:H + 2, 1:W + 3], w2[:, 24:]))
+    u = torch.randn(n, 16, H + 1, W + 2, dtype=dd)          # window flush with the source's bottom / right edge: zeros beyond it
+    close(_ref_conv(n, H, W, 3, 1, 1, [(x0, 0, 0), (u, -1, -2)], w2, [24, 16], 40)[:, :37],
+          F.conv2d(x0, w2[:, :24], padding=1) + F.conv2d(F.pad(u, [0, 1, 0, 1])[:, :, 0:H + 2, 1:W + 3], w2[:, 24:]))
+    # 1x1 over a 72-channel source (two K chunks, the second 8 of 64)
+    x1 = torch.randn(n, 72, H, W, dtype=dd)
+    w1 = torch.randn(13, 72, 1, 1, dtype=dd)
+    close(_ref_conv(n, H, W, 1, 1, 0, [(x1, 0, 0)], w1, [72], 16)[:, :13], F.conv2d(x1, w1))
+    # 5x5 / 7x7, also on 3x4 images
+    for k in (5, 7):
+        for h, wd in ((9, 11), (3, 4)):
+            xs = torch.randn(n, 16, h, wd, dtype=dd)
+            wk = torch.randn(21, 16, k, k, dtype=dd)
+            close(_ref_conv(n, h, wd, k, 1, k // 2, [(xs, 0, 0)], wk, [16], 24)[:, :21], F.conv2d(xs, wk, padding=k // 2))
+    # scale-2 gather (ConvTranspose2d(k2, s2) input gradient = stride-2 2x2 convolution), even and odd source
+    h, wd = 5, 6
+    wg = torch.randn(37, 24, 2, 2, dtype=dd)
+    xs = torch.randn(n, 24, 2 * h, 2 * wd, dtype=dd)
+    close(_ref_conv(n, h, wd, 2, 2, 0, [(xs, 0, 0)], wg, [24], 40)[:, :37], F.conv2d(xs, wg, stride=2))
+    xs = torch.randn(n, 24, 2 * h - 1, 2 * wd - 1, dtype=dd)
+    close(_ref_conv(n, h, wd, 2, 2, 0, [(xs, 0, 0)], wg, [24], 40)[:, :37], F.conv2d(F.pad(xs, [0, 1, 0, 1]), wg, stride=2))
+    # ConvTranspose2d forward: 1x1 GEMM with tap-major rows n = tap*Cop + co, four scale-2 segments
+    Co, Cop = 13, 16
+    xs = torch.randn(n, 24, h, wd, dtype=dd)
+    wt = torch.randn(24, Co, 2, 2, dtype=dd)
+    wp = torch.zeros(4 * Cop, 64, dtype=dd)
+    for t in range(4):
+        wp[t * Cop:t * Cop + Co, :24] = wt[:, :, t // 2, t % 2].t()
+    A = IC.gather_a(n, h, wd, 1, 1, 0, [(xs.permute(0, 2, 3, 1).contiguous(), 0, 0)])
+    val, _ = IC.gemm_ref(A, wp)
+    full = F.conv_transpose2d(xs, wt, stride=2)
+    for Hd, Wd in ((2 * h, 2 * wd), (2 * h + 1, 2 * wd + 1), (2 * h - 1, 2 * wd - 1)):
+        segs = [(t * Cop, (t + 1) * Cop, Cop, 0, Hd, Wd, 2, t // 2, t % 2) for t in range(4)]
+        dsts = IC.scatter_segments(val, n, h, wd, segs)
+        merged = torch.full((n, Hd, Wd, Cop), float("nan"), dtype=dd)
+        for dst in dsts:
+            assert not bool((~torch.isnan(dst) & ~torch.isnan(merged)).any())       # the four taps never collide
+            merged = torch.where(torch.isnan(dst), merged, dst)
+        hh, ww = min(Hd, 2 * h), min(Wd, 2 * wd)
+        close(merged[:, :hh, :ww, :Co].permute(0, 3, 1, 2), full[:, :, :hh, :ww])
+        assert bool(torch.isnan(merged[:, 2 * h:]).all()) and bool(torch.isnan(merged[:, :, 2 * wd:]).all())
+        assert not bool(torch.isnan(merged[:, :hh, :ww]).any())
+    # c_off into a wider destination and a column range: everything else stays unwritten
+    dst = IC.scatter_segments(val, n, h, wd, [(8, 32, 48, 16, h, wd, 1, 0, 0)])[0]
+    close(dst[..., 16:40].reshape(-1, 24), val[:, 8:32])
+    assert bool(torch.isnan(dst[..., :16]).all()) and bool(torch.isnan(dst[..., 40:]).all())
+    # K ranges: the partial sums add up to the full sum, range r holds the chunks [r*cpr, (r+1)*cpr) of every tap
+    A = IC.gather_a(n, H, W, 3, 1, 1, [(x1.permute(0, 2, 3, 1).contiguous(), 0, 0), (x0.permute(0, 2, 3, 1).contiguous(), 0, 0)])
+    wp = torch.randn(8, 9 * 192, dtype=dd)
+    for ks, sizes in ((1, [3]), (2, [2, 1]), (8, [1, 1, 1])):
+        masks = IC.krange_masks(3, [128, 64], ks)
+        assert [int(m.sum()) // (9 * 64) for m in masks] == sizes and len(masks) == L.lib.uclstm_igemm_ksplit_used(9 * 192, 3, ks)
+        close(sum(IC.gemm_ref(A, wp, m)[0] for m in masks), IC.gemm_ref(A, wp)[0])
+    assert [int(m.sum()) // (9 * 64) for m in IC.krange_masks(3, [320], 3)] == [2, 2, 1]
+    # the cell: gate order and row interleave (n = hb*64 + gate*16 + j), against torch.chunk on the reference's channel order
+    pre = torch.randn(7, 128, dtype=dd)
+    g = IC.lstm_rows_to_gates(pre, 24)
+    assert g.shape == (7, 4, 24) and float(g[3, 2, 17]) == float(pre[3, 64 + 2 * 16 + 1])
+    cp = torch.randn(7, 24, dtype=dd)
+    gates, cn, hn = IC.lstm_cell_ref(g, cp)
+    i, f, gg, o = torch.chunk(g.reshape(7, 96), 4, dim=1)
+    close(cn, torch.sigmoid(f) * cp + torch.sigmoid(i) * torch.tanh(gg))
+    close(hn, torch.sigmoid(o) * torch.tanh(cn))
+
+
+def test_igemm_parity_cases_dispatch_plan():
+    """Every case of tests/test_gpu_igemm_abi.py really reaches the kernel, tile count and K-range count it is meant for
+    (validation-only entry points, dummy aligned pointers)."""
+    import igemm_cases as IC
+    names = [c.name for c in IC.ALL_CASES]
+    assert len(set(names)) == len(names)
+    for c in IC.ALL_CASES + IC.GROUP_B:
+        d = IC.dummy_desc(c)
+        assert L.lib.uclstm_igemm_fwd_shape(C.byref(d)) == c.shape, c.name
+        if c.stats:
+            tiles = IC.stats_tiles(c)
+            assert len(tiles) == c.groups * L.lib.uclstm_igemm_tiles_per_group(c.n_img, c.H, c.W, c.groups, c.N), c.name
+            assert max(len(p) for p in tiles) == min(c.tile_pixels(), c.M // c.groups)
+    plan = {c.name: c for c in IC.ALL_CASES}
+    tpg = lambda c: L.lib.uclstm_igemm_tiles_per_group(c.n_img, c.H, c.W, c.groups, c.N)
+    assert [tpg(plan[k]) for k in ("S9-k0-g3", "S9-k1-g3", "S9-k0-g2", "S9-k1-g2")] == [1, 1, 3, 2]      # 99 and 384 pixels per group
+    assert [tpg(plan[k]) for k in ("S11-a", "S11-b", "S11-c", "S12-a", "S12-b", "S13-b", "S13-c")] == [2, 2, 6, 4, 12, 4, 5]
+    # the ring case above 256 tiles: 129 blocks of two tiles and one of one; three group boundaries cut a block's run
+    runs = IC.stats_runs(plan["S13-e"])
+    assert tpg(plan["S13-e"]) == 37 and len(runs) == 133 and sum(len(r[0]) for r in runs) == 126
+    assert all(len(r[0]) == 0 for r in IC.stats_runs(plan["S13-b"]))
+    # every kernel and epilogue is reached
+    assert {(c.epi, c.shape) for c in IC.ALL_CASES} >= {(L.EPI_STORE, 0), (L.EPI_STORE, 1), (L.EPI_STORE, 2), (L.EPI_STORE, 3),
+                                                         (L.EPI_ATOMIC, 0), (L.EPI_ATOMIC, 1), (L.EPI_ATOMIC, 2), (L.EPI_LSTM, 0), (L.EPI_LSTM, 2)}
+    for c in IC.ATOMIC_CASES:
+        assert L.lib.uclstm_igemm_ksplit_used(c.Ktot, c.ktap, c.ksplit) == IC.ATOMIC_USED[c.name.split("-")[-1]], c.name
+    for members in (IC.GROUP_A, IC.GROUP_B):
+        arr = (L.IgemmDesc * len(members))(*[IC.dummy_desc(c) for c in members])
+        assert L.lib.uclstm_igemm_fwd_group_blocks(arr, len(members)) == IC.group_blocks_expected(members)
+    assert IC.group_blocks_expected(IC.GROUP_A) == 24 and IC.group_blocks_expected(IC.GROUP_B) == 40
+
+
+def test_igemm_forward_contracts_are_checked_before_launch():
+    """UCLSTM_E_BADARG of the forward family beyond test_argument_contracts_are_checked_before_launch; every descriptor below is a
+    valid case of the parity table with ONE field broken (the unbroken one is accepted first)."""
+    import igemm_cases as IC
+    plan = {c.name: c for c in IC.ALL_CASES}
+    shape = lambda d: L.lib.uclstm_igemm_fwd_shape(C.byref(d))
+    # split-K: acc_ld < N, a slab smaller than the output
+    c = plan["A-k0-s2"]
+    d = IC.dummy_desc(c)
+    assert shape(d) == 0
+    d.acc_ld = c.N - 8
+    assert shape(d) == -1
+    d = IC.dummy_desc(c)
+    d.acc_slab = c.M * d.acc_ld - 1
+    assert shape(d) == -1
+    d = IC.dummy_desc(c)
+    d.ksplit = 0
+    assert shape(d) == -1
+    # stats with a kernel wider than 3x3
+    c = plan["S10-5"]
+    d = IC.dummy_desc(c)
+    assert shape(d) == 0
+    d.stats = IC.DUMMY
+    assert shape(d) == -1
+    # a segment that does not fit its destination's channels
+    c = plan["S7"]
+    d = IC.dummy_desc(c)
+    assert shape(d) == 0
+    d.seg[0].c_off = 32                 # 32 + 24 > 48
+    assert shape(d) == -1
+    # fused cell: misaligned pre_add, N != 64 * ceil(Hd_p / 16)
+    c = plan["L0-hd24"]
+    d = IC.dummy_desc(c)
+    assert shape(d) == 0
+    d.pre_add = IC.DUMMY + 4
+    assert shape(d) == -1
+    d = IC.dummy_desc(c)
+    d.Hd_p = 40                         # needs N = 192
+    assert shape(d) == -1
+    d = IC.dummy_desc(c)
+    d.c_out = None
+    assert shape(d) == -1
+    # group launch: a member that is not on the patch shape, mixed source counts
+    ok = [IC.dummy_desc(m) for m in IC.GROUP_A]
+    blocks = lambda ds: L.lib.uclstm_igemm_fwd_group_blocks((L.IgemmDesc * len(ds))(*ds), len(ds))
+    assert blocks(ok) == 24
+    assert blocks(ok + [IC.dummy_desc(plan["A-k0-s2"])]) == -1          # per-tap shape
+    assert blocks(ok + [IC.dummy_desc(plan["S8-k2"])]) == -1            # patch shape, STORE epilogue
+    assert blocks(ok + [IC.dummy_desc(plan["L2-h-only"])]) == -1        # one source among two-source members
+    assert blocks([IC.dummy_desc(plan["L2-h-only"])]) == 8
+    assert blocks(ok * 2) == -1                                          # more than four members
+    for K in (L.lib, L.lib16):
+        assert K.uclstm_igemm_fwd_group((L.IgemmDesc * 4)(*(ok + [IC.dummy_desc(plan["A-k0-s2"])])), 4, None) == -1

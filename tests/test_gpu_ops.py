@@ -127,8 +127,9 @@ def test_conv3x3_forward(N, C0, C1, Co, H, W):
     assert pad_is_zero(out, Co)
 
 
+@pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
 @pytest.mark.parametrize("W", [64, 128, 320])
-def test_c64_ring_kernel_is_bit_identical_to_the_generic_kernel(tmp_path, W):
+def test_c64_ring_kernel_is_bit_identical_to_the_generic_kernel(tmp_path, W, dtype):
     """The persistent 64-channel kernel accumulates in the same order as the generic one (taps 0..8, two 32-channel halves
     each): outputs must be bit-identical, the per-group statistics equal up to f32 summation order.  The generic kernel
     runs in a subprocess with UCLSTM_FWD_C64=0 (the switch is read once per process)."""
@@ -138,24 +139,26 @@ def test_c64_ring_kernel_is_bit_identical_to_the_generic_kernel(tmp_path, W):
         sys.path.insert(0, %r)
         import unet_convlstm_amd as U
         from unet_convlstm_amd import ops
-        torch.manual_seed(21)
-        N, H, W, groups = 6, 12, int(sys.argv[2]), 3
-        xn = (torch.randn(N, H, W, 64) * 0.7).to(torch.bfloat16).cuda()
-        w = (torch.randn(64, 64, 3, 3) * 0.1).cuda()
-        b = (torch.randn(64) * 0.3).cuda()
-        pd = ops.conv_pack_desc(64, 64, [64], [64])
-        wp, bp = ops.pack_weights(pd, w), ops.pack_bias(pd, b)
-        out = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device="cuda")
-        tpg = U._lib.lib.uclstm_igemm_tiles_per_group(N, H, W, groups, 64)
-        stats = torch.full((groups, tpg, 64, 2), float("nan"), device="cuda")
-        ops.SHAPE_LOG = []
-        ops.igemm_store([ops.SrcView(xn)], wp, (H, W), N, [(out, 0, 64, 0, 1, 0, 0)], ktap=3, pad=1, groups=groups, bias=bp, stats=stats)
-        torch.save({"out": out.cpu(), "stats": stats.sum(1).cpu(), "shape": ops.SHAPE_LOG[0]}, sys.argv[1])
+        DT = getattr(torch, sys.argv[3])
+        with ops.compute_dtype(DT):
+            torch.manual_seed(21)
+            N, H, W, groups = 6, 12, int(sys.argv[2]), 3
+            xn = (torch.randn(N, H, W, 64) * 0.7).to(DT).cuda()
+            w = (torch.randn(64, 64, 3, 3) * 0.1).cuda()
+            b = (torch.randn(64) * 0.3).cuda()
+            pd = ops.conv_pack_desc(64, 64, [64], [64])
+            wp, bp = ops.pack_weights(pd, w, dtype=DT), ops.pack_bias(pd, b)
+            out = torch.empty(N, H, W, 64, dtype=DT, device="cuda")
+            tpg = U._lib.lib.uclstm_igemm_tiles_per_group(N, H, W, groups, 64)
+            stats = torch.full((groups, tpg, 64, 2), float("nan"), device="cuda")
+            ops.SHAPE_LOG = []
+            ops.igemm_store([ops.SrcView(xn)], wp, (H, W), N, [(out, 0, 64, 0, 1, 0, 0)], ktap=3, pad=1, groups=groups, bias=bp, stats=stats)
+            torch.save({"out": out.cpu(), "stats": stats.sum(1).cpu(), "shape": ops.SHAPE_LOG[0]}, sys.argv[1])
     """ % ROOT_DIR)
     res = {}
     for tag, val in (("ring", "1"), ("generic", "0")):
         f = str(tmp_path / (tag + ".pt"))
-        r = subprocess.run([sys.executable, "-c", code, f, str(W)], env=dict(os.environ, UCLSTM_FWD_C64=val), capture_output=True, text=True,
+        r = subprocess.run([sys.executable, "-c", code, f, str(W), dtype], env=dict(os.environ, UCLSTM_FWD_C64=val), capture_output=True, text=True,
                            timeout=240)
         assert r.returncode == 0, r.stderr[-1500:]
         res[tag] = torch.load(f)
@@ -165,7 +168,8 @@ def test_c64_ring_kernel_is_bit_identical_to_the_generic_kernel(tmp_path, W):
     torch.testing.assert_close(res["ring"]["stats"], res["generic"]["stats"], rtol=1e-4, atol=1e-2)
 
 
-def test_patch_loop_is_bit_identical_to_the_per_tap_loop(tmp_path):
+@pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
+def test_patch_loop_is_bit_identical_to_the_per_tap_loop(tmp_path, dtype):
     """The patch shape of the forward kernel (activations of a 64-channel chunk staged once, nine taps as shifted LDS
     reads, 128 x 256 tiles) walks K in the same order as the per-tap loop, so every output must be bit-identical and the
     BatchNorm partial sums equal up to their f32 summation order.  Covers: one image per tile (16x16), four images per tile
@@ -179,71 +183,73 @@ def test_patch_loop_is_bit_identical_to_the_per_tap_loop(tmp_path):
         sys.path.insert(0, %r)
         import unet_convlstm_amd as U
         from unet_convlstm_amd import ops
-        torch.manual_seed(33)
-        res = {}
-        ops.SHAPE_LOG = []
-        #        imgs H   W   C0   C1   Co  groups
-        cases = [(8, 16, 16, 128, 0, 128, 2), (16, 8, 8, 128, 64, 256, 4), (4, 32, 32, 128, 0, 192, 1), (2, 64, 64, 128, 0, 128, 1),
-                 (8, 16, 24, 64, 64, 128, 1), (64, 4, 4, 128, 64, 256, 2),
-                 # images wider than 64 pixels: 4-row x 64-column STRIP tiles (halo columns = real pixels of the neighbouring strip)
-                 (2, 8, 128, 128, 0, 128, 2), (1, 12, 256, 64, 64, 192, 1), (3, 4, 192, 128, 0, 128, 3)]
-        for ci, (N, H, W, C0, C1, Co, groups) in enumerate(cases):
-            xs = [(torch.randn(N, H, W, C0) * 0.7).to(torch.bfloat16).cuda()]
-            if C1:
-                xs.append((torch.randn(N, H, W, C1) * 0.7).to(torch.bfloat16).cuda())
-            cs = [C0] + ([C1] if C1 else [])
-            w = (torch.randn(Co, C0 + C1, 3, 3) * 0.05).cuda()
-            b = (torch.randn(Co) * 0.3).cuda()
-            pd = ops.conv_pack_desc(Co, C0 + C1, cs, cs)
-            wp, bp = ops.pack_weights(pd, w), ops.pack_bias(pd, b)
-            out = torch.empty(N, H, W, Co, dtype=torch.bfloat16, device="cuda")
-            tpg = U._lib.lib.uclstm_igemm_tiles_per_group(N, H, W, groups, Co)
-            stats = torch.full((groups, tpg, Co, 2), float("nan"), device="cuda")
-            ops.igemm_store([ops.SrcView(t) for t in xs], wp, (H, W), N, [(out, 0, Co, 0, 1, 0, 0)], ktap=3, pad=1, groups=groups, bias=bp,
-                            stats=stats)
-            res["store%%d" %% ci] = out.cpu()
-            res["stats%%d" %% ci] = stats.sum(1).cpu()
-            # the same convolution as split-K slabs (K ranges of whole chunks: ksteps = 9 * chunks)
-            ksteps = wp.shape[1] // 64
-            ks = 2 if (ksteps // 9) %% 2 == 0 else 1
-            nsl = ops.ksplit_used(wp.shape[1], ks)
-            acc = torch.full((nsl, N * H * W, wp.shape[0]), float("nan"), device="cuda")
-            ops.igemm_atomic([ops.SrcView(t) for t in xs], wp, (H, W), N, acc, ks, ktap=3, pad=1, slabs=True)
-            res["slab%%d" %% ci] = acc.cpu()
-            if ci < 2:      # f32-atomic form of the same split (one shared accumulator): order-dependent rounding only
-                acc1 = torch.zeros((N * H * W, wp.shape[0]), device="cuda")
-                ops.igemm_atomic([ops.SrcView(t) for t in xs], wp, (H, W), N, acc1, ks, ktap=3, pad=1, slabs=False)
-                res["atom%%d" %% ci] = acc1.cpu()
-                res["slabsum%%d" %% ci] = acc.sum(0).cpu()
-        # fused ConvLSTM cell: 16 images of 4x... 16x16 with Cx = Hd = 64 (N = 256 gate rows)
-        B, H, W, Cx, Hd = 4, 16, 16, 64, 64
-        x = (torch.randn(B, H, W, Cx) * 0.5).to(torch.bfloat16).cuda()
-        h = (torch.randn(B, H, W, Hd) * 0.5).to(torch.bfloat16).cuda()
-        c = torch.randn(B, H, W, Hd).cuda()
-        w = (torch.randn(4 * Hd, Cx + Hd, 3, 3) * 0.05).cuda()
-        bias = (torch.randn(4 * Hd) * 0.2).cuda()
-        pd = ops.lstm_pack_desc(Hd, Cx)
-        wp, bp = ops.pack_weights(pd, w), ops.pack_bias(pd, bias)
-        c_out, h_out = torch.empty_like(c), torch.empty_like(h)
-        gates = torch.empty(B, H, W, 4 * Hd, dtype=torch.bfloat16, device="cuda")
-        ops.igemm_lstm(x, h, wp, bp, c, c_out, h_out, gates)
-        res["lstm_c"], res["lstm_h"], res["lstm_g"] = c_out.cpu(), h_out.cpu(), gates.cpu()
-        # the same cell on a 128-wide map (strip tiles through the fused epilogue: the 512x512 rollout's skip2 level)
-        B, H, W = 1, 8, 128
-        x = (torch.randn(B, H, W, Cx) * 0.5).to(torch.bfloat16).cuda()
-        h = (torch.randn(B, H, W, Hd) * 0.5).to(torch.bfloat16).cuda()
-        c = torch.randn(B, H, W, Hd).cuda()
-        c_out, h_out = torch.empty_like(c), torch.empty_like(h)
-        gates = torch.empty(B, H, W, 4 * Hd, dtype=torch.bfloat16, device="cuda")
-        ops.igemm_lstm(x, h, wp, bp, c, c_out, h_out, gates)
-        res["lstmw_c"], res["lstmw_h"], res["lstmw_g"] = c_out.cpu(), h_out.cpu(), gates.cpu()
-        res["shapes"] = torch.tensor(ops.SHAPE_LOG)
-        torch.save(res, sys.argv[1])
+        DT = getattr(torch, sys.argv[2])
+        with ops.compute_dtype(DT):
+            torch.manual_seed(33)
+            res = {}
+            ops.SHAPE_LOG = []
+            #        imgs H   W   C0   C1   Co  groups
+            cases = [(8, 16, 16, 128, 0, 128, 2), (16, 8, 8, 128, 64, 256, 4), (4, 32, 32, 128, 0, 192, 1), (2, 64, 64, 128, 0, 128, 1),
+                     (8, 16, 24, 64, 64, 128, 1), (64, 4, 4, 128, 64, 256, 2),
+                     # images wider than 64 pixels: 4-row x 64-column STRIP tiles (halo columns = real pixels of the neighbouring strip)
+                     (2, 8, 128, 128, 0, 128, 2), (1, 12, 256, 64, 64, 192, 1), (3, 4, 192, 128, 0, 128, 3)]
+            for ci, (N, H, W, C0, C1, Co, groups) in enumerate(cases):
+                xs = [(torch.randn(N, H, W, C0) * 0.7).to(DT).cuda()]
+                if C1:
+                    xs.append((torch.randn(N, H, W, C1) * 0.7).to(DT).cuda())
+                cs = [C0] + ([C1] if C1 else [])
+                w = (torch.randn(Co, C0 + C1, 3, 3) * 0.05).cuda()
+                b = (torch.randn(Co) * 0.3).cuda()
+                pd = ops.conv_pack_desc(Co, C0 + C1, cs, cs)
+                wp, bp = ops.pack_weights(pd, w, dtype=DT), ops.pack_bias(pd, b)
+                out = torch.empty(N, H, W, Co, dtype=DT, device="cuda")
+                tpg = U._lib.lib.uclstm_igemm_tiles_per_group(N, H, W, groups, Co)
+                stats = torch.full((groups, tpg, Co, 2), float("nan"), device="cuda")
+                ops.igemm_store([ops.SrcView(t) for t in xs], wp, (H, W), N, [(out, 0, Co, 0, 1, 0, 0)], ktap=3, pad=1, groups=groups, bias=bp,
+                                stats=stats)
+                res["store%%d" %% ci] = out.cpu()
+                res["stats%%d" %% ci] = stats.sum(1).cpu()
+                # the same convolution as split-K slabs (K ranges of whole chunks: ksteps = 9 * chunks)
+                ksteps = wp.shape[1] // 64
+                ks = 2 if (ksteps // 9) %% 2 == 0 else 1
+                nsl = ops.ksplit_used(wp.shape[1], ks)
+                acc = torch.full((nsl, N * H * W, wp.shape[0]), float("nan"), device="cuda")
+                ops.igemm_atomic([ops.SrcView(t) for t in xs], wp, (H, W), N, acc, ks, ktap=3, pad=1, slabs=True)
+                res["slab%%d" %% ci] = acc.cpu()
+                if ci < 2:      # f32-atomic form of the same split (one shared accumulator): order-dependent rounding only
+                    acc1 = torch.zeros((N * H * W, wp.shape[0]), device="cuda")
+                    ops.igemm_atomic([ops.SrcView(t) for t in xs], wp, (H, W), N, acc1, ks, ktap=3, pad=1, slabs=False)
+                    res["atom%%d" %% ci] = acc1.cpu()
+                    res["slabsum%%d" %% ci] = acc.sum(0).cpu()
+            # fused ConvLSTM cell: 16 images of 4x... 16x16 with Cx = Hd = 64 (N = 256 gate rows)
+            B, H, W, Cx, Hd = 4, 16, 16, 64, 64
+            x = (torch.randn(B, H, W, Cx) * 0.5).to(DT).cuda()
+            h = (torch.randn(B, H, W, Hd) * 0.5).to(DT).cuda()
+            c = torch.randn(B, H, W, Hd).cuda()
+            w = (torch.randn(4 * Hd, Cx + Hd, 3, 3) * 0.05).cuda()
+            bias = (torch.randn(4 * Hd) * 0.2).cuda()
+            pd = ops.lstm_pack_desc(Hd, Cx)
+            wp, bp = ops.pack_weights(pd, w, dtype=DT), ops.pack_bias(pd, bias)
+            c_out, h_out = torch.empty_like(c), torch.empty_like(h)
+            gates = torch.empty(B, H, W, 4 * Hd, dtype=DT, device="cuda")
+            ops.igemm_lstm(x, h, wp, bp, c, c_out, h_out, gates)
+            res["lstm_c"], res["lstm_h"], res["lstm_g"] = c_out.cpu(), h_out.cpu(), gates.cpu()
+            # the same cell on a 128-wide map (strip tiles through the fused epilogue: the 512x512 rollout's skip2 level)
+            B, H, W = 1, 8, 128
+            x = (torch.randn(B, H, W, Cx) * 0.5).to(DT).cuda()
+            h = (torch.randn(B, H, W, Hd) * 0.5).to(DT).cuda()
+            c = torch.randn(B, H, W, Hd).cuda()
+            c_out, h_out = torch.empty_like(c), torch.empty_like(h)
+            gates = torch.empty(B, H, W, 4 * Hd, dtype=DT, device="cuda")
+            ops.igemm_lstm(x, h, wp, bp, c, c_out, h_out, gates)
+            res["lstmw_c"], res["lstmw_h"], res["lstmw_g"] = c_out.cpu(), h_out.cpu(), gates.cpu()
+            res["shapes"] = torch.tensor(ops.SHAPE_LOG)
+            torch.save(res, sys.argv[1])
     """ % ROOT_DIR)
     res = {}
     for tag, val in (("patch", "1"), ("pertap", "0")):
         f = str(tmp_path / (tag + ".pt"))
-        r = subprocess.run([sys.executable, "-c", code, f], env=dict(os.environ, UCLSTM_FWD_PATCH=val), capture_output=True, text=True, timeout=300)
+        r = subprocess.run([sys.executable, "-c", code, f, dtype], env=dict(os.environ, UCLSTM_FWD_PATCH=val), capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2500:]
         res[tag] = torch.load(f)
     # the library reports which kernel each launch took: every launch of the first run the patch loop, none of the second

@@ -648,11 +648,31 @@ __device__ __forceinline__ void igemm_fwd_body(const uclstm_igemm_desc& d, const
                     s1 = Red[((2 * half) * TBN + col) * 2] + Red[((2 * half + 1) * TBN + col) * 2];
                     s2 = Red[((2 * half) * TBN + col) * 2 + 1] + Red[((2 * half + 1) * TBN + col) * 2 + 1];
                 } else {
-                    for (int r = 0; r < rows_valid; ++r) {
-                        const float v = act_to_f32(*(const act16*)(Ot + r * OT_PITCH + col * 2));
-                        s1 += v;
-                        s2 += v * v;
+                    // eight interleaved partial sums, added as a tree: one serial f32 chain over the tile's 128 / 256 rows missed
+                    // the 2e-6 of sum|terms| that every other reduction here holds (sum of squares of fp16 values; DESIGN.md
+                    // section 4 has the figures)
+                    float p1[8], p2[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) p1[j] = p2[j] = 0.f;
+                    int r = 0;
+                    for (; r + 8 <= rows_valid; r += 8) {
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            const float v = act_to_f32(*(const act16*)(Ot + (r + j) * OT_PITCH + col * 2));
+                            p1[j] += v;
+                            p2[j] += v * v;
+                        }
                     }
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) {
+                        if (r + j < rows_valid) {
+                            const float v = act_to_f32(*(const act16*)(Ot + (r + j) * OT_PITCH + col * 2));
+                            p1[j] += v;
+                            p2[j] += v * v;
+                        }
+                    }
+                    s1 = ((p1[0] + p1[4]) + (p1[1] + p1[5])) + ((p1[2] + p1[6]) + (p1[3] + p1[7]));
+                    s2 = ((p2[0] + p2[4]) + (p2[1] + p2[5])) + ((p2[2] + p2[6]) + (p2[3] + p2[7]));
                 }
                 float* sp = d.stats + ((long)(mt * HALVES + half) * d.N + n) * 2;
                 sp[0] = s1;
