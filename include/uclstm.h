@@ -34,6 +34,10 @@ extern "C" {
 #define UCLSTM_E_LAUNCH     -2   /* hipLaunchKernel reported an error (hipGetLastError)      */
 #define UCLSTM_E_NODEVICE   -3   /* no gfx950 device visible                                 */
 
+/* activation type of the entry points that read 16-bit activations but have no _f16 twin (the *_ordered reductions) */
+#define UCLSTM_ACT_TYPE_BF16 0
+#define UCLSTM_ACT_TYPE_F16  1
+
 /* ------------------------------------------------------------------------------------ */
 /* Implicit-GEMM convolution family                                                     */
 /* ------------------------------------------------------------------------------------ */
@@ -215,6 +219,19 @@ int32_t uclstm_pack_weights_batched(const uclstm_pack_job* jobs_dev /* DEVICE me
  * slab 0 in place: dwp is scratch of the weight-gradient GEMM and is CONSUMED by this call. */
 int32_t uclstm_unpack_wgrad(const uclstm_pack_desc* d, const float* dwp, int32_t nslab /* dWp = sum of nslab slabs */,
                             int64_t slab /* floats between slabs */, float* grad, int32_t accumulate, void* stream);
+/* Ordered form of uclstm_unpack_wgrad (deterministic mode): the same result contract with NO atomics on any path, a pure function
+ * of dwp, grad and the shapes.  uclstm_unpack_wgrad_ordered_groups (a function of the descriptor and nslab alone, 1 .. 1024) says
+ * into how many slab groups G the call splits the slabs, per = ceil(nslab / G) consecutive slabs each.
+ *   G == 1: the non-atomic paths of uclstm_unpack_wgrad (fold / row-family kernel / one thread per element), which add the slabs
+ *           in index order; `scratch` is not touched and may be NULL.
+ *   G  > 1: two launches.  Stage 1: group g adds its slabs g*per .. min(nslab, (g+1)*per) - 1 in that order, starting from 0, and
+ *           STORES the sum to scratch[g][idx] (scratch: f32 [G][N*Ktot], caller-owned, need not be initialised; every element of
+ *           every row is written, zeros for an empty group or a padding element).  Stage 2: one thread per element,
+ *           grad[off] = (accumulate ? grad[off] : 0) + scratch[0][idx] + scratch[1][idx] + ... + scratch[G-1][idx], left to right.
+ * Nobody zeroes anything.  As uclstm_unpack_wgrad, dwp may be consumed. */
+int32_t uclstm_unpack_wgrad_ordered_groups(const uclstm_pack_desc* d, int32_t nslab);
+int32_t uclstm_unpack_wgrad_ordered(const uclstm_pack_desc* d, const float* dwp, int32_t nslab, int64_t slab, float* scratch,
+                                    float* grad, int32_t accumulate, void* stream);
 /* bias [n_valid*(4 if LSTM)] f32 -> panel-row order [N] f32 (zero padded). */
 int32_t uclstm_pack_bias(const uclstm_pack_desc* d, const float* b, float* bp, void* stream);
 
@@ -288,6 +305,17 @@ int32_t uclstm_bn_head_bwd_reduce(const void* z, const float* dy, const float* s
 int32_t uclstm_bn_head_bwd_apply(const void* z, const float* dy, const float* scale, const float* shift, const float* mean,
                                  const float* rstd, const float* sums, const float* w, void* dz, int64_t pixels,
                                  int64_t pixels_per_group, int32_t Cp, int32_t C, void* stream);
+
+/* Ordered form of uclstm_bn_head_bwd_reduce (deterministic mode; ONE symbol for both activation types, act_type =
+ * UCLSTM_ACT_TYPE_BF16 / UCLSTM_ACT_TYPE_F16): partials / sums exactly as there; the head's C + 1 columns (dw[0..C-1], db) no
+ * longer end in one atomic per block but go through `head_partials` (f32 [rows][C + 1], rows = the row count of `partials`,
+ * caller-owned, need not be initialised): block r stores row r, then one thread per column adds the rows in index order,
+ *   dw[c] = dw[c] + hp[0][c] + hp[1][c] + ... + hp[rows-1][c]   (left to right; db likewise from column C).
+ * The += into dw / db stays (they are attached gradient buffers, train/unet.py:101-107); nothing is zeroed by anybody. */
+int32_t uclstm_bn_head_bwd_reduce_ordered(const void* z, const float* dy, const float* scale, const float* shift, const float* mean,
+                                          const float* rstd, const float* w, float* partials, float* head_partials, float* sums,
+                                          float* dw, float* db, int64_t pixels, int64_t pixels_per_group, int32_t Cp, int32_t C,
+                                          int32_t act_type, void* stream);
 
 /* Parameter gradients of the BatchNorm (train/unet.py:70) from the sums of pass 1, summed over the groups in order:
  * dbeta[c] = (accumulate ? dbeta[c] : 0) + sum_g sums[g][c][0],  dgamma likewise from sums[g][c][1],  c < C. */
@@ -374,6 +402,17 @@ int32_t uclstm_outconv_fwd(const void* a, const float* w, const float* b, float*
 int32_t uclstm_outconv_bwd(const void* a, const float* w, const float* dy, void* da, float* dw, float* db,
                            int64_t n_img, int32_t HW, int32_t Cp, int32_t C, int32_t Co, void* stream);
 
+/* Ordered form (deterministic mode; one symbol, act_type as above).  da as uclstm_outconv_bwd.  Pixel range r (of
+ * uclstm_outconv_bwd_ordered_rows, a function of the shape alone, 1 .. 1024) stores its block totals to row r of `partials`
+ * (f32 [rows][Co*C + Co]: the dw columns in [co][c] order, then the Co db columns; caller-owned, need not be initialised, every
+ * element is written); then one thread per column adds the rows in index order,
+ *   out = (accumulate ? out : 0) + p[0][col] + p[1][col] + ... + p[rows-1][col]   (left to right),
+ * into dw [Co][C] / db [Co].  dw or db NULL: that output is skipped; both NULL: no parameter-gradient launch, partials unused. */
+int64_t uclstm_outconv_bwd_ordered_rows(int64_t n_img, int32_t HW);
+int32_t uclstm_outconv_bwd_ordered(const void* a, const float* w, const float* dy, void* da, float* partials, float* dw, float* db,
+                                   int32_t accumulate, int64_t n_img, int32_t HW, int32_t Cp, int32_t C, int32_t Co,
+                                   int32_t act_type, void* stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* SpatialAttention (train/unet.py:113-125): mean & max over channels -> k x k conv (2 -> 1, no bias) -> sigmoid -> scale */
 /* ------------------------------------------------------------------------------------ */
@@ -390,6 +429,17 @@ int32_t uclstm_attention_bwd(const void* x, const void* dout, const float* w, co
 
 /* column sums of a bf16 [pixels][Cp] tensor into f32 [Cp] (bias gradients); out must be zeroed. */
 int32_t uclstm_colsum(const void* a, float* out, int64_t pixels, int32_t Cp, void* stream);
+/* Ordered form (deterministic mode; one symbol, act_type as above): pixel range r (of uclstm_colsum_ordered_rows, a function of
+ * pixels and Cp alone, 1 .. 1024) stores its column sums to row r of `partials` (f32 [rows][Cp], caller-owned, need not be
+ * initialised; a range without pixels stores zeros), then one thread per column adds the rows in index order,
+ *   out[c] = (accumulate ? out[c] : 0) + p[0][c] + p[1][c] + ... + p[rows-1][c]   (left to right).  Nobody zeroes anything. */
+int64_t uclstm_colsum_ordered_rows(int64_t pixels, int32_t Cp);
+int32_t uclstm_colsum_ordered(const void* a, float* partials, float* out, int64_t pixels, int32_t Cp, int32_t accumulate,
+                              int32_t act_type, void* stream);
+/* The finishing step of the ordered reductions on its own: out[c] = (accumulate ? out[c] : 0) + partials[0][c] + partials[1][c] +
+ * ... + partials[rows-1][c] for c < cols, one thread per column, the additions strictly left to right (partials [rows][cols]). */
+int32_t uclstm_ordered_sum_f32(const float* partials, int32_t rows, int32_t cols, float* out, int32_t accumulate, void* stream);
+int32_t uclstm_ordered_sum_f64(const double* partials, int32_t rows, int32_t cols, double* out, int32_t accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Loss (main.py:28-72) -- weighted L1 + 0.005 * gradient L1, f32 [n][H][W] planes      */
@@ -397,6 +447,12 @@ int32_t uclstm_colsum(const void* a, float* out, int64_t pixels, int32_t Cp, voi
 /* sums[0..3] = sum(ad*w*m), sum(w*m), sum(gd*mc), sum(mc)  (m = 1 when mask == NULL); caller zeroes sums. */
 int32_t uclstm_loss_fwd(const float* y_pred, const float* y, const float* mask, double* sums,
                         int64_t planes, int32_t H, int32_t W, void* stream);
+/* Ordered form (deterministic mode): block r of the same sweep stores its four block totals to partials[r][0..3] (f64 [rows][4],
+ * rows = uclstm_loss_fwd_ordered_rows, a function of the shape alone, 1 .. 1024; caller-owned, need not be initialised), then
+ * sums[k] = (accumulate ? sums[k] : 0) + p[0][k] + p[1][k] + ... + p[rows-1][k], left to right.  Nobody zeroes anything. */
+int64_t uclstm_loss_fwd_ordered_rows(int64_t planes, int32_t H, int32_t W);
+int32_t uclstm_loss_fwd_ordered(const float* y_pred, const float* y, const float* mask, double* partials, double* sums,
+                                int32_t accumulate, int64_t planes, int32_t H, int32_t W, void* stream);
 /* grad = coefs[0] * d(sum ad*w*m)/dy_pred + coefs[1] * d(sum gd*mc)/dy_pred; coefs is a DEVICE f32[2]
  * (1/denominators times the upstream gradient), so the step never syncs with the host. */
 int32_t uclstm_loss_bwd(const float* y_pred, const float* y, const float* mask, const float* coefs,
@@ -406,6 +462,11 @@ int32_t uclstm_loss_bwd(const float* y_pred, const float* y, const float* mask, 
 /* Optimiser (main.py:106-108): global-norm clip + AdamW on flat f32 buffers            */
 /* ------------------------------------------------------------------------------------ */
 int32_t uclstm_sumsq(const float* g, int64_t n, double* out /* accumulates, caller zeroes */, void* stream);
+/* Ordered form (deterministic mode): partials f64 [uclstm_sumsq_ordered_rows] (1 .. 1024 rows, a function of n alone), one stored
+ * block total each; *out = (accumulate ? *out : 0) + p[0] + p[1] + ... + p[rows-1], left to right.  Nobody zeroes anything.
+ * The clip coefficient of main.py:106 is derived from this sum, so it reaches every parameter. */
+int64_t uclstm_sumsq_ordered_rows(int64_t n);
+int32_t uclstm_sumsq_ordered(const float* g, int64_t n, double* partials, double* out, int32_t accumulate, void* stream);
 /* p,m,v,g flat f32 [n]; grad is scaled by min(1, max_norm/(sqrt(*sumsq)+1e-6)) read on device (no host sync). */
 int32_t uclstm_adamw_step(float* p, float* m, float* v, const float* g, int64_t n, const double* sumsq, float max_norm,
                           float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, void* stream);
@@ -460,6 +521,13 @@ int32_t uclstm_dataset_transform(const float* x_raw, const float* y_raw, float* 
  * d = denormalize(y_pred) - denormalize(y) (train/unet.py:316-319, asinh transform); mask may be NULL. */
 int32_t uclstm_metric_sums(const float* y_pred, const float* y, const float* mask, double* sums, int64_t n, float y_scale,
                            float trans_min, float trans_max, void* stream);
+
+/* Ordered form (deterministic mode): partials f64 [uclstm_metric_sums_ordered_rows][4] (1 .. 1024 rows, a function of n alone) as
+ * for uclstm_loss_fwd_ordered; sums[k] = (accumulate ? sums[k] : 0) + p[0][k] + ... + p[rows-1][k], left to right (main.py:114-142
+ * keeps running sums over an epoch: accumulate = 1). */
+int64_t uclstm_metric_sums_ordered_rows(int64_t n);
+int32_t uclstm_metric_sums_ordered(const float* y_pred, const float* y, const float* mask, double* partials, double* sums,
+                                   int32_t accumulate, int64_t n, float y_scale, float trans_min, float trans_max, void* stream);
 
 /* Evaluation report of train/get_metrics.py:117-358 and test.py:333-351 in one pass over f32 y_pred / y / mask (mask may be
  * NULL; a pixel counts when mask != 0).  Each tensor is [B][T] frames of P = C*H*W contiguous elements, addressed as

@@ -18,8 +18,9 @@ from .engine import train_one_epoch, evaluate, train_step, GraphedTrainStep, qui
 from .ddp import FlatDDP
 from .streaming import StreamingPredictor
 from .ops import compute_dtype, set_compute_dtype, get_compute_dtype
+from .ops import deterministic, set_deterministic, is_deterministic
 
 __all__ = ["ConvLSTMCell", "ConvLSTM", "DoubleConv", "Down", "Up", "OutConv", "SpatialAttention",
            "TemporalUNetDualView", "UNet", "compute_loss", "FusedAdamW", "train_one_epoch", "evaluate",
            "train_step", "GraphedTrainStep", "quiesce_host_gc", "SyntheticSequences", "NPZSequenceDataset", "device_transform", "EvalReport", "evaluate_report", "FlatDDP", "StreamingPredictor", "UclstmError", "ops",
-           "compute_dtype", "set_compute_dtype", "get_compute_dtype"]
+           "compute_dtype", "set_compute_dtype", "get_compute_dtype", "deterministic", "set_deterministic", "is_deterministic"]

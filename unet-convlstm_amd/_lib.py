@@ -23,6 +23,7 @@ ABI_VERSION = 16
 EPI_STORE, EPI_LSTM, EPI_ATOMIC = 0, 1, 2
 NMODE_IDENTITY, NMODE_LSTM, NMODE_TAPMAJOR = 0, 1, 2
 KMODE_IDENTITY, KMODE_GATES, KMODE_IM2COL = 0, 1, 2
+ACT_TYPE_BF16, ACT_TYPE_F16 = 0, 1
 
 _ERRORS = {-1: "bad argument (shape/alignment/null contract)", -2: "kernel launch failed", -3: "no gfx950 device"}
 
@@ -121,6 +122,8 @@ _PROTOS = {
     "uclstm_pack_job_init": [C.POINTER(PackJob), C.POINTER(PackDesc), _P, _P, _I],
     "uclstm_pack_weights_batched": [_P, _I, _I, _I, _P],
     "uclstm_unpack_wgrad": [C.POINTER(PackDesc), _P, _I, _L, _P, _I, _P],
+    "uclstm_unpack_wgrad_ordered_groups": [C.POINTER(PackDesc), _I],
+    "uclstm_unpack_wgrad_ordered": [C.POINTER(PackDesc), _P, _I, _L, _P, _P, _I, _P],
     "uclstm_pack_bias": [C.POINTER(PackDesc), _P, _P, _P],
     "uclstm_bn_finalize": [_P, _I, _I, _I, _I, _L, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P],
     "uclstm_bn_stats_fwd": [_P, _I, _I, _I, _I, _L, _P, _P, _F, _P, _P, _P, _P, _P],
@@ -135,6 +138,7 @@ _PROTOS = {
     "uclstm_bn_pool_bwd_apply": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
     "uclstm_bn_head_fwd": [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P],
     "uclstm_bn_head_bwd_reduce": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P],
+    "uclstm_bn_head_bwd_reduce_ordered": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P],
     "uclstm_bn_head_bwd_apply": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P],
     "uclstm_bn_bwd_param_grads": [_P, _I, _I, _I, _P, _P, _I, _P],
     "uclstm_maxpool2_fwd": [_P, _P, _I, _I, _I, _I, _P],
@@ -151,12 +155,22 @@ _PROTOS = {
     "uclstm_nhwc_to_nchw_f32": [_P, _P, _I, _I, _I, _I, _I, _P],
     "uclstm_outconv_fwd": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
     "uclstm_outconv_bwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
+    "uclstm_outconv_bwd_ordered_rows": [_L, _I],
+    "uclstm_outconv_bwd_ordered": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P],
     "uclstm_colsum": [_P, _P, _L, _I, _P],
+    "uclstm_colsum_ordered_rows": [_L, _I],
+    "uclstm_colsum_ordered": [_P, _P, _P, _L, _I, _I, _I, _P],
+    "uclstm_ordered_sum_f32": [_P, _I, _I, _P, _I, _P],
+    "uclstm_ordered_sum_f64": [_P, _I, _I, _P, _I, _P],
     "uclstm_attention_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "uclstm_attention_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "uclstm_loss_fwd": [_P, _P, _P, _P, _L, _I, _I, _P],
+    "uclstm_loss_fwd_ordered_rows": [_L, _I, _I],
+    "uclstm_loss_fwd_ordered": [_P, _P, _P, _P, _P, _I, _L, _I, _I, _P],
     "uclstm_loss_bwd": [_P, _P, _P, _P, _P, _L, _I, _I, _P],
     "uclstm_sumsq": [_P, _L, _P, _P],
+    "uclstm_sumsq_ordered_rows": [_L],
+    "uclstm_sumsq_ordered": [_P, _L, _P, _P, _I, _P],
     "uclstm_adamw_step": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _F, _I, _P],
     "uclstm_adamw_step_dev": [_P, _P, _P, _P, _L, _P, _P, _P],
     "uclstm_adamw_step_groups": [_P, _P, _P, _P, _L, _P, _P, _I, _P, _I, _P, _P],
@@ -164,6 +178,8 @@ _PROTOS = {
     "uclstm_loss_scale_update": [_P, _P, _F, _F, _I, _P],
     "uclstm_dataset_transform": [_P, _P, _P, _P, _P, _L, _I, _I, _F, _F, _F, _I, _F, _F, _F, _P],
     "uclstm_metric_sums": [_P, _P, _P, _P, _L, _F, _F, _F, _P],
+    "uclstm_metric_sums_ordered_rows": [_L],
+    "uclstm_metric_sums_ordered": [_P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _P],
     "uclstm_eval_stats": [C.POINTER(EvalDesc), _P],
     "uclstm_eval_stats_rows": [_L, _L],
     "uclstm_stream_spin": [_I, _P],
@@ -173,7 +189,8 @@ _PROTOS = {
     "uclstm_last_error_string": [],
 }
 _RESTYPES = {"uclstm_build_arch": C.c_char_p, "uclstm_source_hash": C.c_char_p, "uclstm_last_error_string": C.c_char_p, "uclstm_bn_bwd_reduce_rows": C.c_int64, "uclstm_bn_pool_bwd_rows": C.c_int64,
-             "uclstm_eval_stats_rows": C.c_int64}
+             "uclstm_eval_stats_rows": C.c_int64, "uclstm_colsum_ordered_rows": C.c_int64, "uclstm_outconv_bwd_ordered_rows": C.c_int64,
+             "uclstm_loss_fwd_ordered_rows": C.c_int64, "uclstm_sumsq_ordered_rows": C.c_int64, "uclstm_metric_sums_ordered_rows": C.c_int64}
 
 
 # entry points that exist twice: name (bfloat16) and name_f16 (IEEE binary16), identical signatures (include/uclstm.h)
@@ -236,6 +253,15 @@ def kernels(dtype):
         return lib
     if dtype == torch.float16:
         return lib16
+    raise UclstmError(f"activations must be torch.bfloat16 or torch.float16, got {dtype}")
+
+
+def act_type(dtype) -> int:
+    """``act_type`` argument of the entry points that read 16-bit activations but exist once (the ordered reductions)."""
+    if dtype == torch.bfloat16:
+        return ACT_TYPE_BF16
+    if dtype == torch.float16:
+        return ACT_TYPE_F16
     raise UclstmError(f"activations must be torch.bfloat16 or torch.float16, got {dtype}")
 
 

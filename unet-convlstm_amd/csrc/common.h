@@ -38,6 +38,11 @@
 #define uclstm_colsum uclstm_colsum_f16
 #define uclstm_attention_fwd uclstm_attention_fwd_f16
 #define uclstm_attention_bwd uclstm_attention_bwd_f16
+// a body that reads 16-bit data behind an entry point that exists ONCE (explicit activation-type argument, no _f16 twin):
+// internal name, not in the public header; the bfloat16 pass defines the dispatcher
+#define UCLSTM_ACT_IMPL(fn) fn##_impl_f16
+#else
+#define UCLSTM_ACT_IMPL(fn) fn##_impl_bf16
 #endif
 #include "../../include/uclstm.h"
 

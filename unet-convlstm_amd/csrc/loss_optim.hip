@@ -1,5 +1,6 @@
 // Loss (main.py:28-72) and optimiser (main.py:106-108) kernels: one pass each over f32 planes /
-// flat parameter buffers, wave-shuffle + LDS block reduction, one f64 atomic per block.
+// flat parameter buffers, wave-shuffle + LDS block reduction, one f64 atomic per block -- or, in the ORDERED forms of the
+// three reductions (deterministic mode), one stored row of block totals per block and a second launch that adds the rows in order.
 #include "common.h"
 
 namespace {
@@ -27,9 +28,24 @@ __device__ __forceinline__ void block_sum(double (&v)[K], double* red /* [4][K] 
         for (int k = 0; k < K; ++k) v[k] = red[k] + red[K + k] + red[2 * K + k] + red[3 * K + k];
 }
 
+// the same block totals, stored: thread k < K writes column k of the block's row (the four wave sums added in the order above)
+template <int K>
+__device__ __forceinline__ void block_sum_store(double (&v)[K], double* red /* [4][K] */, double* __restrict__ row) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[wave * K + k] = v[k];
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < K) row[t] = red[t] + red[K + t] + red[2 * K + t] + red[3 * K + t];
+}
+
 __device__ __forceinline__ float sgn(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
 
-// sums: [0] sum(ad*w*m) [1] sum(w*m) [2] sum(gd*mc) [3] sum(mc)
+// sums: [0] sum(ad*w*m) [1] sum(w*m) [2] sum(gd*mc) [3] sum(mc).  ORDERED: sums is the partial buffer [gridDim.x][4], no atomics
+template <bool ORDERED>
 __global__ void loss_fwd_kernel(const float* __restrict__ yp, const float* __restrict__ y, const float* __restrict__ mask,
                                 double* __restrict__ sums, int64_t total, FastDiv dHW, FastDiv dW, int H, int W) {
     __shared__ double red[16];
@@ -53,10 +69,14 @@ __global__ void loss_fwd_kernel(const float* __restrict__ yp, const float* __res
             acc[3] += (double)m;
         }
     }
-    block_sum<4>(acc, red);
-    if (threadIdx.x == 0)
+    if constexpr (ORDERED) {
+        block_sum_store<4>(acc, red, sums + (int64_t)blockIdx.x * 4);
+    } else {
+        block_sum<4>(acc, red);
+        if (threadIdx.x == 0)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) atomicAdd(sums + k, acc[k]);
+            for (int k = 0; k < 4; ++k) atomicAdd(sums + k, acc[k]);
+    }
 }
 
 __global__ void loss_bwd_kernel(const float* __restrict__ yp, const float* __restrict__ y, const float* __restrict__ mask,
@@ -94,6 +114,8 @@ __global__ void loss_bwd_kernel(const float* __restrict__ yp, const float* __res
     }
 }
 
+// ORDERED: out is the partial buffer [gridDim.x], no atomics
+template <bool ORDERED>
 __global__ void sumsq_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ out) {
     __shared__ double red[4];
     double acc[1] = {0.0};
@@ -107,8 +129,12 @@ __global__ void sumsq_kernel(const float* __restrict__ g, int64_t n, double* __r
         const float v = g[(n4 << 2) + threadIdx.x];
         acc[0] += (double)(v * v);
     }
-    block_sum<1>(acc, red);
-    if (threadIdx.x == 0) atomicAdd(out, acc[0]);
+    if constexpr (ORDERED) {
+        block_sum_store<1>(acc, red, out + blockIdx.x);
+    } else {
+        block_sum<1>(acc, red);
+        if (threadIdx.x == 0) atomicAdd(out, acc[0]);
+    }
 }
 
 __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g,
@@ -349,7 +375,8 @@ __global__ void dataset_transform_kernel(const float* __restrict__ xr, const flo
 }
 
 // Epoch metrics of main.py:114-142 as running sums: de-normalise (train/unet.py:316-319) prediction and target,
-// d = pred - target, sums += (sum |d| m, sum d^2 m, sum d m, sum m)
+// d = pred - target, sums += (sum |d| m, sum d^2 m, sum d m, sum m).  ORDERED: sums is the partial buffer [gridDim.x][4], no atomics
+template <bool ORDERED>
 __global__ void metric_sums_kernel(const float* __restrict__ yp, const float* __restrict__ y, const float* __restrict__ mask,
                                    double* __restrict__ sums, int64_t n, float yscale, float tmin, float trange) {
     __shared__ double red[16];
@@ -364,10 +391,34 @@ __global__ void metric_sums_kernel(const float* __restrict__ yp, const float* __
         acc[2] += d * m;
         acc[3] += m;
     }
-    block_sum<4>(acc, red);
-    if (threadIdx.x == 0)
+    if constexpr (ORDERED) {
+        block_sum_store<4>(acc, red, sums + (int64_t)blockIdx.x * 4);
+    } else {
+        block_sum<4>(acc, red);
+        if (threadIdx.x == 0)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) atomicAdd(sums + k, acc[k]);
+            for (int k = 0; k < 4; ++k) atomicAdd(sums + k, acc[k]);
+    }
+}
+
+// Stage 2 of the ordered f64 reductions: thread c owns output column c and adds the `rows` block partials of that column strictly
+// in row order, out[c] = (accumulate ? out[c] : 0) + p[0][c] + p[1][c] + ... (eight loads in flight, one dependent chain of adds).
+__global__ __launch_bounds__(64) void ordered_sum_f64_kernel(const double* __restrict__ p, int rows, int cols, double* __restrict__ out,
+                                                            int accumulate) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= cols) return;
+    double acc = accumulate ? out[c] : 0.0;
+    const double* q = p + c;
+    int r = 0;
+    for (; r + 8 <= rows; r += 8) {
+        double t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t[u] = q[(int64_t)(r + u) * cols];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += t[u];
+    }
+    for (; r < rows; ++r) acc += q[(int64_t)r * cols];
+    out[c] = acc;
 }
 
 int grid_for(int64_t items, int cap) {
@@ -375,6 +426,7 @@ int grid_for(int64_t items, int cap) {
     if (b > cap) b = cap;
     return (int)(b < 1 ? 1 : b);
 }
+constexpr int ORDERED_ROWS_CAP = 1024;          // = the grids of the atomic forms: the producers are the same launches
 
 }  // namespace
 
@@ -383,7 +435,7 @@ extern "C" int32_t uclstm_loss_fwd(const float* y_pred, const float* y, const fl
     if (!y_pred || !y || !sums || planes <= 0 || H <= 0 || W <= 0) return UCLSTM_E_BADARG;
     const int64_t total = planes * H * W;
     if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
-    UCLSTM_LAUNCH(loss_fwd_kernel, dim3(grid_for(total, 1024)), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, sums, total,
+    UCLSTM_LAUNCH(loss_fwd_kernel<false>, dim3(grid_for(total, 1024)), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, sums, total,
                        make_fastdiv(H * W), make_fastdiv(W), H, W);
     return UCLSTM_OK;
 }
@@ -400,7 +452,7 @@ extern "C" int32_t uclstm_loss_bwd(const float* y_pred, const float* y, const fl
 
 extern "C" int32_t uclstm_sumsq(const float* g, int64_t n, double* out, void* stream) {
     if (!g || !out || n <= 0 || ((uintptr_t)g % 16)) return UCLSTM_E_BADARG;
-    UCLSTM_LAUNCH(sumsq_kernel, dim3(grid_for((n + 3) / 4, 1024)), dim3(NT), 0, (hipStream_t)stream, g, n, out);
+    UCLSTM_LAUNCH(sumsq_kernel<false>, dim3(grid_for((n + 3) / 4, 1024)), dim3(NT), 0, (hipStream_t)stream, g, n, out);
     return UCLSTM_OK;
 }
 
@@ -468,8 +520,57 @@ extern "C" int32_t uclstm_dataset_transform(const float* x_raw, const float* y_r
 extern "C" int32_t uclstm_metric_sums(const float* y_pred, const float* y, const float* mask, double* sums, int64_t n, float y_scale,
                                       float trans_min, float trans_max, void* stream) {
     if (!y_pred || !y || !sums || n <= 0) return UCLSTM_E_BADARG;
-    UCLSTM_LAUNCH(metric_sums_kernel, dim3(grid_for(n, 1024)), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, sums, n, y_scale,
+    UCLSTM_LAUNCH(metric_sums_kernel<false>, dim3(grid_for(n, 1024)), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, sums, n, y_scale,
                   trans_min, trans_max - trans_min);
+    return UCLSTM_OK;
+}
+
+// ---- ordered (deterministic-mode) forms of the three f64 reductions: producer rows + ordered_sum_f64_kernel ----
+extern "C" int64_t uclstm_loss_fwd_ordered_rows(int64_t planes, int32_t H, int32_t W) {
+    if (planes <= 0 || H <= 0 || W <= 0 || planes * H * W >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    return grid_for(planes * H * W, ORDERED_ROWS_CAP);
+}
+extern "C" int32_t uclstm_loss_fwd_ordered(const float* y_pred, const float* y, const float* mask, double* partials, double* sums,
+                                           int32_t accumulate, int64_t planes, int32_t H, int32_t W, void* stream) {
+    if (!y_pred || !y || !partials || !sums || planes <= 0 || H <= 0 || W <= 0) return UCLSTM_E_BADARG;
+    const int64_t total = planes * H * W;
+    if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    const int rows = grid_for(total, ORDERED_ROWS_CAP);
+    UCLSTM_LAUNCH(loss_fwd_kernel<true>, dim3(rows), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, partials, total, make_fastdiv(H * W),
+                  make_fastdiv(W), H, W);
+    UCLSTM_LAUNCH(ordered_sum_f64_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, rows, 4, sums, accumulate);
+    return UCLSTM_OK;
+}
+
+extern "C" int64_t uclstm_sumsq_ordered_rows(int64_t n) {
+    if (n <= 0) return UCLSTM_E_BADARG;
+    return grid_for((n + 3) / 4, ORDERED_ROWS_CAP);
+}
+extern "C" int32_t uclstm_sumsq_ordered(const float* g, int64_t n, double* partials, double* out, int32_t accumulate, void* stream) {
+    if (!g || !partials || !out || n <= 0 || ((uintptr_t)g % 16)) return UCLSTM_E_BADARG;
+    const int rows = grid_for((n + 3) / 4, ORDERED_ROWS_CAP);
+    UCLSTM_LAUNCH(sumsq_kernel<true>, dim3(rows), dim3(NT), 0, (hipStream_t)stream, g, n, partials);
+    UCLSTM_LAUNCH(ordered_sum_f64_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, rows, 1, out, accumulate);
+    return UCLSTM_OK;
+}
+
+extern "C" int64_t uclstm_metric_sums_ordered_rows(int64_t n) {
+    if (n <= 0) return UCLSTM_E_BADARG;
+    return grid_for(n, ORDERED_ROWS_CAP);
+}
+extern "C" int32_t uclstm_metric_sums_ordered(const float* y_pred, const float* y, const float* mask, double* partials, double* sums,
+                                              int32_t accumulate, int64_t n, float y_scale, float trans_min, float trans_max, void* stream) {
+    if (!y_pred || !y || !partials || !sums || n <= 0) return UCLSTM_E_BADARG;
+    const int rows = grid_for(n, ORDERED_ROWS_CAP);
+    UCLSTM_LAUNCH(metric_sums_kernel<true>, dim3(rows), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, partials, n, y_scale, trans_min,
+                  trans_max - trans_min);
+    UCLSTM_LAUNCH(ordered_sum_f64_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, rows, 4, sums, accumulate);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_ordered_sum_f64(const double* partials, int32_t rows, int32_t cols, double* out, int32_t accumulate, void* stream) {
+    if (!partials || !out || rows <= 0 || cols <= 0) return UCLSTM_E_BADARG;
+    UCLSTM_LAUNCH(ordered_sum_f64_kernel, dim3((cols + 63) / 64), dim3(64), 0, (hipStream_t)stream, partials, rows, cols, out, accumulate);
     return UCLSTM_OK;
 }
 

@@ -96,6 +96,13 @@ __global__ void pack_kernel(const uclstm_pack_desc d, const PackDiv dv, const fl
 // grid.y > 1 (accumulate only): slab group blockIdx.y adds its share of the slabs with one f32 atomic per element -- for the
 // small panels whose weight gradient used hundreds of pixel ranges (first layer: 4096 elements x ~1000 slabs), where one
 // thread per element would walk all the slabs serially.
+// Ordered form of that split (deterministic mode), two launches and no atomics: UNPACK_GROUP_SUMS -- slab group blockIdx.y adds its
+// slabs s0 .. s1-1 in that order, exactly as the grid.y == 1 path does, and STORES the sum to grad[blockIdx.y * total + idx] (grad
+// is then the caller's scratch [groups][N * Ktot]; every element of every group's row is written, zeros where the group holds no
+// slab or the element is padding); UNPACK_GROUP_FINISH -- dwp is that scratch, nslab the number of groups, and one thread per
+// element adds the groups in index order: grad = (accumulate ? grad : 0) + s[0] + s[1] + ..., left to right.
+enum { UNPACK_PLAIN = 0, UNPACK_GROUP_SUMS = 1, UNPACK_GROUP_FINISH = 2 };
+template <int MODE>
 __global__ void unpack_kernel(const uclstm_pack_desc d, const PackDiv dv, const float* __restrict__ dwp, int nslab, int64_t slab,
                               float* __restrict__ grad, int accumulate) {
     const uint32_t total = (uint32_t)d.N * (uint32_t)d.Ktot;
@@ -105,7 +112,18 @@ __global__ void unpack_kernel(const uclstm_pack_desc d, const PackDiv dv, const 
         const int n = (int)fdiv(idx, dv.ktot);
         const int k = (int)(idx - (uint32_t)n * (uint32_t)d.Ktot);
         const Decoded r = decode(d, dv, n, k);
-        if (r.valid && s0 < s1) {
+        if constexpr (MODE == UNPACK_GROUP_SUMS) {
+            float v = 0.f;
+            if (r.valid)
+                for (int sl = s0; sl < s1; ++sl) v += dwp[sl * slab + idx];
+            grad[(int64_t)blockIdx.y * total + idx] = v;
+        } else if constexpr (MODE == UNPACK_GROUP_FINISH) {
+            if (r.valid) {
+                float v = accumulate ? grad[r.off] : 0.f;
+                for (int sl = 0; sl < nslab; ++sl) v += dwp[sl * slab + idx];
+                grad[r.off] = v;
+            }
+        } else if (r.valid && s0 < s1) {
             float v = 0.f;
             for (int sl = s0; sl < s1; ++sl) v += dwp[sl * slab + idx];      // partial panels of the pixel ranges
             if (gridDim.y > 1) atomicAdd(grad + r.off, v);
@@ -489,8 +507,31 @@ extern "C" int32_t uclstm_pack_weights_batched(const uclstm_pack_job* jobs_dev, 
 }
 
 #ifndef UCLSTM_ACT_F16
-extern "C" int32_t uclstm_unpack_wgrad(const uclstm_pack_desc* d, const float* dwp, int32_t nslab, int64_t slab, float* grad,
-                                       int32_t accumulate, void* stream) {
+// few elements, many slabs: spread the slabs over grid.y until the launch has ~1024 blocks, at least four slabs per group
+static int generic_slab_groups(const uclstm_pack_desc& d, int nslab) {
+    const int gx = grid_for((int64_t)d.N * d.Ktot);
+    int gy = 1;
+    if (nslab >= 16 && gx < 512) {
+        gy = 1024 / gx;
+        if (gy > nslab / 4) gy = nslab / 4;
+        if (gy < 1) gy = 1;
+    }
+    return gy;
+}
+// Slab groups of the ordered unpack, a function of the descriptor and the slab count alone: 1 wherever uclstm_unpack_wgrad folds
+// the slabs or takes the row-family kernel.
+static int unpack_slab_groups(const uclstm_pack_desc& d, int nslab) {
+    if (rows_family(d)) {
+        if (nslab <= 64) return 1;
+        // folded first (the fold also needs 16-byte aligned slabs; the GEMM's scratch has them, others are merely slower below)
+        if (((int64_t)d.N * d.Ktot % 4) == 0) return 1;
+    }
+    return generic_slab_groups(d, nslab);
+}
+
+// split: the slabs of a small generic panel may be spread over grid.y and added with atomics
+static int32_t unpack_wgrad_impl(const uclstm_pack_desc* d, const float* dwp, int32_t nslab, int64_t slab, float* grad,
+                                 int32_t accumulate, void* stream, bool split) {
     if (!desc_ok(d) || !dwp || !grad || nslab < 1 || (nslab > 1 && slab < (int64_t)d->N * d->Ktot)) return UCLSTM_E_BADARG;
     if (rows_family(*d) && nslab > 64 && (slab % 4) == 0 && ((int64_t)d->N * d->Ktot % 4) == 0 && ((uintptr_t)dwp % 16) == 0) {
         // hundreds of small slabs: fold them into slab 0 first (the slabs are scratch of the weight-gradient GEMM and are
@@ -511,15 +552,36 @@ extern "C" int32_t uclstm_unpack_wgrad(const uclstm_pack_desc* d, const float* d
                           slab, grad, accumulate, ch0);
         return UCLSTM_OK;
     }
-    // few elements, many slabs: spread the slabs over grid.y (atomic accumulate) until the launch has ~1024 blocks
     const int gx = grid_for((int64_t)d->N * d->Ktot);
-    int gy = 1;
-    if (accumulate && nslab >= 16 && gx < 512) {
-        gy = 1024 / gx;
-        if (gy > nslab / 4) gy = nslab / 4;
-        if (gy < 1) gy = 1;
-    }
-    UCLSTM_LAUNCH(unpack_kernel, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, make_pack_div(*d), dwp, nslab, slab, grad, accumulate);
+    const int gy = (accumulate && split) ? generic_slab_groups(*d, nslab) : 1;
+    UCLSTM_LAUNCH(unpack_kernel<UNPACK_PLAIN>, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, make_pack_div(*d), dwp, nslab, slab, grad,
+                  accumulate);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_unpack_wgrad(const uclstm_pack_desc* d, const float* dwp, int32_t nslab, int64_t slab, float* grad,
+                                       int32_t accumulate, void* stream) {
+    return unpack_wgrad_impl(d, dwp, nslab, slab, grad, accumulate, stream, true);
+}
+
+extern "C" int32_t uclstm_unpack_wgrad_ordered_groups(const uclstm_pack_desc* d, int32_t nslab) {
+    if (!desc_ok(d) || nslab < 1) return UCLSTM_E_BADARG;
+    return unpack_slab_groups(*d, nslab);
+}
+
+extern "C" int32_t uclstm_unpack_wgrad_ordered(const uclstm_pack_desc* d, const float* dwp, int32_t nslab, int64_t slab, float* scratch,
+                                               float* grad, int32_t accumulate, void* stream) {
+    if (!desc_ok(d) || nslab < 1) return UCLSTM_E_BADARG;
+    const int groups = unpack_slab_groups(*d, nslab);
+    // one group: the fold / row-family / one-thread-per-element paths of uclstm_unpack_wgrad, which add the slabs in index order
+    if (groups == 1) return unpack_wgrad_impl(d, dwp, nslab, slab, grad, accumulate, stream, false);
+    if (!dwp || !grad || !scratch || slab < (int64_t)d->N * d->Ktot) return UCLSTM_E_BADARG;
+    const int gx = grid_for((int64_t)d->N * d->Ktot);
+    const int64_t total = (int64_t)d->N * d->Ktot;
+    UCLSTM_LAUNCH(unpack_kernel<UNPACK_GROUP_SUMS>, dim3(gx, groups), dim3(256), 0, (hipStream_t)stream, *d, make_pack_div(*d), dwp, nslab, slab,
+                  scratch, 0);
+    UCLSTM_LAUNCH(unpack_kernel<UNPACK_GROUP_FINISH>, dim3(gx, 1), dim3(256), 0, (hipStream_t)stream, *d, make_pack_div(*d), scratch, groups,
+                  total, grad, accumulate);
     return UCLSTM_OK;
 }
 #endif

@@ -2,7 +2,8 @@
 // the ConvLSTM backward point-wise part, layout conversion at the module boundary, OutConv 1x1 and
 // column sums.  All move 16 bytes (8 act16 channels) per lane per access on NHWC tensors; reductions
 // over pixels keep a fixed channel chunk per thread, reduce across the block in LDS and finish with
-// one f32 atomic per (block, channel).
+// one f32 atomic per (block, channel) -- or, in their ORDERED instances (deterministic mode), with one
+// stored row of block totals per block that a second launch adds in row order.
 #include "common.h"
 #include <algorithm>
 #include <cstdlib>
@@ -749,7 +750,9 @@ __global__ void bn_head_fwd_kernel(const uint4* __restrict__ z, const float* __r
 }
 
 // partials as bn_bwd_reduce_kernel; additionally dw[c] += sum_p dy[p] * a[p][c], db += sum_p dy[p] (one f32 atomic per block
-// and element, as outconv_bwd_dw_kernel)
+// and element, as outconv_bwd_dw_kernel).  ORDERED: no atomics; `dw` is then the block-partial buffer [gridDim.x][C + 1] (C head
+// weight columns, then the bias column), every block stores its own row, ordered_sum_f32_kernel adds the rows in index order.
+template <bool ORDERED>
 __global__ void bn_head_bwd_reduce_kernel(const uint4* __restrict__ z, const float* __restrict__ dy, const float* __restrict__ scale,
                                           const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ rstd,
                                           const float* __restrict__ w, float* __restrict__ partials, float* __restrict__ dw,
@@ -838,9 +841,14 @@ __global__ void bn_head_bwd_reduce_kernel(const uint4* __restrict__ z, const flo
             if (ch < Cp) partials[((long)blockIdx.x * Cp + ch) * 2 + (j & 1)] = t;
         } else if (j < cg.cpc * 24) {
             const int ch = j - cg.cpc * 16;
-            if (ch < C) atomicAdd(dw + ch, t);
+            if constexpr (ORDERED) {
+                if (ch < C) dw[(long)blockIdx.x * (C + 1) + ch] = t;
+            } else {
+                if (ch < C) atomicAdd(dw + ch, t);
+            }
         } else {
-            atomicAdd(db, t);
+            if constexpr (ORDERED) dw[(long)blockIdx.x * (C + 1) + C] = t;
+            else atomicAdd(db, t);
         }
     }
 }
@@ -1245,7 +1253,9 @@ __global__ void outconv_bwd_da_kernel(const float* __restrict__ w, const float* 
     }
 }
 
-// dw[co][c] += sum_p dy[p][co]*a[p][c]; db[co] += sum_p dy[p][co]   (one co per blockIdx.y)
+// dw[co][c] += sum_p dy[p][co]*a[p][c]; db[co] += sum_p dy[p][co]   (one co per blockIdx.y).  ORDERED: no atomics; `dw` is then the
+// block-partial buffer [gridDim.x][Co*C + Co] (the dw columns, then the db columns) and every block stores its share of its row.
+template <bool ORDERED>
 __global__ void outconv_bwd_dw_kernel(const uint4* __restrict__ a, const float* __restrict__ dy, float* __restrict__ dw,
                                       float* __restrict__ db, int64_t pixels, FastDiv dHW, ColGeom cg, int C, int Co,
                                       int64_t pix_per_block) {
@@ -1279,16 +1289,28 @@ __global__ void outconv_bwd_dw_kernel(const uint4* __restrict__ a, const float* 
     for (int j = threadIdx.x; j < width; j += NT) {
         float t = 0.f;
         for (int r = 0; r < cg.rows; ++r) t += red[r * width + j];
-        if (j < cg.cpc * 8) {
-            if (j < C) atomicAdd(dw + co * C + j, t);
+        if constexpr (ORDERED) {
+            float* row = dw + (int64_t)blockIdx.x * (Co * C + Co);
+            if (j < cg.cpc * 8) {
+                if (j < C) row[co * C + j] = t;
+            } else {
+                row[Co * C + co] = t;
+            }
         } else {
-            atomicAdd(db + co, t);
+            if (j < cg.cpc * 8) {
+                if (j < C) atomicAdd(dw + co * C + j, t);
+            } else {
+                atomicAdd(db + co, t);
+            }
         }
     }
 }
 
 // Column sums of a [pixels][Cp] act16 tensor (bias gradients).  grid.x = pixel ranges, grid.y = groups of NT 16-byte
 // column chunks; a thread owns one chunk column of `rows` interleaved pixel rows and keeps four loads in flight.
+// ORDERED: no atomics; `out` is then the block-partial buffer [gridDim.x][Cp], pixel range blockIdx.x stores row blockIdx.x (zeros
+// from a range that holds no pixels) and ordered_sum_f32_kernel adds the rows in index order.
+template <bool ORDERED>
 __global__ void colsum_kernel(const uint4* __restrict__ a, float* __restrict__ out, int64_t pixels, ColGeom cg, int Cp,
                               int64_t pix_per_block) {
     extern __shared__ float red[];   // [rows][min(cpc,NT)*8]
@@ -1339,8 +1361,34 @@ __global__ void colsum_kernel(const uint4* __restrict__ a, float* __restrict__ o
         float t = 0.f;
         for (int r = 0; r < cg.rows; ++r) t += red[r * width + j];
         const int ch = cbase * 8 + j;
-        if (ch < Cp && (cg.cpc >= NT ? (cbase + j / 8) < cg.cpc : true)) atomicAdd(out + ch, t);
+        if (ch < Cp && (cg.cpc >= NT ? (cbase + j / 8) < cg.cpc : true)) {
+            if constexpr (ORDERED) out[(int64_t)blockIdx.x * Cp + ch] = t;
+            else atomicAdd(out + ch, t);
+        }
     }
+}
+
+// Stage 2 of every ordered f32 reduction: thread c owns output column c and adds the `rows` block partials of that column strictly
+// in row order, out = (accumulate ? out : 0) + p[0][c] + p[1][c] + ... (eight loads in flight, the additions one dependent chain:
+// the result is a function of the partials alone).  Columns [0, n0) go to out0, [n0, cols) to out1; a NULL output is skipped.
+__global__ __launch_bounds__(64) void ordered_sum_f32_kernel(const float* __restrict__ p, int rows, int cols, float* __restrict__ out0,
+                                                            int n0, float* __restrict__ out1, int accumulate) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= cols) return;
+    float* o = c < n0 ? (out0 ? out0 + c : nullptr) : (out1 ? out1 + (c - n0) : nullptr);
+    if (!o) return;
+    float acc = accumulate ? *o : 0.f;
+    const float* q = p + c;
+    int r = 0;
+    for (; r + 8 <= rows; r += 8) {
+        float t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t[u] = q[(int64_t)(r + u) * cols];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += t[u];
+    }
+    for (; r < rows; ++r) acc += q[(int64_t)r * cols];
+    *o = acc;
 }
 
 bool aligned16(const void* p) { return p && ((uintptr_t)p % 16) == 0; }
@@ -1745,7 +1793,7 @@ extern "C" int32_t uclstm_bn_head_bwd_reduce(const void* z, const float* dy, con
     const int bpg = bn_bwd_blocks_per_group(pixels_per_group, groups);          // = uclstm_bn_bwd_reduce_rows / groups
     const int64_t ppb = (pixels_per_group + bpg - 1) / bpg;
     const size_t lds = (size_t)cg.rows * (cg.cpc * 24 + 1) * sizeof(float);
-    UCLSTM_LAUNCH(bn_head_bwd_reduce_kernel, dim3(groups * bpg), dim3(NT), lds, (hipStream_t)stream, (const uint4*)z, dy, scale, shift, mean,
+    UCLSTM_LAUNCH(bn_head_bwd_reduce_kernel<false>, dim3(groups * bpg), dim3(NT), lds, (hipStream_t)stream, (const uint4*)z, dy, scale, shift, mean,
                   rstd, w, partials, dw, db, pixels_per_group, Cp, C, cg, bpg, ppb);
     UCLSTM_LAUNCH(bn_bwd_sum_kernel, dim3((Cp * 2 + 31) / 32, groups), dim3(256), 0, (hipStream_t)stream, partials, sums, bpg, Cp);
     return UCLSTM_OK;
@@ -2025,7 +2073,7 @@ extern "C" int32_t uclstm_outconv_bwd(const void* a, const float* w, const float
         if (nb > 1024) nb = 1024;
         const int64_t ppb = (pixels + nb - 1) / nb;
         const size_t lds = (size_t)cg.rows * (cg.cpc * 8 + 1) * sizeof(float);
-        UCLSTM_LAUNCH(outconv_bwd_dw_kernel, dim3(nb, Co), dim3(NT), lds, (hipStream_t)stream, (const uint4*)a, dy, dw, db, pixels,
+        UCLSTM_LAUNCH(outconv_bwd_dw_kernel<false>, dim3(nb, Co), dim3(NT), lds, (hipStream_t)stream, (const uint4*)a, dy, dw, db, pixels,
                            make_fastdiv(HW), cg, C, Co, ppb);
     }
     return UCLSTM_OK;
@@ -2042,9 +2090,151 @@ extern "C" int32_t uclstm_colsum(const void* a, float* out, int64_t pixels, int3
     if (nb < 1) nb = 1;
     const int64_t ppb = (pixels + nb - 1) / nb;
     const size_t lds = (size_t)cg.rows * (cg.cpc < NT ? cg.cpc : NT) * 8 * sizeof(float);
-    UCLSTM_LAUNCH(colsum_kernel, dim3((unsigned)nb, (unsigned)ncg), dim3(NT), lds, (hipStream_t)stream, (const uint4*)a, out, pixels, cg, Cp, ppb);
+    UCLSTM_LAUNCH(colsum_kernel<false>, dim3((unsigned)nb, (unsigned)ncg), dim3(NT), lds, (hipStream_t)stream, (const uint4*)a, out, pixels, cg, Cp, ppb);
     return UCLSTM_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Ordered (deterministic-mode) forms of the three reductions above that end in f32 atomics
+// ---------------------------------------------------------------------------------------------
+// Two launches each, as uclstm_bn_bwd_reduce: the producer (the same kernel body, ORDERED) stores one row of block totals per pixel
+// range into caller-owned `partials`, ordered_sum_f32_kernel adds the rows in index order.  The bodies read 16-bit activations, so
+// they are compiled in both passes under UCLSTM_ACT_IMPL(name); the public entry points (one symbol each, explicit activation
+// type) exist in the bfloat16 pass only and dispatch.
+namespace {
+constexpr int ORDERED_ROWS_CAP = 1024;          // as the BatchNorm reductions (bn_bwd_blocks_per_group): the finisher's chain stays a few us
+
+inline int colsum_ordered_blocks(int64_t pixels, const ColGeom& cg) {
+    // at least 32 pixels per thread row, as uclstm_colsum
+    int64_t nb = (pixels + 32 * cg.rows - 1) / (32 * cg.rows);
+    if (nb > ORDERED_ROWS_CAP) nb = ORDERED_ROWS_CAP;
+    return (int)(nb < 1 ? 1 : nb);
+}
+inline int outconv_ordered_blocks(int64_t pixels) {
+    int64_t nb = (pixels + 1023) / 1024;              // as uclstm_outconv_bwd
+    if (nb > ORDERED_ROWS_CAP) nb = ORDERED_ROWS_CAP;
+    return (int)(nb < 1 ? 1 : nb);
+}
+}  // namespace
+
+__attribute__((visibility("hidden"))) int32_t UCLSTM_ACT_IMPL(colsum_ordered)(const void* a, float* partials, float* out, int64_t pixels,
+                                                                             int32_t Cp, int32_t accumulate, void* stream) {
+    if (!aligned16(a) || !partials || !out || pixels <= 0 || Cp <= 0 || (Cp % 8)) return UCLSTM_E_BADARG;
+    const ColGeom cg = col_geom(Cp);
+    const int ncg = (cg.cpc + NT - 1) / NT;
+    const int nb = colsum_ordered_blocks(pixels, cg);
+    const int64_t ppb = (pixels + nb - 1) / nb;
+    const size_t lds = (size_t)cg.rows * (cg.cpc < NT ? cg.cpc : NT) * 8 * sizeof(float);
+    UCLSTM_LAUNCH(colsum_kernel<true>, dim3((unsigned)nb, (unsigned)ncg), dim3(NT), lds, (hipStream_t)stream, (const uint4*)a, partials, pixels,
+                  cg, Cp, ppb);
+    UCLSTM_LAUNCH(ordered_sum_f32_kernel, dim3((Cp + 63) / 64), dim3(64), 0, (hipStream_t)stream, partials, nb, Cp, out, Cp, nullptr,
+                  accumulate);
+    return UCLSTM_OK;
+}
+
+__attribute__((visibility("hidden"))) int32_t UCLSTM_ACT_IMPL(outconv_bwd_ordered)(const void* a, const float* w, const float* dy, void* da,
+                                                                                  float* partials, float* dw, float* db, int32_t accumulate,
+                                                                                  int64_t n_img, int32_t HW, int32_t Cp, int32_t C, int32_t Co,
+                                                                                  void* stream) {
+    if (!aligned16(a) || !w || !dy || n_img <= 0 || HW <= 0 || Cp < C || (Cp % 8) || C <= 0 || Co <= 0 || Cp / 8 > NT)
+        return UCLSTM_E_BADARG;
+    if ((dw || db) && !partials) return UCLSTM_E_BADARG;
+    const int64_t pixels = n_img * HW;
+    const int64_t chunks = pixels * (Cp / 8);
+    if (chunks >= ((int64_t)1 << 31) || (int64_t)Co * (C + 1) >= ((int64_t)1 << 24)) return UCLSTM_E_BADARG;
+    if (da) {
+        if (!aligned16(da)) return UCLSTM_E_BADARG;
+        UCLSTM_LAUNCH(outconv_bwd_da_kernel, dim3(ew_grid(chunks)), dim3(NT), 0, (hipStream_t)stream, w, dy, (uint4*)da, chunks,
+                      make_fastdiv(Cp / 8), make_fastdiv(HW), C, Co);
+    }
+    if (dw || db) {
+        const ColGeom cg = col_geom(Cp);
+        const int nb = outconv_ordered_blocks(pixels);
+        const int64_t ppb = (pixels + nb - 1) / nb;
+        const size_t lds = (size_t)cg.rows * (cg.cpc * 8 + 1) * sizeof(float);
+        const int cols = Co * C + Co;
+        UCLSTM_LAUNCH(outconv_bwd_dw_kernel<true>, dim3(nb, Co), dim3(NT), lds, (hipStream_t)stream, (const uint4*)a, dy, partials, nullptr,
+                      pixels, make_fastdiv(HW), cg, C, Co, ppb);
+        UCLSTM_LAUNCH(ordered_sum_f32_kernel, dim3((cols + 63) / 64), dim3(64), 0, (hipStream_t)stream, partials, nb, cols, dw, Co * C, db,
+                      accumulate);
+    }
+    return UCLSTM_OK;
+}
+
+__attribute__((visibility("hidden"))) int32_t UCLSTM_ACT_IMPL(bn_head_bwd_reduce_ordered)(
+    const void* z, const float* dy, const float* scale, const float* shift, const float* mean, const float* rstd, const float* w,
+    float* partials, float* head_partials, float* sums, float* dw, float* db, int64_t pixels, int64_t pixels_per_group, int32_t Cp,
+    int32_t C, void* stream) {
+    if (!aligned16(z) || !dy || !scale || !shift || !mean || !rstd || !w || !partials || !head_partials || !sums || !dw || !db ||
+        pixels <= 0 || pixels_per_group <= 0 || (pixels % pixels_per_group) || !head_geom_ok(Cp, C))
+        return UCLSTM_E_BADARG;
+    const ColGeom cg = col_geom(Cp);
+    const int groups = (int)(pixels / pixels_per_group);
+    const int bpg = bn_bwd_blocks_per_group(pixels_per_group, groups);          // = uclstm_bn_bwd_reduce_rows / groups
+    const int64_t ppb = (pixels_per_group + bpg - 1) / bpg;
+    const size_t lds = (size_t)cg.rows * (cg.cpc * 24 + 1) * sizeof(float);
+    UCLSTM_LAUNCH(bn_head_bwd_reduce_kernel<true>, dim3(groups * bpg), dim3(NT), lds, (hipStream_t)stream, (const uint4*)z, dy, scale, shift,
+                  mean, rstd, w, partials, head_partials, nullptr, pixels_per_group, Cp, C, cg, bpg, ppb);
+    UCLSTM_LAUNCH(bn_bwd_sum_kernel, dim3((Cp * 2 + 31) / 32, groups), dim3(256), 0, (hipStream_t)stream, partials, sums, bpg, Cp);
+    UCLSTM_LAUNCH(ordered_sum_f32_kernel, dim3((C + 1 + 63) / 64), dim3(64), 0, (hipStream_t)stream, head_partials, groups * bpg, C + 1, dw, C,
+                  db, 1);
+    return UCLSTM_OK;
+}
+
+#ifndef UCLSTM_ACT_F16
+int32_t colsum_ordered_impl_f16(const void*, float*, float*, int64_t, int32_t, int32_t, void*);
+int32_t outconv_bwd_ordered_impl_f16(const void*, const float*, const float*, void*, float*, float*, float*, int32_t, int64_t, int32_t, int32_t,
+                                     int32_t, int32_t, void*);
+int32_t bn_head_bwd_reduce_ordered_impl_f16(const void*, const float*, const float*, const float*, const float*, const float*, const float*,
+                                            float*, float*, float*, float*, float*, int64_t, int64_t, int32_t, int32_t, void*);
+
+extern "C" int64_t uclstm_colsum_ordered_rows(int64_t pixels, int32_t Cp) {
+    if (pixels <= 0 || Cp <= 0 || (Cp % 8)) return UCLSTM_E_BADARG;
+    return colsum_ordered_blocks(pixels, col_geom(Cp));
+}
+
+extern "C" int32_t uclstm_colsum_ordered(const void* a, float* partials, float* out, int64_t pixels, int32_t Cp, int32_t accumulate,
+                                         int32_t act_type, void* stream) {
+    if (act_type == UCLSTM_ACT_TYPE_BF16) return UCLSTM_ACT_IMPL(colsum_ordered)(a, partials, out, pixels, Cp, accumulate, stream);
+    if (act_type == UCLSTM_ACT_TYPE_F16) return colsum_ordered_impl_f16(a, partials, out, pixels, Cp, accumulate, stream);
+    return UCLSTM_E_BADARG;
+}
+
+extern "C" int64_t uclstm_outconv_bwd_ordered_rows(int64_t n_img, int32_t HW) {
+    if (n_img <= 0 || HW <= 0) return UCLSTM_E_BADARG;
+    return outconv_ordered_blocks(n_img * HW);
+}
+
+extern "C" int32_t uclstm_outconv_bwd_ordered(const void* a, const float* w, const float* dy, void* da, float* partials, float* dw, float* db,
+                                              int32_t accumulate, int64_t n_img, int32_t HW, int32_t Cp, int32_t C, int32_t Co,
+                                              int32_t act_type, void* stream) {
+    if (act_type == UCLSTM_ACT_TYPE_BF16)
+        return UCLSTM_ACT_IMPL(outconv_bwd_ordered)(a, w, dy, da, partials, dw, db, accumulate, n_img, HW, Cp, C, Co, stream);
+    if (act_type == UCLSTM_ACT_TYPE_F16)
+        return outconv_bwd_ordered_impl_f16(a, w, dy, da, partials, dw, db, accumulate, n_img, HW, Cp, C, Co, stream);
+    return UCLSTM_E_BADARG;
+}
+
+extern "C" int32_t uclstm_bn_head_bwd_reduce_ordered(const void* z, const float* dy, const float* scale, const float* shift,
+                                                     const float* mean, const float* rstd, const float* w, float* partials,
+                                                     float* head_partials, float* sums, float* dw, float* db, int64_t pixels,
+                                                     int64_t pixels_per_group, int32_t Cp, int32_t C, int32_t act_type, void* stream) {
+    if (act_type == UCLSTM_ACT_TYPE_BF16)
+        return UCLSTM_ACT_IMPL(bn_head_bwd_reduce_ordered)(z, dy, scale, shift, mean, rstd, w, partials, head_partials, sums, dw, db, pixels,
+                                                           pixels_per_group, Cp, C, stream);
+    if (act_type == UCLSTM_ACT_TYPE_F16)
+        return bn_head_bwd_reduce_ordered_impl_f16(z, dy, scale, shift, mean, rstd, w, partials, head_partials, sums, dw, db, pixels,
+                                                   pixels_per_group, Cp, C, stream);
+    return UCLSTM_E_BADARG;
+}
+
+extern "C" int32_t uclstm_ordered_sum_f32(const float* partials, int32_t rows, int32_t cols, float* out, int32_t accumulate, void* stream) {
+    if (!partials || !out || rows <= 0 || cols <= 0) return UCLSTM_E_BADARG;
+    UCLSTM_LAUNCH(ordered_sum_f32_kernel, dim3((cols + 63) / 64), dim3(64), 0, (hipStream_t)stream, partials, rows, cols, out, cols, nullptr,
+                  accumulate);
+    return UCLSTM_OK;
+}
+#endif
 
 extern "C" int32_t uclstm_attention_fwd(const void* x, const float* w, void* out, float* att, float* desc, int32_t* argmax, int32_t n_img,
                                         int32_t H, int32_t W, int32_t Cp, int32_t C, int32_t k, void* stream) {

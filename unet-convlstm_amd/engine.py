@@ -217,7 +217,11 @@ class GraphedTrainStep:
     ``optimizer.sync_hyper()`` before a replay.  fp16 compute (``ops.compute_dtype(torch.float16)`` around construction and
     calls, ``FusedAdamW(loss_scale=..., capturable=True)``): the loss scale, the overflow test, the skipped step and the scale
     update all live on the device, so an overflowed replay leaves parameters and moments alone without the host knowing.
-    Data-parallel training keeps the eager step (its collectives are launched from backward hooks)."""
+    Data-parallel training keeps the eager step (its collectives are launched from backward hooks).
+
+    Deterministic mode (``ops.deterministic()`` / ``ops.set_deterministic``) is part of what is captured: the graph holds the
+    ordered or the atomic reductions according to the switch at construction (``self.deterministic``), and every replay keeps
+    that mode whatever the switch says later."""
 
     def __init__(self, model, optimizer, x, y, mask=None, use_mask: bool = True, clip_norm: Optional[float] = 1.0, warmup: int = 3):
         if not (isinstance(optimizer, FusedAdamW) and optimizer.capturable):
@@ -225,6 +229,7 @@ class GraphedTrainStep:
         if not x.is_cuda:
             raise ops.L.UclstmError("GraphedTrainStep: HIP device tensors required")
         self.model, self.optimizer, self.use_mask, self.clip_norm = model, optimizer, use_mask, clip_norm
+        self.deterministic = ops.is_deterministic()
         self.x, self.y = x.clone(), y.clone()
         self.mask = None if mask is None else mask.clone()
         optimizer.max_grad_norm = clip_norm
@@ -272,6 +277,14 @@ class _Metrics:
             yp = y_pred.contiguous().float()
             yt = y.contiguous().float()
             m = mask.contiguous().float() if (use_mask and mask is not None) else None
+            if ops.is_deterministic():
+                partials = torch.empty((int(L.lib.uclstm_metric_sums_ordered_rows(yp.numel())), 4), dtype=torch.float64, device=yp.device)
+                ops._log_reduce("metric_sums_ordered")
+                L.check(L.lib.uclstm_metric_sums_ordered(ops._p(yp), ops._p(yt), ops._p(m), ops._p(partials), ops._p(self.s), 1, yp.numel(),
+                                                         float(dataset_obj.y_scale), float(dataset_obj.trans_min),
+                                                         float(dataset_obj.trans_max), ops._stream()), "metric_sums_ordered")
+                return
+            ops._log_reduce("metric_sums")
             L.check(L.lib.uclstm_metric_sums(ops._p(yp), ops._p(yt), ops._p(m), ops._p(self.s), yp.numel(),
                                              float(dataset_obj.y_scale), float(dataset_obj.trans_min), float(dataset_obj.trans_max),
                                              ops._stream()), "metric_sums")
@@ -532,7 +545,8 @@ def evaluate_report(model, loader, device, dataset_obj, use_mask=True, **report_
     The first four are computed as ``evaluate`` computes them, from the same launches as the report (``report`` is the dict
     of ``EvalReport.result``).  Against a SEPARATE ``evaluate()`` pass they agree as far as ``evaluate`` agrees with itself:
     its loss and metric kernels add block partials with f64 atomics in arrival order, so two passes can differ in the last
-    bits (~1e-13 relative); the report's own sums do not have that freedom."""
+    bits (~1e-13 relative); the report's own sums do not have that freedom.  (In deterministic mode, ``ops.deterministic()``, those
+    kernels add their block partials in a fixed order and two passes are identical.)"""
     model.eval()
     total = torch.zeros((), dtype=torch.float64, device=device)
     n = 0

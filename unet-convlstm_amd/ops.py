@@ -52,6 +52,39 @@ class compute_dtype:
         set_compute_dtype(self.prev)
 
 
+# Deterministic mode: every reduction of the training step, the evaluation loop and the optimiser that otherwise ends in float
+# atomics (summed in arrival order) takes its ordered form instead -- block partials stored to a scratch buffer, a second launch
+# adds them in a fixed order (include/uclstm.h, the *_ordered entry points).  Off by default; UCLSTM_DETERMINISTIC=1 turns it on
+# at import.  torch.use_deterministic_algorithms() is NOT consulted: that flag also changes torch.empty and ATen behaviour this
+# package does not control, and it does not reach these kernels either way.
+_DETERMINISTIC = os.environ.get("UCLSTM_DETERMINISTIC", "0") == "1"
+
+
+def set_deterministic(on: bool) -> None:
+    global _DETERMINISTIC
+    _DETERMINISTIC = bool(on)
+
+
+def is_deterministic() -> bool:
+    return _DETERMINISTIC
+
+
+class deterministic:
+    """``with ops.deterministic(): train_step(...)`` -- the work enqueued inside runs on the ordered reductions; the previous
+    setting is restored on exit, also when the block raises.  (A captured graph keeps the mode it was captured in.)"""
+
+    def __init__(self, on: bool = True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.prev = _DETERMINISTIC
+        set_deterministic(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.prev)
+
+
 def _k(t: torch.Tensor):
     """Kernel set (bf16 / fp16 twins) for a 16-bit activation tensor."""
     return L.kernels(t.dtype)
@@ -110,6 +143,18 @@ def _log_shape(d) -> None:
             KERNEL_LOG.append((int(d.epi), shp))
         if LAUNCH_LOG is not None:
             LAUNCH_LOG.append(("fwd", int(d.epi), shp, int(d.W), int(d.N)))
+
+
+# The reductions that end in float atomics by default and in an ordered second launch in deterministic mode are recorded in
+# LAUNCH_LOG as ("reduce", kind), so that a test can assert which path a step took.  The weight-gradient unpack is recorded only
+# where its slabs are spread over several slab groups (the only place it is atomic); every other unpack is ordered in both modes.
+ATOMIC_KINDS = ("colsum", "outconv_bwd", "bn_head_bwd_reduce", "unpack_atomic", "loss_fwd", "sumsq", "metric_sums")
+ORDERED_KINDS = tuple((k if k != "unpack_atomic" else "unpack") + "_ordered" for k in ATOMIC_KINDS)
+
+
+def _log_reduce(kind: str) -> None:
+    if LAUNCH_LOG is not None:
+        LAUNCH_LOG.append(("reduce", kind))
 
 
 # Same for the HBM-bound kernels (BatchNorm passes, pooling, LSTM point-wise): (kernel, algorithmic BYTES, start, stop, note).
@@ -557,9 +602,27 @@ def pack_bias(desc: L.PackDesc, b: torch.Tensor) -> torch.Tensor:
 def unpack_wgrad(desc: L.PackDesc, dwp: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
     """dwp: f32 panel gradient [N, Ktot] or its per-pixel-range slabs [splits, N, Ktot] (added up here)."""
     grad = torch.empty_like(like, dtype=F32, memory_format=torch.contiguous_format)
-    ns, st = _slabs_of(dwp)
-    L.check(L.lib.uclstm_unpack_wgrad(C.byref(desc), _p(dwp), ns, st, _p(grad), 0, _stream()), "unpack_wgrad")
+    _unpack_wgrad_launch(desc, dwp, grad, 0)
     return grad
+
+
+def _unpack_wgrad_launch(desc: L.PackDesc, dwp: torch.Tensor, grad: torch.Tensor, accumulate: int) -> None:
+    """grad = (accumulate ? grad : 0) + sum of the slabs of dwp, on the current stream.  Deterministic mode: the ordered form,
+    with a scratch row per slab group where the library splits the slabs (allocated on the current stream, freed to it)."""
+    ns, st = _slabs_of(dwp)
+    if _DETERMINISTIC:
+        groups = int(L.lib.uclstm_unpack_wgrad_ordered_groups(C.byref(desc), ns))
+        if groups < 1:
+            raise L.UclstmError(f"unpack_wgrad_ordered_groups: code {groups}")
+        scratch = torch.empty((groups, desc.N * desc.Ktot), dtype=F32, device=grad.device) if groups > 1 else None
+        if groups > 1:
+            _log_reduce("unpack_ordered")
+        L.check(L.lib.uclstm_unpack_wgrad_ordered(C.byref(desc), _p(dwp), ns, st, _p(scratch), _p(grad), accumulate, _stream()),
+                "unpack_wgrad_ordered")
+        return
+    if LAUNCH_LOG is not None and accumulate and int(L.lib.uclstm_unpack_wgrad_ordered_groups(C.byref(desc), ns)) > 1:
+        _log_reduce("unpack_atomic")
+    L.check(L.lib.uclstm_unpack_wgrad(C.byref(desc), _p(dwp), ns, st, _p(grad), accumulate, _stream()), "unpack_wgrad")
 
 
 def _slabs_of(dwp: torch.Tensor) -> Tuple[int, int]:
@@ -685,8 +748,7 @@ def wgrad_into_param(weight: torch.Tensor, desc: L.PackDesc, inputs: Sequence[to
             dwp = run_gemm()
         finally:
             _WGRAD_OVERLAPPED = False
-        ns, st = _slabs_of(dwp)
-        L.check(L.lib.uclstm_unpack_wgrad(C.byref(desc), _p(dwp), ns, st, _p(g), 1, _stream()), "unpack_wgrad(accumulate)")
+        _unpack_wgrad_launch(desc, dwp, g, 1)           # (scratch of the ordered form: allocated and freed under the side stream)
         for t in inputs:
             if t is not None:
                 t.record_stream(side)           # the caching allocator must not recycle them under the side stream
@@ -1005,7 +1067,16 @@ def colsum(a: torch.Tensor, into: Optional[torch.Tensor] = None) -> torch.Tensor
     gradient: saves the zero-fill, the slice copy and autograd's accumulate kernel); else a fresh zeroed vector."""
     _dev(a, ACT, "colsum input")
     Cp = a.shape[-1]
+    if _DETERMINISTIC:
+        pixels = a.numel() // Cp
+        out = into if into is not None else torch.empty((Cp,), dtype=F32, device=a.device)
+        partials = torch.empty((int(L.lib.uclstm_colsum_ordered_rows(pixels, Cp)), Cp), dtype=F32, device=a.device)
+        _log_reduce("colsum_ordered")
+        L.check(L.lib.uclstm_colsum_ordered(_p(a), _p(partials), _p(out), pixels, Cp, 1 if into is not None else 0, L.act_type(a.dtype),
+                                            _stream()), "colsum_ordered")
+        return out
     out = into if into is not None else torch.zeros((Cp,), dtype=F32, device=a.device)
+    _log_reduce("colsum")
     L.check(_k(a).uclstm_colsum(_p(a), _p(out), a.numel() // Cp, Cp, _stream()), "colsum")
     return out
 
@@ -1307,10 +1378,20 @@ class ConvBNReLU(_GradAwareFunction):
             direct = gw is not None and gw.is_contiguous() and (head_b is None or gb is not None)
             dwh = gw if direct else torch.zeros_like(head_w, memory_format=torch.contiguous_format)
             dbh = gb if (direct and head_b is not None) else torch.zeros((1,), dtype=F32, device=dev)
-            _timed_hbm("bn_head_bwd_reduce", 2.0 * z.numel() + 4.0 * pixels,
-                       lambda: L.check(K.uclstm_bn_head_bwd_reduce(_p(z), _p(dy), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(head_w),
-                                                                   _p(partials), _p(sums), _p(dwh), _p(dbh), pixels, ppg, Cop, Co, _stream()),
-                                       "bn_head_bwd_reduce"))
+            if _DETERMINISTIC:
+                # the head's Co + 1 columns go through partial rows of their own and are finished in row order (dwh / dbh keep +=)
+                head_partials = torch.empty((partials.shape[0], Co + 1), dtype=F32, device=dev)
+                _log_reduce("bn_head_bwd_reduce_ordered")
+                _timed_hbm("bn_head_bwd_reduce", 2.0 * z.numel() + 4.0 * pixels,
+                           lambda: L.check(L.lib.uclstm_bn_head_bwd_reduce_ordered(
+                               _p(z), _p(dy), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(head_w), _p(partials), _p(head_partials),
+                               _p(sums), _p(dwh), _p(dbh), pixels, ppg, Cop, Co, L.act_type(z.dtype), _stream()), "bn_head_bwd_reduce_ordered"))
+            else:
+                _log_reduce("bn_head_bwd_reduce")
+                _timed_hbm("bn_head_bwd_reduce", 2.0 * z.numel() + 4.0 * pixels,
+                           lambda: L.check(K.uclstm_bn_head_bwd_reduce(_p(z), _p(dy), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(head_w),
+                                                                       _p(partials), _p(sums), _p(dwh), _p(dbh), pixels, ppg, Cop, Co, _stream()),
+                                           "bn_head_bwd_reduce"))
             _timed_hbm("bn_head_bwd_apply", 4.0 * z.numel() + 4.0 * pixels,
                        lambda: L.check(K.uclstm_bn_head_bwd_apply(_p(z), _p(dy), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(sums),
                                                                   _p(head_w), _p(dz), pixels, ppg, Cop, Co, _stream()), "bn_head_bwd_apply"))
@@ -1568,10 +1649,19 @@ class OutConv1x1(_GradAwareFunction):
         gw = direct_grad(weight)
         gb = direct_grad(bias) if ctx.has_bias else None
         direct = need_w and gw is not None and (gb is not None or not ctx.has_bias) and gw.is_contiguous() and (need_b or not ctx.has_bias)
-        dw = gw if direct else torch.zeros((Co, Ci), dtype=F32, device=a.device)
-        db = gb if (direct and ctx.has_bias) else torch.zeros((Co,), dtype=F32, device=a.device)
-        L.check(_k(a).uclstm_outconv_bwd(_p(a), _p(weight), _p(dy), _p(da), _p(dw), _p(db), N, H * W, Cp, Ci, Co, _stream()),
-                "outconv_bwd")
+        if _DETERMINISTIC:
+            dw = gw if direct else torch.empty((Co, Ci), dtype=F32, device=a.device)
+            db = gb if (direct and ctx.has_bias) else (torch.empty((Co,), dtype=F32, device=a.device) if need_b else None)
+            partials = torch.empty((int(L.lib.uclstm_outconv_bwd_ordered_rows(N, H * W)), Co * Ci + Co), dtype=F32, device=a.device)
+            _log_reduce("outconv_bwd_ordered")
+            L.check(L.lib.uclstm_outconv_bwd_ordered(_p(a), _p(weight), _p(dy), _p(da), _p(partials), _p(dw), _p(db), 1 if direct else 0,
+                                                     N, H * W, Cp, Ci, Co, L.act_type(a.dtype), _stream()), "outconv_bwd_ordered")
+        else:
+            dw = gw if direct else torch.zeros((Co, Ci), dtype=F32, device=a.device)
+            db = gb if (direct and ctx.has_bias) else torch.zeros((Co,), dtype=F32, device=a.device)
+            _log_reduce("outconv_bwd")
+            L.check(_k(a).uclstm_outconv_bwd(_p(a), _p(weight), _p(dy), _p(da), _p(dw), _p(db), N, H * W, Cp, Ci, Co, _stream()),
+                    "outconv_bwd")
         if direct:
             grad_written(weight)
             if ctx.has_bias:
@@ -2022,8 +2112,16 @@ class LossFn(torch.autograd.Function):
         H, W = y_pred.shape[-2], y_pred.shape[-1]
         planes = y_pred.numel() // (H * W)
         m = _dev(mask.contiguous().float(), F32, "mask") if (use_mask and mask is not None) else None
-        sums = torch.zeros((4,), dtype=torch.float64, device=y_pred.device)
-        L.check(L.lib.uclstm_loss_fwd(_p(y_pred), _p(y), _p(m), _p(sums), planes, H, W, _stream()), "loss_fwd")
+        if _DETERMINISTIC:
+            sums = torch.empty((4,), dtype=torch.float64, device=y_pred.device)
+            partials = torch.empty((int(L.lib.uclstm_loss_fwd_ordered_rows(planes, H, W)), 4), dtype=torch.float64, device=y_pred.device)
+            _log_reduce("loss_fwd_ordered")
+            L.check(L.lib.uclstm_loss_fwd_ordered(_p(y_pred), _p(y), _p(m), _p(partials), _p(sums), 0, planes, H, W, _stream()),
+                    "loss_fwd_ordered")
+        else:
+            sums = torch.zeros((4,), dtype=torch.float64, device=y_pred.device)
+            _log_reduce("loss_fwd")
+            L.check(L.lib.uclstm_loss_fwd(_p(y_pred), _p(y), _p(m), _p(sums), planes, H, W, _stream()), "loss_fwd")
         n1 = float(y_pred.numel())
         n2 = float(planes * (H - 1) * (W - 1))
         if m is not None:

@@ -251,6 +251,22 @@ class FusedAdamW(torch.optim.Optimizer):
         """The tensor to call ``backward()`` on: ``loss`` itself, or ``loss * scale`` with fp16 loss scaling."""
         return loss if self.scale_state is None else loss * self.scale_state[0]
 
+    def _global_sumsq(self) -> None:
+        """self.sumsq = sum of squares of the flat gradient buffer (the global norm the clip coefficient comes from).  In
+        deterministic mode the block totals go through a partial buffer and are added in a fixed order; nothing is zeroed."""
+        from . import _lib as L
+        from . import ops
+        f = self.flat
+        if ops.is_deterministic():
+            partials = torch.empty(int(L.lib.uclstm_sumsq_ordered_rows(f.numel)), dtype=torch.float64, device=f.flat_g.device)
+            ops._log_reduce("sumsq_ordered")
+            L.check(L.lib.uclstm_sumsq_ordered(C.c_void_p(f.flat_g.data_ptr()), f.numel, C.c_void_p(partials.data_ptr()),
+                                               C.c_void_p(self.sumsq.data_ptr()), 0, ops._stream()), "sumsq_ordered")
+            return
+        self.sumsq.zero_()
+        ops._log_reduce("sumsq")
+        L.check(L.lib.uclstm_sumsq(C.c_void_p(f.flat_g.data_ptr()), f.numel, C.c_void_p(self.sumsq.data_ptr()), ops._stream()), "sumsq")
+
     @torch.no_grad()
     def step(self, closure=None):
         from . import _lib as L
@@ -263,8 +279,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.uses_groups:
             if not torch.cuda.is_current_stream_capturing():
                 self.sync_hyper()
-            self.sumsq.zero_()
-            L.check(L.lib.uclstm_sumsq(C.c_void_p(f.flat_g.data_ptr()), f.numel, C.c_void_p(self.sumsq.data_ptr()), _stream()), "sumsq")
+            self._global_sumsq()
             state = None
             if self.scale_state is not None:
                 self._last_scale.copy_(self.scale_state[0])      # a buffer of its own: the scale update below overwrites the state
@@ -281,9 +296,8 @@ class FusedAdamW(torch.optim.Optimizer):
             ops.weights_changed()
             return None
         if self.scale_state is not None:
-            self.sumsq.zero_()
             self._last_scale = self.scale_state[0].clone()
-            L.check(L.lib.uclstm_sumsq(C.c_void_p(f.flat_g.data_ptr()), f.numel, C.c_void_p(self.sumsq.data_ptr()), _stream()), "sumsq")
+            self._global_sumsq()
             L.check(L.lib.uclstm_adamw_step_scaled(C.c_void_p(f.flat_p.data_ptr()), C.c_void_p(self.m.data_ptr()), C.c_void_p(self.v.data_ptr()),
                                                    C.c_void_p(f.flat_g.data_ptr()), f.numel, C.c_void_p(self.sumsq.data_ptr()),
                                                    float(self.max_grad_norm or 0.0), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
@@ -298,8 +312,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.capturable:
             if not torch.cuda.is_current_stream_capturing():
                 self.sync_hyper()
-            self.sumsq.zero_()
-            L.check(L.lib.uclstm_sumsq(C.c_void_p(f.flat_g.data_ptr()), f.numel, C.c_void_p(self.sumsq.data_ptr()), _stream()), "sumsq")
+            self._global_sumsq()
             L.check(L.lib.uclstm_adamw_step_dev(C.c_void_p(f.flat_p.data_ptr()), C.c_void_p(self.m.data_ptr()), C.c_void_p(self.v.data_ptr()),
                                                 C.c_void_p(f.flat_g.data_ptr()), f.numel, C.c_void_p(self.sumsq.data_ptr()),
                                                 C.c_void_p(self.hyper.data_ptr()), _stream()), "adamw_step_dev")
@@ -308,8 +321,7 @@ class FusedAdamW(torch.optim.Optimizer):
             return None
         sq = None
         if self.max_grad_norm is not None:
-            self.sumsq.zero_()
-            L.check(L.lib.uclstm_sumsq(C.c_void_p(f.flat_g.data_ptr()), f.numel, C.c_void_p(self.sumsq.data_ptr()), _stream()), "sumsq")
+            self._global_sumsq()
             sq = C.c_void_p(self.sumsq.data_ptr())
         L.check(L.lib.uclstm_adamw_step(C.c_void_p(f.flat_p.data_ptr()), C.c_void_p(self.m.data_ptr()), C.c_void_p(self.v.data_ptr()),
                                         C.c_void_p(f.flat_g.data_ptr()), f.numel, sq,
