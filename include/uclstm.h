@@ -517,6 +517,17 @@ int32_t uclstm_loss_scale_update(float* scale_state, const double* sumsq, float 
 int32_t uclstm_dataset_transform(const float* x_raw, const float* y_raw, float* x, float* y, float* mask, int64_t n_frames,
                                  int32_t C, int32_t HW, float norm_const, float min_vel, float max_vel, int32_t clip,
                                  float y_scale, float trans_min, float trans_max, void* stream);
+/* NPZSequenceDataset.__getitem__ (train/unet.py:273-304) for the sequences idx[0..n_out) of a RAW dataset resident on the device:
+ * x_all f32 [n_seq][T][C][HW], y_all f32 [n_seq][T][1][HW]  ->  x [n_out][T][C][HW], y, mask [n_out][T][1][HW] (f32).
+ * idx: device int64 [n_out], NULL = identity (then n_out <= n_seq); an index outside [0, n_seq) is clamped into it by the
+ * kernel (the caller validates; the clamp only keeps a bad index from becoming a wild read).
+ * transform: 0 none, 1 asinh(v / y_scale), 2 signed_log = sign(v) * log1p(|v| / y_scale); otherwise the arithmetic of
+ * uclstm_dataset_transform.  16-byte loads / stores when HW % 4 == 0 and all five data pointers are 16-byte aligned, a scalar
+ * path otherwise.  f32 only (no _f16 twin).  Requires n_out * T * HW < 2^31, y_scale > 0 for transforms 1 / 2. */
+int32_t uclstm_dataset_gather_transform(const float* x_all, const float* y_all, const int64_t* idx, int64_t n_seq, int64_t n_out,
+                                        int32_t T, int32_t C, int32_t HW, float* x, float* y, float* mask, int32_t transform,
+                                        float norm_const, float min_vel, float max_vel, int32_t clip, float y_scale,
+                                        float trans_min, float trans_max, void* stream);
 /* Epoch metric block of main.py:114-142 as running sums: sums[0..3] += sum|d|m, sum d^2 m, sum d m, sum m with
  * d = denormalize(y_pred) - denormalize(y) (train/unet.py:316-319, asinh transform); mask may be NULL. */
 int32_t uclstm_metric_sums(const float* y_pred, const float* y, const float* mask, double* sums, int64_t n, float y_scale,

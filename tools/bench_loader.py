@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""A/B of the two ways an epoch gets its batches, on a synthetic ``.npz`` in the reference's format (N sequences of
+T frames of 2 x H x W, written to a temporary directory):
+
+    host    torch.utils.data.DataLoader(dataset, batch_size, shuffle=True, pin_memory=True)      (main.py:245, num_workers=0)
+    device  DeviceSequenceLoader(dataset, batch_size, shuffle=True)                              (raw data resident on the GPU)
+
+Both arms run ``train_one_epoch`` over the SAME model and FusedAdamW (the arms alternate epoch by epoch inside one process, so
+clock, allocator and cache state are shared); an epoch is timed with a host clock around it -- ``train_one_epoch`` ends in a
+device-to-host read of the epoch's sums, so the clock covers the device work.  Two warm-up epochs per arm, then ``--epochs``
+timed ones per arm.  Also timed: the gather kernel alone (cold caches: a 1 GiB fill before every launch, HIP events) against
+its algorithmic bytes ((C + 1) * 4 read + (C + 2) * 4 written per pixel), the one-off upload of the raw arrays, and the
+training step alone on one resident batch (what ``bench.py`` times: the floor for both arms).
+
+    python tools/bench_loader.py [--epochs 3] [--out profiles/device_loader_ab.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import unet_convlstm_amd as U   # noqa: E402
+from unet_convlstm_amd import engine as E   # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--epochs", type=int, default=3, help="timed epochs per arm (>= 3)")
+ap.add_argument("--n", type=int, default=256, help="sequences in the synthetic dataset")
+ap.add_argument("--batch", type=int, default=32)
+ap.add_argument("--base-ch", type=int, default=64)
+ap.add_argument("--shapes", default="20x64,12x128", help="comma-separated TxS: T frames of 2 x S x S")
+ap.add_argument("--kernel-rounds", type=int, default=9)
+ap.add_argument("--out", default=None, help="also append the table to this file")
+a = ap.parse_args()
+if a.epochs < 3:
+    ap.error("--epochs must be at least 3")
+if not torch.cuda.is_available():
+    sys.exit("bench_loader: needs a GPU (no CPU fallback: a timing taken elsewhere says nothing)")
+dev = torch.device("cuda", 0)
+lines = []
+
+
+def say(msg=""):
+    print(msg, flush=True)
+    lines.append(msg)
+
+
+def write_npz(path, n, T, S, seed=0):
+    rng = np.random.default_rng(seed)
+    X = (rng.random((n, T, 2, S, S), dtype=np.float32) * 30).astype(np.float32)
+    X[X < 6] = 0.0
+    Y = (np.tanh(X[:, :, :1] / 15.0 - 1.0) * 4.0 + rng.standard_normal((n, T, 1, S, S), dtype=np.float32) * 0.5).astype(np.float32)
+    np.savez(path, X=X, Y=Y)
+
+
+def epoch_seconds(model, loader, opt, ds):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = U.train_one_epoch(model, loader, opt, dev, ds, use_mask=True)
+    torch.cuda.synchronize()
+    assert all(np.isfinite(v) for v in out), out
+    return time.perf_counter() - t0
+
+
+def kernel_alone(ds, loader, T, S):
+    flush = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+    idx = torch.randperm(len(ds), generator=torch.Generator().manual_seed(1))[:a.batch].to(dev)
+    out = tuple(torch.empty((a.batch, T, c, S, S), device=dev) for c in (2, 1, 1))
+    st = torch.cuda.current_stream()
+    ts = []
+    for r in range(a.kernel_rounds + 1):
+        flush.fill_(1.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        E._gather_transform(ds, loader.x_all, loader.y_all, idx, a.batch, out)
+        e1.record(st)
+        torch.cuda.synchronize()
+        if r:                                   # round 0 warms up (code-object load)
+            ts.append(e0.elapsed_time(e1) * 1e3)
+    nbytes = a.batch * T * S * S * (3 * 4 + 4 * 4)
+    med = statistics.median(ts)
+    say(f"  gather kernel alone, cold caches, batch {a.batch}: median {med:.1f} us (min {min(ts):.1f}, max {max(ts):.1f}, "
+        f"{a.kernel_rounds} rounds); {nbytes / 1e6:.1f} MB algorithmic (28 B/pixel) -> {nbytes / med / 1e3:.0f} GB/s")
+    del flush
+
+
+def step_alone(model, opt, loader):
+    x, y, m = next(iter(loader))
+    for _ in range(3):
+        U.train_step(model, opt, x, y, m, True)
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        for _ in range(8):
+            U.train_step(model, opt, x, y, m, True)
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) / 8 * 1e3)
+    say(f"  training step alone on one resident batch (the bench.py measurement, 8 steps x 3): median {statistics.median(ts):.2f} ms "
+        f"(min {min(ts):.2f}, max {max(ts):.2f})")
+
+
+def one_shape(T, S, tmp):
+    path = os.path.join(tmp, f"bench_{T}x{S}.npz")
+    write_npz(path, a.n, T, S)
+    ds = U.NPZSequenceDataset(path)
+    say(f"shape: N = {a.n}, T = {T}, 2 x {S} x {S}, batch {a.batch} ({a.n // a.batch} steps per epoch), base_ch {a.base_ch}, bf16; "
+        f"raw arrays {(ds.X.nbytes + ds.Y.nbytes) / 1e6:.0f} MB")
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    device_loader = U.DeviceSequenceLoader(ds, a.batch, shuffle=True, generator=torch.Generator().manual_seed(7), drop_last=True)
+    torch.cuda.synchronize()
+    up = time.perf_counter() - t0
+    say(f"  one-off upload of the raw arrays (pageable host memory): {up * 1e3:.1f} ms "
+        f"({(ds.X.nbytes + ds.Y.nbytes) / up / 1e9:.1f} GB/s)")
+    host_loader = torch.utils.data.DataLoader(ds, batch_size=a.batch, shuffle=True, pin_memory=True, drop_last=True,
+                                              generator=torch.Generator().manual_seed(7))
+    torch.manual_seed(0)
+    model = U.TemporalUNetDualView(1, 1, base_ch=a.base_ch, lstm_layers=1, use_skip_lstm=True, use_attention=False).to(dev)
+    opt = U.FusedAdamW(model.parameters(), lr=1e-3, weight_decay=1e-4, max_grad_norm=1.0)
+    arms = {"host DataLoader": host_loader, "DeviceSequenceLoader": device_loader}
+    times = {k: [] for k in arms}
+    for r in range(2 + a.epochs):
+        for name, loader in arms.items():
+            t = epoch_seconds(model, loader, opt, ds)
+            if r >= 2:
+                times[name].append(t)
+    steps = a.n // a.batch
+    say(f"  {'arm':22s} {'ms/step':>9s} {'min':>8s} {'max':>8s} {'frames/s':>10s}   ({a.epochs} timed epochs per arm, alternating, after 2 warm-up epochs each)")
+    for name, ts in times.items():
+        per = [t / steps * 1e3 for t in ts]
+        med = statistics.median(per)
+        say(f"  {name:22s} {med:9.2f} {min(per):8.2f} {max(per):8.2f} {a.batch * T / med * 1e3:10.0f}")
+    h, d = (statistics.median(times[k]) for k in arms)
+    spread = max(max(v) - min(v) for v in times.values()) / steps * 1e3
+    say(f"  device arm / host arm = {d / h:.3f} (median epoch time); largest min - max spread of an arm {spread:.2f} ms/step")
+    step_alone(model, opt, device_loader)
+    kernel_alone(ds, device_loader, T, S)
+    say()
+
+
+with tempfile.TemporaryDirectory() as tmp:
+    say(f"tools/bench_loader.py on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
+    torch.zeros(1 << 20, device=dev).sum().item()          # the HIP context and the allocator exist before the first timed upload
+    for shape in a.shapes.split(","):
+        T, S = (int(v) for v in shape.split("x"))
+        one_shape(T, S, tmp)
+        torch.cuda.empty_cache()
+if a.out:
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:
+        f.write("\n".join(lines) + "\n")

@@ -25,13 +25,15 @@ def main() -> int:
     os.makedirs(OUT, exist_ok=True)
     hipcc = B._hipcc()
 
-    def one(src):
-        obj = os.path.join(OUT, src.replace(".hip", ".o"))
-        subprocess.run([hipcc, *B.FLAGS, *SAN, "-c", os.path.join(B.CSRC, src), "-o", obj], check=True)
+    def one(job):
+        src, f16 = job
+        obj = os.path.join(OUT, src.replace(".hip", "_f16.o" if f16 else ".o"))
+        subprocess.run([hipcc, *B.FLAGS, *(B.F16_FLAGS if f16 else []), *SAN, "-c", os.path.join(B.CSRC, src), "-o", obj], check=True)
         return obj
 
+    # both passes, as build.py: the bfloat16 objects call the *_impl_f16 bodies of the binary16 pass
     with ThreadPoolExecutor(max_workers=5) as ex:
-        objs = list(ex.map(one, B.SOURCES))
+        objs = list(ex.map(one, [(s, False) for s in B.SOURCES] + [(s, True) for s in B.F16_SOURCES]))
     lib = os.path.join(OUT, "libuclstm_asan.so")
     subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address", "-fsanitize=undefined", "-o", lib, *objs], check=True)
     exe = os.path.join(OUT, "driver")

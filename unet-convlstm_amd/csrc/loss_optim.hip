@@ -374,6 +374,102 @@ __global__ void dataset_transform_kernel(const float* __restrict__ xr, const flo
     }
 }
 
+// V consecutive floats as one access: V = 4 is a 16-byte load / store, V = 1 the scalar path
+template <int V>
+__device__ __forceinline__ void load_px(const float* __restrict__ p, float (&r)[V]) {
+    if constexpr (V == 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = v[k];
+    } else {
+        r[0] = *p;
+    }
+}
+template <int V>
+__device__ __forceinline__ void store_px(float* __restrict__ p, const float (&r)[V]) {
+    if constexpr (V == 4) {
+        f32x4 v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = r[k];
+        *reinterpret_cast<f32x4*>(p) = v;
+    } else {
+        *p = r[0];
+    }
+}
+
+// the three forward target transforms of train/unet.py:243-248 (0 none, 1 asinh, 2 signed_log = np.sign(v) * np.log1p(|v| / s))
+__device__ __forceinline__ float target_fwd(float v, int transform, float inv_yscale) {
+    if (transform == 1) return asinhf(v * inv_yscale);
+    if (transform == 2) return copysignf(log1pf(fabsf(v) * inv_yscale), v);
+    return v;
+}
+
+// NPZSequenceDataset.__getitem__ for the sequences idx[0 .. n_out) of a RAW dataset resident on the device: the arithmetic of
+// dataset_transform_kernel (plus the two other target transforms), the source frame found through the index vector.
+// A block iteration is one CHUNK = NT work items (V pixels each) of ONE output frame, so the sequence index is uniform: it is
+// read once per chunk (a scalar load), clamped into [0, n_seq) -- never a wild read -- and every lane's loads go to a clamped
+// address unconditionally ("Branch-free loads"); lanes past the end of the frame only skip their stores.
+// CT: the channel count when it is known at compile time (2: all C + 1 loads are issued before the first store), 0 = runtime C.
+template <int V, int CT>
+__global__ __launch_bounds__(NT) void dataset_gather_transform_kernel(
+        const float* __restrict__ xa, const float* __restrict__ ya, const int64_t* __restrict__ idx, int64_t n_seq, int n_chunks,
+        FastDiv dCpf, FastDiv dT, int Crt, int HW, float* __restrict__ x, float* __restrict__ y, float* __restrict__ mask, int transform,
+        float inv_norm, float min_vel, float max_vel, int clip, float inv_yscale, float tmin, float inv_trange) {
+    const int C = CT > 0 ? CT : Crt;
+    const int per = HW / V;                                         // work items per frame
+    const int cpf = (int)dCpf.d, T = (int)dT.d;
+    for (int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t f = fdiv((uint32_t)chunk, dCpf);             // output frame = o * T + t
+        const uint32_t o = fdiv(f, dT);                             // output sequence
+        int64_t row = idx ? idx[o] : (int64_t)o;
+        row = row < 0 ? 0 : (row >= n_seq ? n_seq - 1 : row);
+        const int64_t sf = row * T + (int64_t)(f - o * (uint32_t)T);   // source frame
+        const int q = (chunk - (int)f * cpf) * NT + (int)threadIdx.x;
+        const bool live = q < per;
+        const int px = (live ? q : per - 1) * V;
+        const float* xs = xa + sf * C * HW + px;
+        float* xd = x + (int64_t)f * C * HW + px;
+        const int64_t od = (int64_t)f * HW + px;
+        float v[V], c0[V], m[V];
+        load_px<V>(ya + sf * HW + px, v);
+        load_px<V>(xs, c0);
+        if constexpr (CT > 0) {
+            float cc[CT > 1 ? CT - 1 : 1][V];
+#pragma unroll
+            for (int c = 1; c < CT; ++c) load_px<V>(xs + (int64_t)c * HW, cc[c - 1]);
+            if (live) {
+#pragma unroll
+                for (int c = 1; c < CT; ++c) {
+#pragma unroll
+                    for (int k = 0; k < V; ++k) cc[c - 1][k] *= inv_norm;
+                    store_px<V>(xd + (int64_t)c * HW, cc[c - 1]);
+                }
+            }
+        } else {
+            for (int c = 1; c < C; ++c) {
+                float r[V];
+                load_px<V>(xs + (int64_t)c * HW, r);
+#pragma unroll
+                for (int k = 0; k < V; ++k) r[k] *= inv_norm;
+                if (live) store_px<V>(xd + (int64_t)c * HW, r);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            m[k] = c0[k] > 1.1f ? 1.f : 0.f;
+            c0[k] *= inv_norm;
+            float w = v[k];
+            if (clip) w = fminf(fmaxf(w, min_vel), max_vel);
+            v[k] = 2.f * (target_fwd(w, transform, inv_yscale) - tmin) * inv_trange - 1.f;
+        }
+        if (live) {
+            store_px<V>(xd, c0);
+            store_px<V>(mask + od, m);
+            store_px<V>(y + od, v);
+        }
+    }
+}
+
 // Epoch metrics of main.py:114-142 as running sums: de-normalise (train/unet.py:316-319) prediction and target,
 // d = pred - target, sums += (sum |d| m, sum d^2 m, sum d m, sum m).  ORDERED: sums is the partial buffer [gridDim.x][4], no atomics
 template <bool ORDERED>
@@ -514,6 +610,36 @@ extern "C" int32_t uclstm_dataset_transform(const float* x_raw, const float* y_r
     UCLSTM_LAUNCH(dataset_transform_kernel, dim3(grid_for(total, 2048)), dim3(NT), 0, (hipStream_t)stream, x_raw, y_raw, x, y, mask, total,
                   make_fastdiv(HW), C, 1.0f / norm_const, min_vel, max_vel, clip, 1.0f / y_scale, trans_min,
                   1.0f / (trans_max - trans_min));
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_dataset_gather_transform(const float* x_all, const float* y_all, const int64_t* idx, int64_t n_seq, int64_t n_out,
+                                                   int32_t T, int32_t C, int32_t HW, float* x, float* y, float* mask, int32_t transform,
+                                                   float norm_const, float min_vel, float max_vel, int32_t clip, float y_scale,
+                                                   float trans_min, float trans_max, void* stream) {
+    if (!x_all || !y_all || !x || !y || !mask || n_seq <= 0 || n_out <= 0 || T <= 0 || C <= 0 || HW <= 0 || transform < 0 ||
+        transform > 2 || norm_const == 0.f || trans_max == trans_min || (transform != 0 && !(y_scale > 0.f)) || (!idx && n_out > n_seq))
+        return UCLSTM_E_BADARG;
+    const int64_t frame_px = (int64_t)T * HW;                                  // < 2^62
+    if (n_out > (((int64_t)1 << 31) - 1) / frame_px) return UCLSTM_E_BADARG;    // n_out * T * HW >= 2^31
+    const bool vec = HW % 4 == 0 && (((uintptr_t)x_all | (uintptr_t)y_all | (uintptr_t)x | (uintptr_t)y | (uintptr_t)mask) % 16) == 0;
+    const int per = vec ? HW / 4 : HW;                                         // work items per frame
+    const int cpf = (per + NT - 1) / NT;                                       // chunks per frame
+    const int64_t n_chunks = n_out * T * cpf;                                  // <= n_out * T * HW < 2^31
+    const int grid = (int)(n_chunks < 2048 ? n_chunks : 2048);
+    const float inv_yscale = transform != 0 ? 1.0f / y_scale : 1.0f;
+#define UCLSTM_GATHER_LAUNCH(V, CT)                                                                                                      \
+    UCLSTM_LAUNCH((dataset_gather_transform_kernel<V, CT>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, x_all, y_all, idx, n_seq,     \
+                  (int)n_chunks, make_fastdiv(cpf), make_fastdiv(T), C, HW, x, y, mask, transform, 1.0f / norm_const, min_vel, max_vel, \
+                  clip, inv_yscale, trans_min, 1.0f / (trans_max - trans_min))
+    if (vec) {
+        if (C == 2) UCLSTM_GATHER_LAUNCH(4, 2);
+        else UCLSTM_GATHER_LAUNCH(4, 0);
+    } else {
+        if (C == 2) UCLSTM_GATHER_LAUNCH(1, 2);
+        else UCLSTM_GATHER_LAUNCH(1, 0);
+    }
+#undef UCLSTM_GATHER_LAUNCH
     return UCLSTM_OK;
 }
 

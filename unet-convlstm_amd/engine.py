@@ -148,12 +148,14 @@ class NPZSequenceDataset(torch.utils.data.Dataset):
 def device_transform(ds, x_raw: torch.Tensor, y_raw: torch.Tensor):
     """``NPZSequenceDataset.__getitem__`` (train/unet.py:273-304) for a whole RAW batch already on the device:
     ``x_raw [B,T,C,H,W]``, ``y_raw [B,T,1,H,W]`` f32 -> ``(x, y, mask)`` exactly as the host dataset would yield them
-    (asinh transform only).  One kernel; lets the loader ship raw ``.npz`` slabs and skip the per-item numpy work."""
+    (every target transform of the dataset: ``asinh`` through ``uclstm_dataset_transform``, ``signed_log`` and none through
+    ``uclstm_dataset_gather_transform`` in identity order).  One kernel; lets a loader ship raw ``.npz`` slabs and skip the
+    per-item numpy work -- ``DeviceSequenceLoader`` below keeps the whole raw dataset on the device instead."""
     from . import _lib as L
-    if ds.y_transform != "asinh":
-        raise ValueError("device_transform implements the 'asinh' target transform (the reference default)")
     x_raw = ops._dev(x_raw.contiguous(), torch.float32, "x_raw")
     y_raw = ops._dev(y_raw.contiguous(), torch.float32, "y_raw")
+    if ds.y_transform != "asinh":          # 'signed_log' / None: the gather kernel over the batch itself, identity order
+        return _gather_transform(ds, x_raw, y_raw, None, x_raw.shape[0])
     B, T, Cc, H, W = x_raw.shape
     x, y = torch.empty_like(x_raw), torch.empty_like(y_raw)
     mask = torch.empty_like(y_raw)
@@ -162,6 +164,146 @@ def device_transform(ds, x_raw: torch.Tensor, y_raw: torch.Tensor):
                                            float(ds.y_scale), float(ds.trans_min), float(ds.trans_max), ops._stream()),
             "dataset_transform")
     return x, y, mask
+
+
+def _gather_transform(ds, x_all, y_all, idx, n_out, out=None):
+    """One launch of ``uclstm_dataset_gather_transform``: the sequences ``idx[0..n_out)`` (device int64; None = the first
+    ``n_out`` in order) of the RAW device arrays ``x_all [N,T,C,H,W]`` / ``y_all [N,T,1,H,W]`` as ``ds.__getitem__`` would yield
+    them.  ``out``: caller-owned ``(x, y, mask)`` to write into; fresh tensors on the current stream otherwise."""
+    from . import _lib as L
+    N, T, Cc, H, W = x_all.shape
+    if out is None:
+        x = torch.empty((n_out, T, Cc, H, W), dtype=torch.float32, device=x_all.device)
+        y = torch.empty((n_out, T, 1, H, W), dtype=torch.float32, device=x_all.device)
+        mask = torch.empty_like(y)
+    else:
+        x, y, mask = out
+    L.check(L.lib.uclstm_dataset_gather_transform(
+        ops._p(x_all), ops._p(y_all), ops._p(idx), N, n_out, T, Cc, H * W, ops._p(x), ops._p(y), ops._p(mask),
+        _TRANSFORM_IDS[ds.y_transform], float(ds.norm_const), float(ds.min_vel), float(ds.max_vel), int(bool(ds.clip_outliers)),
+        float(ds.y_scale), float(ds.trans_min), float(ds.trans_max), ops._stream()), "dataset_gather_transform")
+    return x, y, mask
+
+
+def _root_rows(dataset):
+    """``dataset`` (an ``NPZSequenceDataset`` or nested ``Subset``s of one, as ``random_split`` returns them) ->
+    ``(root dataset, rows)``: ``rows[p]`` is the root's row behind position ``p`` (int64 array; None = identity)."""
+    rows, d = None, dataset
+    while isinstance(d, torch.utils.data.Subset):
+        ind = _checked(np.asarray(d.indices, dtype=np.int64).reshape(-1), len(d.dataset), "Subset index")
+        rows = ind if rows is None else ind[rows]
+        d = d.dataset
+    if not isinstance(d, NPZSequenceDataset):
+        raise TypeError(f"DeviceSequenceLoader needs an NPZSequenceDataset or a Subset of one, got {type(d).__name__}")
+    return d, rows
+
+
+def _checked(ind: np.ndarray, n: int, what: str) -> np.ndarray:
+    bad = (ind < 0) | (ind >= n)
+    if bad.any():
+        raise IndexError(f"{what} {int(ind[bad][0])} is outside [0, {n})")
+    return ind
+
+
+def epoch_rows(dataset, sampler, batch_size: int, drop_last: bool = False):
+    """The batches of one epoch as rows of the ROOT dataset: a pure function of its arguments (plus the sampler's own random
+    state).  ``sampler`` yields positions into ``dataset`` (any torch sampler or iterable; None = in order); they are chunked as
+    ``torch.utils.data.BatchSampler`` chunks them and mapped through the Subset indices.  Returns a list of int64 arrays.
+    A position or row out of range raises ``IndexError``."""
+    if batch_size <= 0:
+        raise ValueError(f"batch_size must be positive, got {batch_size}")
+    root, rows = _root_rows(dataset)
+    pos = np.arange(len(dataset), dtype=np.int64) if sampler is None else np.fromiter((int(p) for p in sampler), dtype=np.int64)
+    pos = _checked(pos, len(dataset), "sampler position")
+    flat = _checked(pos if rows is None else rows[pos], len(root), "dataset row")
+    stop = len(flat) // batch_size * batch_size if drop_last else len(flat)
+    return [flat[s:min(s + batch_size, stop)] for s in range(0, stop, batch_size)]
+
+
+class DeviceSequenceLoader:
+    """``DataLoader(dataset, batch_size, ...)`` for a dataset whose RAW arrays live on the GPU: a batch is one launch of
+    ``uclstm_dataset_gather_transform`` (gather by row, mask, normalise, clip, target transform) instead of per-item numpy
+    work, a collate and a host-to-device copy.  Yields ``(x [b,T,C,H,W], y [b,T,1,H,W], mask [b,T,1,H,W])`` as fresh f32 device
+    tensors on the current stream, batch for batch what a ``DataLoader`` over the same sampler yields;
+    ``train_one_epoch`` / ``evaluate`` / ``evaluate_report`` take it unchanged.
+
+    ``dataset``: an ``NPZSequenceDataset`` or (nested) ``Subset``s of one.  Its raw ``X`` / ``Y`` are uploaded once per
+    (dataset, device) and cached on the dataset object, so loaders over several Subsets of one dataset share one device copy;
+    a dataset larger than ``max_resident_bytes`` (default: 80 % of the device memory free at that moment) raises
+    ``UclstmError`` -- streaming is not implemented.  The index order is the torch sampler's, iterated on the host:
+    ``sampler=`` any sampler or iterable of positions (``DistributedSampler``: ``set_epoch`` stays the caller's job),
+    ``shuffle=True`` = ``RandomSampler(dataset, generator=generator)``.  Per epoch the row list goes to the device as one pinned
+    int64 tensor; per batch nothing is copied and nothing synchronises."""
+
+    def __init__(self, dataset, batch_size: int, shuffle: bool = False, sampler=None, drop_last: bool = False, generator=None,
+                 device="cuda", max_resident_bytes: Optional[int] = None):
+        self.root, _ = _root_rows(dataset)
+        if batch_size <= 0:
+            raise ValueError(f"batch_size must be positive, got {batch_size}")
+        if sampler is not None and shuffle:
+            raise ValueError("sampler option is mutually exclusive with shuffle")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ops.L.UclstmError(f"DeviceSequenceLoader: a HIP device is required, got {dev} (this package has no CPU path)")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+        self.dataset, self.batch_size, self.drop_last = dataset, int(batch_size), bool(drop_last)
+        if sampler is None:
+            sampler = (torch.utils.data.RandomSampler(dataset, generator=generator) if shuffle
+                       else torch.utils.data.SequentialSampler(dataset))
+        self.sampler = sampler
+        self.x_all, self.y_all = self._resident(self.root, self.device, max_resident_bytes)
+
+    @staticmethod
+    def _resident(root, device, max_resident_bytes):
+        cache = root.__dict__.setdefault("_device_resident", {})
+        if device not in cache:
+            need = int(root.X.nbytes) + int(root.Y.nbytes)
+            limit = int(0.8 * torch.cuda.mem_get_info(device)[0]) if max_resident_bytes is None else int(max_resident_bytes)
+            if need > limit:
+                raise ops.L.UclstmError(f"DeviceSequenceLoader: the raw dataset needs {need} bytes on {device} "
+                                        f"(X {root.X.nbytes} + Y {root.Y.nbytes}), the limit is {limit} bytes; "
+                                        "streaming a dataset that does not fit is not implemented")
+            cache[device] = (torch.from_numpy(np.ascontiguousarray(root.X)).to(device),
+                             torch.from_numpy(np.ascontiguousarray(root.Y)).to(device))
+        return cache[device]
+
+    def __len__(self):
+        n = len(self.sampler)
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        return self.batches()
+
+    def batches(self, out=None):
+        """The epoch's batches.  ``out=(x, y, mask)``: every (full) batch is written into these caller-owned contiguous f32
+        device buffers, which are yielded themselves -- the static inputs of a ``GraphedTrainStep``; a short last batch cannot
+        be written into them, so ``drop_last=False`` is refused when the sampler's length is no multiple of the batch."""
+        T, Cc, H, W = self.x_all.shape[1:]
+        if out is not None:
+            if not self.drop_last and len(self.sampler) % self.batch_size:
+                raise ValueError(f"batches(out=...): the last batch of {len(self.sampler)} positions in batches of "
+                                 f"{self.batch_size} would be short; use drop_last=True")
+            want = ((self.batch_size, T, Cc, H, W), (self.batch_size, T, 1, H, W), (self.batch_size, T, 1, H, W))
+            if len(out) != 3:
+                raise ValueError("batches(out=...): expected (x, y, mask)")
+            for t, shape, what in zip(out, want, ("out x", "out y", "out mask")):
+                ops._dev(t, torch.float32, what)
+                if tuple(t.shape) != shape or t.device != self.device:
+                    raise ValueError(f"batches(out=...): {what} must be {shape} on {self.device}, got {tuple(t.shape)} on {t.device}")
+        batches = epoch_rows(self.dataset, self.sampler, self.batch_size, self.drop_last)      # validated before any upload
+        return self._run(batches, out)
+
+    def _run(self, batches, out):
+        if not batches:
+            return
+        # ONE pinned int64 tensor per epoch, copied without blocking; this generator's frame keeps it alive until the epoch ends
+        pinned = torch.from_numpy(np.concatenate(batches)).pin_memory()
+        rows = pinned.to(self.device, non_blocking=True)
+        s = 0
+        for b in [len(b) for b in batches]:
+            yield _gather_transform(self.root, self.x_all, self.y_all, rows[s:s + b], b, out)
+            s += b
+        del pinned
 
 
 # ---------------------------------------------------------------------------------------------
