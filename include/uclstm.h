@@ -258,6 +258,28 @@ int32_t uclstm_bn_stats_fwd(float* stats, int32_t groups, int32_t tiles_per_grou
                             void* stream);
 int32_t uclstm_bn_running_stats(const float* stats, int32_t groups, int32_t tiles_per_group, int32_t Cp, int32_t C,
                                 int64_t count_per_group, float* running_mean, float* running_var, float momentum, void* stream);
+
+/* Statistics over all ranks of a data-parallel run (SyncBatchNorm): uclstm_bn_stats_fwd cut in two where the other ranks' sums
+ * come in.  Every rank must hold the same count per group.
+ *   uclstm_bn_stats_partial:   sums64[g][c] = (sum, sum of squares) in f64 (f64 [groups][Cp][2], 16-byte aligned) of the epilogue's
+ *     f32 partials, in the summation order of uclstm_bn_stats_fwd (16 strided tile lanes in f64, then the lane sums left to
+ *     right).  `stats` is NOT consumed.  The caller adds the sums64 of all ranks (all-reduce, SUM).
+ *   uclstm_bn_stats_from_sums: from the added sums and world_count_per_group = ranks * count_per_group:  m = s1/n,
+ *     var = max(0, s2/n - m*m), then scale / shift / mean / rstd exactly as uclstm_bn_stats_fwd (mean and variance rounded to f32
+ *     before rstd), pad channels zero, and (mean, variance) left in the tile-0 slots of `stats`, where uclstm_bn_running_stats --
+ *     called with world_count_per_group for the unbiased variance -- finds them.
+ * With one rank the pair gives the bits of uclstm_bn_stats_fwd. */
+int32_t uclstm_bn_stats_partial(const float* stats, int32_t groups, int32_t tiles_per_group, int32_t Cp, double* sums64, void* stream);
+int32_t uclstm_bn_stats_from_sums(const double* sums64, int64_t world_count_per_group, float* stats, int32_t groups,
+                                  int32_t tiles_per_group, int32_t Cp, int32_t C, const float* gamma, const float* beta, float eps,
+                                  float* scale, float* shift, float* mean, float* rstd, void* stream);
+/* The same for the backward pass: the f32 (sum g, sum g*xhat) of pass 1 (`sums`, n = groups*Cp*2 values, left untouched: the
+ * parameter gradients keep reading them) as f64 in `sums64`, the all-reduce payload; then sums_dz = (float)(sums64 * inv_world),
+ * inv_world = 1 / ranks in (0, 1].  The apply kernels divide by the LOCAL count, so with equal counts on every rank they compute
+ * S_global / n_global from sums_dz.  With one rank sums_dz has the bits of sums. */
+int32_t uclstm_bn_bwd_sums_stage(const float* sums, double* sums64, int64_t n, void* stream);
+int32_t uclstm_bn_bwd_sums_finish(const double* sums64, double inv_world, float* sums_dz, int64_t n, void* stream);
+
 /* a = relu(z*scale[g] + shift[g]),  g = pixel / pixels_per_group;  z, a bf16 [pixels][Cp]. */
 int32_t uclstm_bn_apply_relu(const void* z, void* a, const float* scale, const float* shift,
                              int64_t pixels, int64_t pixels_per_group, int32_t Cp, void* stream);

@@ -19,8 +19,10 @@ from .ddp import FlatDDP
 from .streaming import StreamingPredictor
 from .ops import compute_dtype, set_compute_dtype, get_compute_dtype
 from .ops import deterministic, set_deterministic, is_deterministic
+from .ops import sync_batchnorm, set_sync_batchnorm, get_sync_batchnorm
 
 __all__ = ["ConvLSTMCell", "ConvLSTM", "DoubleConv", "Down", "Up", "OutConv", "SpatialAttention",
            "TemporalUNetDualView", "UNet", "compute_loss", "FusedAdamW", "train_one_epoch", "evaluate",
            "train_step", "GraphedTrainStep", "quiesce_host_gc", "SyntheticSequences", "NPZSequenceDataset", "device_transform", "EvalReport", "evaluate_report", "DeviceSequenceLoader", "epoch_rows", "FlatDDP", "StreamingPredictor", "UclstmError", "ops",
-           "compute_dtype", "set_compute_dtype", "get_compute_dtype", "deterministic", "set_deterministic", "is_deterministic"]
+           "compute_dtype", "set_compute_dtype", "get_compute_dtype", "deterministic", "set_deterministic", "is_deterministic",
+           "sync_batchnorm", "set_sync_batchnorm", "get_sync_batchnorm"]

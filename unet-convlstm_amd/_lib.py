@@ -128,6 +128,10 @@ _PROTOS = {
     "uclstm_bn_finalize": [_P, _I, _I, _I, _I, _L, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P],
     "uclstm_bn_stats_fwd": [_P, _I, _I, _I, _I, _L, _P, _P, _F, _P, _P, _P, _P, _P],
     "uclstm_bn_running_stats": [_P, _I, _I, _I, _I, _L, _P, _P, _F, _P],
+    "uclstm_bn_stats_partial": [_P, _I, _I, _I, _P, _P],
+    "uclstm_bn_stats_from_sums": [_P, _L, _P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P],
+    "uclstm_bn_bwd_sums_stage": [_P, _P, _L, _P],
+    "uclstm_bn_bwd_sums_finish": [_P, C.c_double, _P, _L, _P],
     "uclstm_bn_apply_relu": [_P, _P, _P, _P, _L, _L, _I, _P],
     "uclstm_bn_bwd_reduce_rows": [_L, _L],
     "uclstm_bn_bwd_reduce": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P],

@@ -153,6 +153,79 @@ __global__ void bn_running_kernel(const float* __restrict__ stats, int groups, i
     rvar[c] = rv;
 }
 
+#ifndef UCLSTM_ACT_F16
+// Statistics over all ranks of a data-parallel run (SyncBatchNorm), bn_stats_kernel cut in two at the point where the sums of the
+// other ranks come in.  First half: the f64 (sum, sum of squares) per (group, channel), summed exactly as bn_stats_kernel does (16
+// strided tile lanes in f64, then the 16 lane sums left to right); `stats` is only read.
+__global__ __launch_bounds__(1024) void bn_stats_partial_kernel(const float* __restrict__ stats, int tpg, int Cp,
+                                                                double* __restrict__ sums64) {
+    __shared__ double r1[16][64], r2[16][64];
+    const int g = blockIdx.x;
+    const int cl = threadIdx.x & 63, lane = threadIdx.x >> 6;
+    const int c = blockIdx.y * 64 + cl;
+    double s1 = 0.0, s2 = 0.0;
+    if (c < Cp) {
+        for (int t = lane; t < tpg; t += 16) {
+            const float2 v = *(const float2*)(stats + (((long)g * tpg + t) * Cp + c) * 2);
+            s1 += v.x;
+            s2 += v.y;
+        }
+    }
+    r1[lane][cl] = s1;
+    r2[lane][cl] = s2;
+    __syncthreads();
+    if (lane == 0 && c < Cp) {
+        s1 = 0.0;
+        s2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            s1 += r1[k][cl];
+            s2 += r2[k][cl];
+        }
+        *(double2*)(sums64 + ((long)g * Cp + c) * 2) = make_double2(s1, s2);
+    }
+}
+
+// Second half: from the sums of all ranks and 1 / (the count of all ranks), what bn_stats_kernel computes after its reduction, in
+// the same operations and roundings (one rank: the same bits).
+__global__ void bn_stats_from_sums_kernel(const double* __restrict__ sums64, float* __restrict__ stats, int tpg, int Cp, int C,
+                                          double inv_cnt, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                          float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ mean_o,
+                                          float* __restrict__ rstd_o) {
+    const int g = blockIdx.x;
+    const int c = blockIdx.y * 64 + threadIdx.x;
+    if (c < Cp) {
+        const double2 s = *(const double2*)(sums64 + ((long)g * Cp + c) * 2);
+        const double s1 = s.x, s2 = s.y;
+        const double m = s1 * inv_cnt;
+        double var = s2 * inv_cnt - m * m;
+        var = var < 0.0 ? 0.0 : var;
+        const float mv = (float)m, vv = (float)var;
+        *(float2*)(stats + ((long)g * tpg * Cp + c) * 2) = make_float2(mv, vv);
+        const bool real = c < C;
+        const float rs = real ? (float)(1.0 / sqrt((double)vv + (double)eps)) : 0.f;
+        const float sc = real ? gamma[c] * rs : 0.f;
+        const long o = (long)g * Cp + c;
+        scale[o] = sc;
+        shift[o] = real ? beta[c] - mv * sc : 0.f;
+        if (mean_o) mean_o[o] = real ? mv : 0.f;
+        if (rstd_o) rstd_o[o] = rs;
+    }
+}
+
+// The f32 (sum g, sum g*xhat) of the backward reduction as f64, the payload of the all-reduce, and back: the sum over all ranks
+// times 1 / world size is what the apply kernels, which divide by the LOCAL count, need in order to compute S_global / n_global
+// (equal counts on every rank).  One rank: f32 -> f64 -> * 1.0 -> f32 is the identity.
+__global__ void bn_bwd_sums_stage_kernel(const float* __restrict__ sums, double* __restrict__ sums64, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) sums64[i] = (double)sums[i];
+}
+__global__ void bn_bwd_sums_finish_kernel(const double* __restrict__ sums64, double inv_world, float* __restrict__ sums_dz, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) sums_dz[i] = (float)(sums64[i] * inv_world);
+}
+#endif
+
 // Pass 2: per channel, groups IN ORDER (running statistics are a sequential momentum recursion).
 __global__ void bn_finalize_kernel(const float* __restrict__ stats, int groups, int tpg, int Cp, int C,
                                    double unbias, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -1599,6 +1672,38 @@ extern "C" int32_t uclstm_bn_running_stats(const float* stats, int32_t groups, i
     const double unb = count_per_group > 1 ? (double)count_per_group / (double)(count_per_group - 1) : 1.0;
     UCLSTM_LAUNCH(bn_running_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, stats, groups, tiles_per_group, Cp, C, unb,
                   running_mean, running_var, momentum);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_bn_stats_partial(const float* stats, int32_t groups, int32_t tiles_per_group, int32_t Cp, double* sums64,
+                                           void* stream) {
+    if (!stats || !sums64 || !aligned16(sums64) || groups <= 0 || tiles_per_group <= 0 || Cp <= 0) return UCLSTM_E_BADARG;
+    UCLSTM_LAUNCH(bn_stats_partial_kernel, dim3(groups, (Cp + 63) / 64), dim3(1024), 0, (hipStream_t)stream, stats, tiles_per_group, Cp,
+                  sums64);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_bn_stats_from_sums(const double* sums64, int64_t world_count_per_group, float* stats, int32_t groups,
+                                             int32_t tiles_per_group, int32_t Cp, int32_t C, const float* gamma, const float* beta, float eps,
+                                             float* scale, float* shift, float* mean, float* rstd, void* stream) {
+    if (!sums64 || !aligned16(sums64) || !stats || groups <= 0 || tiles_per_group <= 0 || Cp <= 0 || C <= 0 || C > Cp ||
+        world_count_per_group <= 0 || !gamma || !beta || !scale || !shift)
+        return UCLSTM_E_BADARG;
+    UCLSTM_LAUNCH(bn_stats_from_sums_kernel, dim3(groups, (Cp + 63) / 64), dim3(64), 0, (hipStream_t)stream, sums64, stats,
+                  tiles_per_group, Cp, C, 1.0 / (double)world_count_per_group, gamma, beta, eps, scale, shift, mean, rstd);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_bn_bwd_sums_stage(const float* sums, double* sums64, int64_t n, void* stream) {
+    if (!sums || !sums64 || n <= 0 || n > ((int64_t)1 << 30)) return UCLSTM_E_BADARG;
+    UCLSTM_LAUNCH(bn_bwd_sums_stage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sums, sums64, (long)n);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_bn_bwd_sums_finish(const double* sums64, double inv_world, float* sums_dz, int64_t n, void* stream) {
+    if (!sums64 || !sums_dz || n <= 0 || n > ((int64_t)1 << 30) || !(inv_world > 0.0) || inv_world > 1.0) return UCLSTM_E_BADARG;
+    UCLSTM_LAUNCH(bn_bwd_sums_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sums64, inv_world,
+                  sums_dz, (long)n);
     return UCLSTM_OK;
 }
 #endif

@@ -5,8 +5,12 @@ ranks, one gradient exchange per step.
 from the END of the buffer backwards: backward produces gradients in (nearly) reverse registration
 order -- decoder first, then the three ConvLSTM weights when their BPTT finishes, encoder last -- so
 each bucket is launched (async, on RCCL's own stream over xGMI) as soon as its last gradient has
-been accumulated and overlaps the rest of backward.  BatchNorm statistics stay local per rank
-(the reference has no SyncBN); parameters and buffers are broadcast from rank 0 once.
+been accumulated and overlaps the rest of backward.  Parameters and buffers are broadcast from rank 0 once.
+
+BatchNorm statistics are per rank by default.  ``FlatDDP(..., sync_bn=True)`` makes ``train_step`` run forward and
+backward under ``ops.sync_batchnorm(process_group)``: every BatchNorm stage then normalises over the batch of all ranks,
+as the (single-process) reference does over its one batch, at the price of two small f64 all-reduces per stage.  The
+statistics are exchanged inside ``no_sync()`` too; only the gradient buckets wait.
 
 Backend-agnostic: ``nccl`` (= RCCL on ROCm) on GPUs, ``gloo`` in the CPU tests.
 """
@@ -31,8 +35,11 @@ def _unregister(side_hook, use_hook) -> None:
 
 class FlatDDP:
     def __init__(self, module: torch.nn.Module, flat: FlatParams, bucket_mb: float = 64.0, process_group=None,
-                 broadcast: bool = True, first_bucket_mb: float = 1.0, grad_dtype: Optional[torch.dtype] = None):
-        """``grad_dtype=torch.bfloat16``: exchange the gradients as bf16 (half the bytes per link; every bucket is cast into
+                 broadcast: bool = True, first_bucket_mb: float = 1.0, grad_dtype: Optional[torch.dtype] = None,
+                 sync_bn: bool = False):
+        """``sync_bn=True``: BatchNorm statistics, running statistics and the BatchNorm backward sums over all ranks of the
+        process group (every rank must bring the same number of sequences per step).
+        ``grad_dtype=torch.bfloat16``: exchange the gradients as bf16 (half the bytes per link; every bucket is cast into
         a staging buffer, all-reduced there and cast back into the f32 gradient buffer before the optimiser step)."""
         if not dist.is_initialized():
             raise RuntimeError("FlatDDP: torch.distributed is not initialised")
@@ -44,6 +51,7 @@ class FlatDDP:
             raise RuntimeError("FlatDDP: these FlatParams already belong to a live FlatDDP; call remove_hooks() on it first")
         flat._ddp_owner = weakref.ref(self)
         self.module, self.flat, self.pg = module, flat, process_group
+        self.sync_bn = bool(sync_bn)
         self.grad_dtype = None if grad_dtype in (None, torch.float32) else grad_dtype
         self._stage = torch.empty_like(flat.flat_g, dtype=self.grad_dtype) if self.grad_dtype is not None else None
         self.world = dist.get_world_size(process_group)

@@ -7,6 +7,7 @@ the metric block on the device as running sums instead of per-pixel Python lists
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Optional
 
@@ -326,12 +327,17 @@ def train_step(model, optimizer, x, y, mask=None, use_mask=True, ddp=None, clip_
     if on_gpu:
         from . import ops
         ops.prepack_begin()          # weights are fixed until optimizer.step(): pack this step's panels ahead, off the main stream
+    # FlatDDP(sync_bn=True): forward and backward run with BatchNorm statistics over the wrapper's process group
+    sync = contextlib.nullcontext()
+    if ddp is not None and getattr(ddp, "sync_bn", False) and on_gpu:
+        sync = ops.sync_batchnorm(ddp.pg)
     try:
-        output, _ = model(x)
-        y_pred = _stack(output)
-        loss = compute_loss(y_pred, y, mask, use_mask)
-        # fp16 compute: backward runs on loss * scale (FusedAdamW(loss_scale=...) owns the device-side dynamic scale)
-        (optimizer.scale_loss(loss) if hasattr(optimizer, "scale_loss") else loss).backward()
+        with sync:
+            output, _ = model(x)
+            y_pred = _stack(output)
+            loss = compute_loss(y_pred, y, mask, use_mask)
+            # fp16 compute: backward runs on loss * scale (FusedAdamW(loss_scale=...) owns the device-side dynamic scale)
+            (optimizer.scale_loss(loss) if hasattr(optimizer, "scale_loss") else loss).backward()
     finally:
         if on_gpu:
             ops.prepack_end()
@@ -370,6 +376,9 @@ class GraphedTrainStep:
             raise ValueError("GraphedTrainStep needs FusedAdamW(..., capturable=True)")
         if not x.is_cuda:
             raise ops.L.UclstmError("GraphedTrainStep: HIP device tensors required")
+        if ops.get_sync_batchnorm() is not None:
+            raise ops.L.UclstmError("GraphedTrainStep: sync_batchnorm is on -- the step then contains collectives, and a graphed "
+                                    "step is single-rank only; turn the switch off or use the eager train_step")
         self.model, self.optimizer, self.use_mask, self.clip_norm = model, optimizer, use_mask, clip_norm
         self.deterministic = ops.is_deterministic()
         self.x, self.y = x.clone(), y.clone()

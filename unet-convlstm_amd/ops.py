@@ -85,6 +85,95 @@ class deterministic:
         set_deterministic(self.prev)
 
 
+# SyncBatchNorm: with the switch on, every training-mode BatchNorm stage normalises over the batch of ALL ranks of a process group
+# (statistics, running statistics and the two mean terms of the backward pass), as the reference does over its one batch -- two
+# small f64 all-reduces per stage (uclstm_bn_stats_partial / _from_sums, uclstm_bn_bwd_sums_stage / _finish in include/uclstm.h).
+# Every rank must bring the same images per BatchNorm group (DistributedSampler does).  Off by default.
+_SYNC_BN = False
+_SYNC_BN_GROUP = None              # the process group while the switch is on; None = the default group
+_SYNC_BN_CHECKED: set = set()      # (group, n_img, H, W, groups) found equal on every rank
+
+
+def set_sync_batchnorm(process_group=None) -> None:
+    """``True`` -- on, over the default process group; a process group -- on, over that group; ``None`` / ``False`` -- off."""
+    global _SYNC_BN, _SYNC_BN_GROUP
+    if process_group is None or process_group is False:
+        _SYNC_BN, _SYNC_BN_GROUP = False, None
+        return
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        raise L.UclstmError("sync_batchnorm: torch.distributed is not initialised (call init_process_group first)")
+    _SYNC_BN, _SYNC_BN_GROUP = True, (None if process_group is True else process_group)
+
+
+def get_sync_batchnorm():
+    """``None`` while the switch is off, otherwise the process group (``True`` stands for the default group)."""
+    return None if not _SYNC_BN else (True if _SYNC_BN_GROUP is None else _SYNC_BN_GROUP)
+
+
+class sync_batchnorm:
+    """``with ops.sync_batchnorm(group): train_step(...)`` -- BatchNorm statistics over all ranks of ``group`` (``None``: the
+    default group) for the forward passes started inside; the backward pass of such a forward uses the same group wherever it
+    runs.  The previous setting is restored on exit, also when the block raises."""
+
+    def __init__(self, process_group=None):
+        self.group = True if process_group is None else process_group
+
+    def __enter__(self):
+        self.prev = get_sync_batchnorm()
+        set_sync_batchnorm(self.group)
+        return self
+
+    def __exit__(self, *exc):
+        global _SYNC_BN, _SYNC_BN_GROUP
+        _SYNC_BN, _SYNC_BN_GROUP = self.prev is not None, (None if self.prev in (None, True) else self.prev)
+
+
+def _sync_bn_check_equal(group, n_img: int, H: int, W: int, groups: int) -> int:
+    """World size of ``group``, after making sure ONCE per shape that every rank brings the same images and plane size per
+    BatchNorm group (one small host-side collective; afterwards nothing here touches the host).  A shape seen for the first
+    time must be new on every rank at the same step, or the ranks disagree about who takes part in the collective -- equal work
+    per rank, which the scheme needs anyway, guarantees it."""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    key = (group, n_img, H, W, groups)
+    if key not in _SYNC_BN_CHECKED:
+        mine = (int(n_img), int(H), int(W), int(groups))
+        seen = [None] * world
+        dist.all_gather_object(seen, mine, group=group)
+        if any(tuple(s) != mine for s in seen):
+            raise L.UclstmError("sync_batchnorm: every rank must bring the same (images, H, W, BatchNorm groups) per stage, got "
+                                + ", ".join(f"rank {r}: {tuple(s)}" for r, s in enumerate(seen)))
+        _SYNC_BN_CHECKED.add(key)
+    return world
+
+
+def _sync_bn_all_reduce(t: torch.Tensor, group, what: str) -> None:
+    """Sum of ``t`` (f64) over the ranks, ordered into the current stream: RCCL's stream waits for the current stream and the
+    current stream for the collective (no host block); gloo copies through the host and blocks it (tests)."""
+    import torch.distributed as dist
+    if LAUNCH_LOG is not None:
+        LAUNCH_LOG.append(("collective", what, t.numel() * t.element_size()))
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+
+
+def _bn_bwd_sums_over_ranks(sums: torch.Tensor, sync, variant: str) -> torch.Tensor:
+    """The backward sums of all ranks in the form the apply kernels take (``sums`` itself stays local for the parameter
+    gradients).  ``sync`` = (group, world) of the forward pass; ``variant`` ("plain" / "pool" / "head") goes to LAUNCH_LOG."""
+    group, world = sync
+    sums64 = torch.empty(sums.shape, dtype=torch.float64, device=sums.device)
+    sums_dz = torch.empty_like(sums)
+    n = sums.numel()
+    if LAUNCH_LOG is not None:
+        LAUNCH_LOG.append(("syncbn", "bn_bwd_sums_stage", variant))
+    L.check(L.lib.uclstm_bn_bwd_sums_stage(_p(sums), _p(sums64), n, _stream()), "bn_bwd_sums_stage")
+    _sync_bn_all_reduce(sums64, group, "bn_bwd_sums")
+    if LAUNCH_LOG is not None:
+        LAUNCH_LOG.append(("syncbn", "bn_bwd_sums_finish", variant))
+    L.check(L.lib.uclstm_bn_bwd_sums_finish(_p(sums64), 1.0 / world, _p(sums_dz), n, _stream()), "bn_bwd_sums_finish")
+    return sums_dz
+
+
 def _k(t: torch.Tensor):
     """Kernel set (bf16 / fp16 twins) for a 16-bit activation tensor."""
     return L.kernels(t.dtype)
@@ -1281,6 +1370,7 @@ class ConvBNReLU(_GradAwareFunction):
         K = _k(x0)
         need_bw = _will_backward(ctx)
         pooled = None
+        sync = None                     # (process group, world size) where this stage's statistics are those of all ranks
         if training:
             ppg = (n_img // groups) * H * W
             tpg = L.lib.uclstm_igemm_tiles_per_group(n_img, H, W, groups, Cop)
@@ -1288,7 +1378,37 @@ class ConvBNReLU(_GradAwareFunction):
             z = out
             igemm_store(srcs, wp, (H, W), n_img, [(z, 0, Cop, 0, 1, 0, 0)], ktap=ktap, pad=pad, groups=groups, bias=bp, stats=stats)
             par = torch.empty((4, groups, Cop), dtype=F32, device=dev)     # scale, shift, mean, rstd
-            if ASYNC_WGRAD and BN_RUNNING_ON_SIDE and not torch.cuda.is_current_stream_capturing():
+            if _SYNC_BN:
+                # statistics over all ranks: f64 sums of this rank -> all-reduce -> scale / shift / mean / rstd from the sums of
+                # all ranks.  `stats` then holds (mean, variance) of the global batch in its tile-0 slots, and the running
+                # statistics below are updated from them with the global count.
+                if torch.cuda.is_current_stream_capturing():
+                    raise L.UclstmError("sync_batchnorm: a step with collectives cannot be captured in a HIP graph")
+                variant = "head" if head_w is not None else ("pool" if (pool and H % 2 == 0 and W % 2 == 0 and Cop // 8 <= 256) else "plain")
+                world = _sync_bn_check_equal(_SYNC_BN_GROUP, n_img, H, W, groups)
+                sync = (_SYNC_BN_GROUP, world)
+                sums64 = torch.empty((groups, Cop, 2), dtype=torch.float64, device=dev)
+                if LAUNCH_LOG is not None:
+                    LAUNCH_LOG.append(("syncbn", "bn_stats_partial", variant))
+                L.check(L.lib.uclstm_bn_stats_partial(_p(stats), groups, tpg, Cop, _p(sums64), _stream()), "bn_stats_partial")
+                _sync_bn_all_reduce(sums64, _SYNC_BN_GROUP, "bn_stats")
+                if LAUNCH_LOG is not None:
+                    LAUNCH_LOG.append(("syncbn", "bn_stats_from_sums", variant))
+                L.check(L.lib.uclstm_bn_stats_from_sums(_p(sums64), world * ppg, _p(stats), groups, tpg, Cop, Co, _p(gamma), _p(beta), eps,
+                                                        _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _stream()), "bn_stats_from_sums")
+                if ASYNC_WGRAD and BN_RUNNING_ON_SIDE:
+                    main, side = torch.cuda.current_stream(dev), side_stream(dev)
+                    side.wait_stream(main)
+                    with torch.cuda.stream(side):
+                        L.check(L.lib.uclstm_bn_running_stats(_p(stats), groups, tpg, Cop, Co, world * ppg, _p(running_mean),
+                                                              _p(running_var), momentum, _stream()), "bn_running_stats")
+                        stats.record_stream(side)
+                    _FWD_SIDE_PENDING.add(str(dev))
+                else:
+                    # the one-launch route's counterpart: the same momentum steps, on the main stream
+                    L.check(L.lib.uclstm_bn_running_stats(_p(stats), groups, tpg, Cop, Co, world * ppg, _p(running_mean), _p(running_var),
+                                                          momentum, _stream()), "bn_running_stats")
+            elif ASYNC_WGRAD and BN_RUNNING_ON_SIDE and not torch.cuda.is_current_stream_capturing():
                 # critical part in one launch (reduction + scale / shift / mean / rstd); the in-order running-statistics recursion,
                 # which nothing in this step waits for, on the second stream (joined at the end of the forward pass: join_forward_side)
                 L.check(L.lib.uclstm_bn_stats_fwd(_p(stats), groups, tpg, Cop, Co, ppg, _p(gamma), _p(beta), eps, _p(par[0]), _p(par[1]),
@@ -1349,6 +1469,7 @@ class ConvBNReLU(_GradAwareFunction):
             ctx.save_for_backward(x0, x1, weight, None, None, gamma, beta, bias, None, None)
         ctx.cfg = (tuple(c_valid), tuple(off), groups, training, im2col, Co, Ci_total, bias is not None)
         ctx.pool = bool(pool)
+        ctx.sync_bn = sync
         if pool:
             ctx.pool_fused = pooled is not None
             if pooled is None:          # evaluation mode, odd sizes: the stand-alone pooling kernel on the finished activation
@@ -1392,8 +1513,9 @@ class ConvBNReLU(_GradAwareFunction):
                            lambda: L.check(K.uclstm_bn_head_bwd_reduce(_p(z), _p(dy), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(head_w),
                                                                        _p(partials), _p(sums), _p(dwh), _p(dbh), pixels, ppg, Cop, Co, _stream()),
                                            "bn_head_bwd_reduce"))
+            sums_dz = sums if ctx.sync_bn is None else _bn_bwd_sums_over_ranks(sums, ctx.sync_bn, "head")
             _timed_hbm("bn_head_bwd_apply", 4.0 * z.numel() + 4.0 * pixels,
-                       lambda: L.check(K.uclstm_bn_head_bwd_apply(_p(z), _p(dy), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(sums),
+                       lambda: L.check(K.uclstm_bn_head_bwd_apply(_p(z), _p(dy), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(sums_dz),
                                                                   _p(head_w), _p(dz), pixels, ppg, Cop, Co, _stream()), "bn_head_bwd_apply"))
             if direct:
                 grad_written(head_w)
@@ -1412,6 +1534,8 @@ class ConvBNReLU(_GradAwareFunction):
                                                                    _p(prt), _p(sums), n_img, H, W, Cop, groups, _stream()),
                                        "bn_pool_bwd_reduce"))
             sums_dz = sums if training else torch.zeros_like(sums)
+            if ctx.sync_bn is not None:
+                sums_dz = _bn_bwd_sums_over_ranks(sums, ctx.sync_bn, "pool")
             _timed_hbm("bn_pool_bwd_apply", (6.5 if dsk is not None else 4.5) * z.numel(),
                        lambda: L.check(K.uclstm_bn_pool_bwd_apply(_p(z), _p(dsk), _p(dp), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]),
                                                                   _p(sums_dz), _p(dz), n_img, H, W, Cop, groups, _stream()),
@@ -1432,6 +1556,8 @@ class ConvBNReLU(_GradAwareFunction):
             # training: dz = scale*(g - s1/n - xhat*s2/n).  Evaluation-mode statistics are constants, the two mean terms vanish:
             # the same kernel with zero sums gives dz = scale*g (sums itself still holds dbeta / dgamma)
             sums_dz = sums if training else torch.zeros_like(sums)
+            if ctx.sync_bn is not None:
+                sums_dz = _bn_bwd_sums_over_ranks(sums, ctx.sync_bn, "plain")
             _timed_hbm("bn_bwd_apply", 6.0 * z.numel(),             # z, da read, dz written
                        lambda: L.check(K.uclstm_bn_bwd_apply(_p(z), _p(da), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(sums_dz),
                                                              _p(dz), pixels, ppg, Cop, _stream()), "bn_bwd_apply"))
