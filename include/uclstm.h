@@ -550,6 +550,29 @@ int32_t uclstm_dataset_gather_transform(const float* x_all, const float* y_all, 
                                         int32_t T, int32_t C, int32_t HW, float* x, float* y, float* mask, int32_t transform,
                                         float norm_const, float min_vel, float max_vel, int32_t clip, float y_scale,
                                         float trans_min, float trans_max, void* stream);
+/* uclstm_dataset_gather_transform with a per-sequence index remap (augmentation): output sequence o takes the device table row
+ * aug[o] = {code, oy, ox, t0} (int32 x 4).  From source frame t0 + t the window [oy, oy + Hc) x [ox, ox + Wc) is cut (s) and moved:
+ * out[i][j] = s[a][b], (a, b) = (j, i) if code & 4 (t) else (i, j); then a = Hc-1-a if code & 2 (v); then b = Wc-1-b if code & 1
+ * (h) -- torch: flip(-1) for h, then flip(-2) for v, then transpose(-2, -1) for t.  The output frame is Ho x Wo = Hc x Wc, or
+ * Wc x Hc with t; one launch has one output shape, so codes with t require Ho == Wo.
+ * x_all f32 [n_seq][T_src][C][Hs][Ws], y_all f32 [n_seq][T_src][1][Hs][Ws] -> x [n_out][T_out][C][Ho][Wo], y, mask
+ * [n_out][T_out][1][Ho][Wo].  The mask is raw channel 0 > 1.1 at the SOURCE pixel; the arithmetic is per pixel and that of
+ * uclstm_dataset_gather_transform, so the result is bit-identical to that entry point's output moved the same way.  Scalar
+ * targets only: a vector target (horizontal velocity components) would need sign changes under mirrors.
+ * flags: bit 0 = the table may hold codes with t (requires Ho == Wo); bit 1 = every ox in the table is a multiple of 4.
+ * The kernel clamps what it reads from the table like idx (the caller validates): code & 7, or & 3 when bit 0 is clear; oy, ox, t0
+ * into the range that keeps the window inside the source (ox rounded down to a multiple of 4 on the 16-byte path).
+ * 16-byte loads / stores when Ws % 4 == 0, Wo % 4 == 0, bit 1 is set and all five data pointers are 16-byte aligned; a scalar path
+ * otherwise.  Every code reads and writes along rows; codes with t turn 32 x 32 tiles through LDS.  f32 only (no _f16 twin).
+ * Requires Ho <= Hs, Wo <= Ws, T_out <= T_src, n_out * T_out * Ho * Wo < 2^31, Hs * Ws < 2^31. */
+int32_t uclstm_dataset_gather_augment(const float* x_all, const float* y_all, const int64_t* idx, const int32_t* aug,
+        int64_t n_seq, int64_t n_out, int32_t T_src, int32_t T_out, int32_t C, int32_t Hs, int32_t Ws, int32_t Ho, int32_t Wo,
+        int32_t flags, float* x, float* y, float* mask, int32_t transform, float norm_const, float min_vel, float max_vel, int32_t clip,
+        float y_scale, float trans_min, float trans_max, void* stream);
+/* dst = (accumulate ? dst : 0) + scale * move(src) with the same mover and codes 0..7: src f32 [n_planes][H][W]; dst
+ * [n_planes][H][W], or [n_planes][W][H] for codes with t.  src and dst must not overlap.  Requires n_planes * H * W < 2^31. */
+int32_t uclstm_plane_d4(const float* src, float* dst, int64_t n_planes, int32_t H, int32_t W, int32_t code, int32_t accumulate,
+                        float scale, void* stream);
 /* Epoch metric block of main.py:114-142 as running sums: sums[0..3] += sum|d|m, sum d^2 m, sum d m, sum m with
  * d = denormalize(y_pred) - denormalize(y) (train/unet.py:316-319, asinh transform); mask may be NULL. */
 int32_t uclstm_metric_sums(const float* y_pred, const float* y, const float* mask, double* sums, int64_t n, float y_scale,

@@ -12,7 +12,13 @@ timed ones per arm.  Also timed: the gather kernel alone (cold caches: a 1 GiB f
 its algorithmic bytes ((C + 1) * 4 read + (C + 2) * 4 written per pixel), the one-off upload of the raw arrays, and the
 training step alone on one resident batch (what ``bench.py`` times: the floor for both arms).
 
+``--augment`` times the augmenting gather kernel (``uclstm_dataset_gather_augment``) alone instead, same protocol (cold caches, HIP
+events, ``--kernel-rounds`` rounds, the arms alternating inside a round), at the same two shapes: codes without t, codes with t
+(through the LDS tile), and a crop to half the frame size (128 -> 64 at the second shape) with all eight codes -- each against the
+plain gather kernel writing the same OUTPUT bytes in the same run.
+
     python tools/bench_loader.py [--epochs 3] [--out profiles/device_loader_ab.txt]
+    python tools/bench_loader.py --augment [--out profiles/device_loader_augment_ab.txt]
 """
 import argparse
 import os
@@ -35,6 +41,7 @@ ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--base-ch", type=int, default=64)
 ap.add_argument("--shapes", default="20x64,12x128", help="comma-separated TxS: T frames of 2 x S x S")
 ap.add_argument("--kernel-rounds", type=int, default=9)
+ap.add_argument("--augment", action="store_true", help="time the augmenting gather kernel against the plain one, nothing else")
 ap.add_argument("--out", default=None, help="also append the table to this file")
 a = ap.parse_args()
 if a.epochs < 3:
@@ -86,6 +93,71 @@ def kernel_alone(ds, loader, T, S):
     med = statistics.median(ts)
     say(f"  gather kernel alone, cold caches, batch {a.batch}: median {med:.1f} us (min {min(ts):.1f}, max {max(ts):.1f}, "
         f"{a.kernel_rounds} rounds); {nbytes / 1e6:.1f} MB algorithmic (28 B/pixel) -> {nbytes / med / 1e3:.0f} GB/s")
+    del flush
+
+
+def augment_kernel(T, S, tmp):
+    """The augmenting kernel against the plain one at equal output bytes.  The raw arrays are random device tensors (the dataset
+    object only supplies the constants of the transform); every launch follows a 1 GiB fill, the arms alternate inside a round."""
+    path = os.path.join(tmp, f"consts_{T}x{S}.npz")
+    write_npz(path, 4, T, S)
+    ds = U.NPZSequenceDataset(path)
+    g = torch.Generator(device=dev).manual_seed(0)
+    h = S // 2
+
+    def raw(s):
+        x = torch.rand((a.n, T, 2, s, s), device=dev, generator=g) * 30
+        return x * (x >= 6), torch.randn((a.n, T, 1, s, s), device=dev, generator=g) * 2
+
+    full, half = raw(S), raw(h)
+    idx = torch.randperm(a.n, generator=torch.Generator().manual_seed(1))[:a.batch].to(dev)
+    cg = torch.Generator().manual_seed(2)
+
+    def table(codes, span):
+        t = torch.zeros((a.batch, 4), dtype=torch.int32)
+        t[:, 0] = torch.tensor(codes)[torch.randint(0, len(codes), (a.batch,), generator=cg)]
+        if span:
+            t[:, 1:3] = torch.randint(0, span // 4 + 1, (a.batch, 2), generator=cg).int() * 4
+        return t.to(dev)
+
+    out_full = tuple(torch.empty((a.batch, T, c, S, S), device=dev) for c in (2, 1, 1))
+    out_half = tuple(torch.empty((a.batch, T, c, h, h), device=dev) for c in (2, 1, 1))
+    tabs = {"no t": table((0, 1, 2, 3), 0), "t": table((4, 5, 6, 7), 0), "crop": table(tuple(range(8)), S - h)}
+    arms = {
+        f"plain {S}x{S}": lambda: E._gather_transform(ds, *full, idx, a.batch, out_full),
+        f"augment {S}x{S}, codes 0-3": lambda: E._gather_augment(ds, *full, idx, tabs["no t"], a.batch, (T, S, S), 3, out_full),
+        f"augment {S}x{S}, codes 4-7": lambda: E._gather_augment(ds, *full, idx, tabs["t"], a.batch, (T, S, S), 3, out_full),
+        f"plain {h}x{h}": lambda: E._gather_transform(ds, *half, idx, a.batch, out_half),
+        f"augment {S} -> {h} crop, codes 0-7": lambda: E._gather_augment(ds, *full, idx, tabs["crop"], a.batch, (T, h, h), 3, out_half),
+    }
+    flush = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+    st = torch.cuda.current_stream()
+    ts = {k: [] for k in arms}
+    for r in range(a.kernel_rounds + 1):
+        for name, launch in arms.items():
+            flush.fill_(1.0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            launch()
+            e1.record(st)
+            torch.cuda.synchronize()
+            if r:                               # round 0 warms up (code-object load)
+                ts[name].append(e0.elapsed_time(e1) * 1e3)
+    say(f"shape: T = {T}, 2 x {S} x {S}, batch {a.batch} of {a.n} resident sequences; cold caches, {a.kernel_rounds} rounds, us")
+    say(f"  {'arm':38s} {'median':>8s} {'min':>8s} {'max':>8s} {'GB/s':>7s}   against the plain kernel at the same output bytes")
+    base = None
+    for name, v in ts.items():
+        med = statistics.median(v)
+        side = h if (f"{h}x{h}" in name or "crop" in name) else S
+        nbytes = a.batch * T * side * side * 28                      # 12 B read + 16 B written per output pixel
+        if name.startswith("plain"):
+            base, note = v, "the yardstick"
+        else:
+            bm = statistics.median(base)
+            where = "inside" if min(base) <= med <= max(base) else ("below" if med < min(base) else "above")
+            note = f"{med / bm:.3f} x its median; {where} its min-max spread [{min(base):.1f}, {max(base):.1f}]"
+        say(f"  {name:38s} {med:8.1f} {min(v):8.1f} {max(v):8.1f} {nbytes / med / 1e3:7.0f}   {note}")
+    say()
     del flush
 
 
@@ -149,7 +221,10 @@ with tempfile.TemporaryDirectory() as tmp:
     torch.zeros(1 << 20, device=dev).sum().item()          # the HIP context and the allocator exist before the first timed upload
     for shape in a.shapes.split(","):
         T, S = (int(v) for v in shape.split("x"))
-        one_shape(T, S, tmp)
+        if a.augment:
+            augment_kernel(T, S, tmp)
+        else:
+            one_shape(T, S, tmp)
         torch.cuda.empty_cache()
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

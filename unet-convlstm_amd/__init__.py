@@ -14,7 +14,7 @@ from .modules import (ConvLSTMCell, ConvLSTM, DoubleConv, Down, Up, OutConv, Spa
                       TemporalUNetDualView, UNet)
 from .loss import compute_loss
 from .optim import FusedAdamW
-from .engine import train_one_epoch, evaluate, train_step, GraphedTrainStep, quiesce_host_gc, SyntheticSequences, NPZSequenceDataset, device_transform, EvalReport, evaluate_report, DeviceSequenceLoader, epoch_rows
+from .engine import train_one_epoch, evaluate, train_step, GraphedTrainStep, quiesce_host_gc, SyntheticSequences, NPZSequenceDataset, device_transform, EvalReport, evaluate_report, DeviceSequenceLoader, epoch_rows, Augment, epoch_augment, plane_d4, predict_tta, d4_inverse
 from .ddp import FlatDDP
 from .streaming import StreamingPredictor
 from .ops import compute_dtype, set_compute_dtype, get_compute_dtype
@@ -23,6 +23,6 @@ from .ops import sync_batchnorm, set_sync_batchnorm, get_sync_batchnorm
 
 __all__ = ["ConvLSTMCell", "ConvLSTM", "DoubleConv", "Down", "Up", "OutConv", "SpatialAttention",
            "TemporalUNetDualView", "UNet", "compute_loss", "FusedAdamW", "train_one_epoch", "evaluate",
-           "train_step", "GraphedTrainStep", "quiesce_host_gc", "SyntheticSequences", "NPZSequenceDataset", "device_transform", "EvalReport", "evaluate_report", "DeviceSequenceLoader", "epoch_rows", "FlatDDP", "StreamingPredictor", "UclstmError", "ops",
+           "train_step", "GraphedTrainStep", "quiesce_host_gc", "SyntheticSequences", "NPZSequenceDataset", "device_transform", "EvalReport", "evaluate_report", "DeviceSequenceLoader", "epoch_rows", "Augment", "epoch_augment", "plane_d4", "predict_tta", "d4_inverse", "FlatDDP", "StreamingPredictor", "UclstmError", "ops",
            "compute_dtype", "set_compute_dtype", "get_compute_dtype", "deterministic", "set_deterministic", "is_deterministic",
            "sync_batchnorm", "set_sync_batchnorm", "get_sync_batchnorm"]

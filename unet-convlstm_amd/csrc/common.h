@@ -95,6 +95,14 @@ __device__ __forceinline__ float fast_sigmoid(float x) { return 1.0f / (1.0f + _
 // 1 - 2/(e^{2x}+1): saturates correctly to +-1 for large |x|
 __device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f / (__expf(2.0f * x) + 1.0f); }
 
+// the three forward target transforms of train/unet.py:243-248 (0 none, 1 asinh, 2 signed_log = np.sign(v) * np.log1p(|v| / s)):
+// ONE definition for the plain and the augmenting dataset kernels, whose outputs must agree bit for bit
+__device__ __forceinline__ float target_fwd(float v, int transform, float inv_yscale) {
+    if (transform == 1) return asinhf(v * inv_yscale);
+    if (transform == 2) return copysignf(log1pf(fabsf(v) * inv_yscale), v);
+    return v;
+}
+
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int32_t round_up32(int32_t a, int32_t b) { return (a + b - 1) / b * b; }
 

@@ -397,13 +397,6 @@ __device__ __forceinline__ void store_px(float* __restrict__ p, const float (&r)
     }
 }
 
-// the three forward target transforms of train/unet.py:243-248 (0 none, 1 asinh, 2 signed_log = np.sign(v) * np.log1p(|v| / s))
-__device__ __forceinline__ float target_fwd(float v, int transform, float inv_yscale) {
-    if (transform == 1) return asinhf(v * inv_yscale);
-    if (transform == 2) return copysignf(log1pf(fabsf(v) * inv_yscale), v);
-    return v;
-}
-
 // NPZSequenceDataset.__getitem__ for the sequences idx[0 .. n_out) of a RAW dataset resident on the device: the arithmetic of
 // dataset_transform_kernel (plus the two other target transforms), the source frame found through the index vector.
 // A block iteration is one CHUNK = NT work items (V pixels each) of ONE output frame, so the sequence index is uniform: it is

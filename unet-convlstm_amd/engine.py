@@ -8,6 +8,7 @@ the metric block on the device as running sums instead of per-pixel Python lists
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import math
 from typing import Optional
 
@@ -186,6 +187,167 @@ def _gather_transform(ds, x_all, y_all, idx, n_out, out=None):
     return x, y, mask
 
 
+# ---------------------------------------------------------------------------------------------
+# augmentation on the device: flips, transpose, crop, time window -- every one an index remap
+# ---------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class Augment:
+    """What ``DeviceSequenceLoader(augment=...)`` draws per output sequence.  ``hflip`` / ``vflip`` / ``transpose``: each enabled
+    bit of the code is Bernoulli(1/2) (``code = h | v << 1 | t << 2``; on a frame ``s``: ``flip(-1)`` for h, then ``flip(-2)`` for
+    v, then ``transpose(-2, -1)`` for t -- together the eight elements of the dihedral group).  ``crop=(Ho, Wo)``: the OUTPUT
+    frame size, cut at an offset uniform over the positions that are multiples of ``crop_align`` and keep the window inside the
+    source (``crop_align=4`` keeps the kernel's 16-byte path when the widths are multiples of 4).  ``frames=T_out``: a window of
+    ``T_out`` consecutive frames at a uniform start.  ``transpose`` needs a square output frame.
+
+    Scalar targets only (the reference's ``MAP_TYPE = 'w'``): a vector target (horizontal velocity components) would have to
+    change sign under mirrors and swap under transposes, which the remap does not do."""
+    hflip: bool = False
+    vflip: bool = False
+    transpose: bool = False
+    crop: Optional[tuple] = None
+    frames: Optional[int] = None
+    crop_align: int = 1
+
+    def __post_init__(self):
+        if self.crop is not None:
+            crop = tuple(int(v) for v in self.crop)
+            if len(crop) != 2 or min(crop) <= 0:
+                raise ValueError(f"Augment: crop must be (Ho, Wo) with positive sizes, got {self.crop!r}")
+            object.__setattr__(self, "crop", crop)
+            if self.transpose and crop[0] != crop[1]:
+                raise ValueError(f"Augment: transpose needs a square output frame, got crop {crop}")
+        if self.frames is not None and int(self.frames) <= 0:
+            raise ValueError(f"Augment: frames must be positive, got {self.frames}")
+        if int(self.crop_align) < 1:
+            raise ValueError(f"Augment: crop_align must be at least 1, got {self.crop_align}")
+
+    @property
+    def code_mask(self) -> int:
+        return int(bool(self.hflip)) | int(bool(self.vflip)) << 1 | int(bool(self.transpose)) << 2
+
+    def output_shape(self, T: int, H: int, W: int):
+        """``(T_out, Ho, Wo)`` for a source of ``T`` frames of ``H x W``; ``ValueError`` when it does not fit."""
+        Ho, Wo = self.crop if self.crop is not None else (H, W)
+        To = T if self.frames is None else int(self.frames)
+        if Ho > H or Wo > W or To > T:
+            raise ValueError(f"Augment: output of {To} frames of {Ho} x {Wo} does not fit a source of {T} frames of {H} x {W}")
+        if self.transpose and Ho != Wo:
+            raise ValueError(f"Augment: transpose needs a square output frame, got {Ho} x {Wo}")
+        return To, Ho, Wo
+
+
+def d4_inverse(code: int) -> int:
+    """The code that undoes ``code``: a code without t is its own inverse; with t the h and v bits swap."""
+    code = int(code)
+    if not 0 <= code <= 7:
+        raise ValueError(f"code must be in 0..7, got {code}")
+    return code if not code & 4 else 4 | (code & 1) << 1 | (code & 2) >> 1
+
+
+def epoch_augment(n: int, T: int, H: int, W: int, augment: Augment, generator=None) -> np.ndarray:
+    """The table of one epoch: int32 ``[n, 4]`` rows ``{code, oy, ox, t0}``, one per output sequence -- a pure function of its
+    arguments and the generator's state.  Drawn with ``torch.randint(..., generator=generator)`` on the CPU in this order: all
+    codes (uniform over 0..7, masked to the enabled bits), then all ``oy``, then all ``ox``, then all ``t0``; a column with a
+    single possible value (a disabled option, a crop as large as the source) is zero and draws nothing.  So a seeded generator
+    reproduces an epoch, and the next call continues the stream."""
+    To, Ho, Wo = augment.output_shape(T, H, W)
+    n, align = int(n), int(augment.crop_align)
+    tab = np.zeros((n, 4), dtype=np.int32)
+    if n <= 0:
+        return tab
+
+    def draw(count):
+        return torch.randint(0, count, (n,), generator=generator).numpy().astype(np.int32)
+    if augment.code_mask:
+        tab[:, 0] = draw(8) & augment.code_mask
+    for col, count, step in ((1, (H - Ho) // align + 1, align), (2, (W - Wo) // align + 1, align), (3, T - To + 1, 1)):
+        if count > 1:
+            tab[:, col] = draw(count) * step
+    return tab
+
+
+def _gather_augment(ds, x_all, y_all, idx, aug, n_out, shape, flags, out=None):
+    """One launch of ``uclstm_dataset_gather_augment``: ``_gather_transform`` with the per-sequence remap of the device table
+    ``aug`` (int32 ``[n_out, 4]`` rows ``{code, oy, ox, t0}``).  ``shape = (T_out, Ho, Wo)`` of the output; ``flags``: bit 0 = the
+    table may hold codes with t, bit 1 = every ``ox`` is a multiple of 4.  Bit-identical to ``_gather_transform`` of the same
+    rows moved with ``torch.flip`` / ``transpose`` / slicing."""
+    from . import _lib as L
+    N, T, Cc, H, W = x_all.shape
+    To, Ho, Wo = (int(v) for v in shape)
+    aug = ops._dev(aug, torch.int32, "aug")
+    if aug.dim() != 2 or aug.shape[1] != 4 or aug.shape[0] < n_out:
+        raise L.UclstmError(f"_gather_augment: aug must be int32 [>= {n_out}, 4], got {tuple(aug.shape)}")
+    if out is None:
+        x = torch.empty((n_out, To, Cc, Ho, Wo), dtype=torch.float32, device=x_all.device)
+        y = torch.empty((n_out, To, 1, Ho, Wo), dtype=torch.float32, device=x_all.device)
+        mask = torch.empty_like(y)
+    else:
+        x, y, mask = out
+    L.check(L.lib.uclstm_dataset_gather_augment(
+        ops._p(x_all), ops._p(y_all), ops._p(idx), ops._p(aug), N, n_out, T, To, Cc, H, W, Ho, Wo, int(flags),
+        ops._p(x), ops._p(y), ops._p(mask), _TRANSFORM_IDS[ds.y_transform], float(ds.norm_const), float(ds.min_vel),
+        float(ds.max_vel), int(bool(ds.clip_outliers)), float(ds.y_scale), float(ds.trans_min), float(ds.trans_max), ops._stream()),
+        "dataset_gather_augment")
+    return x, y, mask
+
+
+def plane_d4(t: torch.Tensor, code: int, out: Optional[torch.Tensor] = None, accumulate: bool = False, scale: float = 1.0):
+    """Move the last two dims of the contiguous f32 device tensor ``t`` by ``code`` (0..7, as in ``Augment``):
+    ``out = (accumulate ? out : 0) + scale * move(t)``, one launch of ``uclstm_plane_d4``.  ``out``: ``t``'s shape, with the last
+    two dims swapped for codes with t; a fresh tensor when None (then ``accumulate`` is refused).  ``out`` must not be ``t``."""
+    from . import _lib as L
+    code = int(code)
+    t = ops._dev(t, torch.float32, "plane_d4 input")
+    if t.dim() < 2 or not 0 <= code <= 7:
+        raise ValueError(f"plane_d4: a tensor of at least 2 dims and a code in 0..7 are required, got {tuple(t.shape)}, code {code}")
+    H, W = t.shape[-2:]
+    shape = tuple(t.shape[:-2]) + ((W, H) if code & 4 else (H, W))
+    if out is None:
+        if accumulate:
+            raise ValueError("plane_d4: accumulate=True needs out=")
+        out = torch.empty(shape, dtype=torch.float32, device=t.device)
+    else:
+        ops._dev(out, torch.float32, "plane_d4 out")
+        if tuple(out.shape) != shape or out.device != t.device or out.data_ptr() == t.data_ptr():
+            raise ValueError(f"plane_d4: out must be another tensor of shape {shape} on {t.device}, got {tuple(out.shape)} on {out.device}")
+    if t.numel():
+        L.check(L.lib.uclstm_plane_d4(ops._p(t), ops._p(out), t.numel() // (H * W), H, W, code, int(bool(accumulate)), float(scale),
+                                      ops._stream()), "plane_d4")
+    return out
+
+
+_TTA_SETS = {"flips": (0, 1, 2, 3), "d4": tuple(range(8))}
+
+
+@torch.no_grad()
+def predict_tta(model, x: torch.Tensor, codes="flips", state=None) -> torch.Tensor:
+    """Test-time augmentation: the mean over ``codes`` of ``inverse move(model(move(x)))``, ``[B,T,C,H,W]`` f32.
+    ``codes``: ``"flips"`` = (0, 1, 2, 3), ``"d4"`` = all eight, or an iterable of codes.  For each code in the given order: ``x``
+    is moved with ``plane_d4``, the model runs under ``no_grad``, its frames are stacked as the epoch loops stack them, and the
+    output moved by the INVERSE code is accumulated with weight 1 / len(codes) by the same kernel (left to right in f32).
+    ``model`` is anything that returns ``(frames or tensor, state)``.  Codes with t need square frames."""
+    if isinstance(codes, str):
+        if codes not in _TTA_SETS:
+            raise ValueError(f"predict_tta: codes must be one of {sorted(_TTA_SETS)} or an iterable of codes, got {codes!r}")
+        codes = _TTA_SETS[codes]
+    codes = tuple(int(c) for c in codes)
+    if not codes or any(not 0 <= c <= 7 for c in codes):
+        raise ValueError(f"predict_tta: codes must be a non-empty sequence of values in 0..7, got {codes}")
+    if any(c & 4 for c in codes) and x.shape[-1] != x.shape[-2]:
+        raise ValueError(f"predict_tta: codes with a transpose need square frames, got {x.shape[-2]} x {x.shape[-1]}")
+    x = x.contiguous().float()
+    acc = None
+    for c in codes:
+        xc = plane_d4(x, c)
+        output, _ = model(xc) if state is None else model(xc, state)
+        y = _stack(output).contiguous().float()
+        if acc is None:
+            acc = plane_d4(y, d4_inverse(c), scale=1.0 / len(codes))
+        else:
+            plane_d4(y, d4_inverse(c), out=acc, accumulate=True, scale=1.0 / len(codes))
+    return acc
+
+
 def _root_rows(dataset):
     """``dataset`` (an ``NPZSequenceDataset`` or nested ``Subset``s of one, as ``random_split`` returns them) ->
     ``(root dataset, rows)``: ``rows[p]`` is the root's row behind position ``p`` (int64 array; None = identity)."""
@@ -234,10 +396,17 @@ class DeviceSequenceLoader:
     ``UclstmError`` -- streaming is not implemented.  The index order is the torch sampler's, iterated on the host:
     ``sampler=`` any sampler or iterable of positions (``DistributedSampler``: ``set_epoch`` stays the caller's job),
     ``shuffle=True`` = ``RandomSampler(dataset, generator=generator)``.  Per epoch the row list goes to the device as one pinned
-    int64 tensor; per batch nothing is copied and nothing synchronises."""
+    int64 tensor; per batch nothing is copied and nothing synchronises.
+
+    ``augment=Augment(...)``: every output sequence is flipped / transposed / cropped / cut in time on the way, by one launch of
+    ``uclstm_dataset_gather_augment`` per batch instead (batches are then ``[b, T_out, C, Ho, Wo]``).  Per epoch
+    ``epoch_augment`` draws one table row per POSITION from ``augment_generator`` (two positions that name the same row get
+    independent draws); the table is uploaded once next to the row list, and ``last_augment`` keeps the host copy of the current
+    epoch.  A batch is bit-identical to the plain batch moved with ``torch.flip`` / ``transpose`` / slicing.  Scalar targets only
+    (see ``Augment``).  ``augment=None`` is the plain path, launch for launch."""
 
     def __init__(self, dataset, batch_size: int, shuffle: bool = False, sampler=None, drop_last: bool = False, generator=None,
-                 device="cuda", max_resident_bytes: Optional[int] = None):
+                 device="cuda", max_resident_bytes: Optional[int] = None, augment: Optional[Augment] = None, augment_generator=None):
         self.root, _ = _root_rows(dataset)
         if batch_size <= 0:
             raise ValueError(f"batch_size must be positive, got {batch_size}")
@@ -252,6 +421,11 @@ class DeviceSequenceLoader:
             sampler = (torch.utils.data.RandomSampler(dataset, generator=generator) if shuffle
                        else torch.utils.data.SequentialSampler(dataset))
         self.sampler = sampler
+        if augment is not None and not isinstance(augment, Augment):
+            raise TypeError(f"DeviceSequenceLoader: augment must be an Augment or None, got {type(augment).__name__}")
+        self.augment, self.augment_generator, self.last_augment = augment, augment_generator, None
+        if augment is not None:
+            augment.output_shape(self.root.T, self.root.H, self.root.W)          # a crop that does not fit fails here, not mid-epoch
         self.x_all, self.y_all = self._resident(self.root, self.device, max_resident_bytes)
 
     @staticmethod
@@ -278,8 +452,11 @@ class DeviceSequenceLoader:
     def batches(self, out=None):
         """The epoch's batches.  ``out=(x, y, mask)``: every (full) batch is written into these caller-owned contiguous f32
         device buffers, which are yielded themselves -- the static inputs of a ``GraphedTrainStep``; a short last batch cannot
-        be written into them, so ``drop_last=False`` is refused when the sampler's length is no multiple of the batch."""
+        be written into them, so ``drop_last=False`` is refused when the sampler's length is no multiple of the batch.  With
+        ``augment`` the buffers have the OUTPUT shape ``(b, T_out, C, Ho, Wo)``."""
         T, Cc, H, W = self.x_all.shape[1:]
+        if self.augment is not None:
+            T, H, W = self.augment.output_shape(T, H, W)
         if out is not None:
             if not self.drop_last and len(self.sampler) % self.batch_size:
                 raise ValueError(f"batches(out=...): the last batch of {len(self.sampler)} positions in batches of "
@@ -300,9 +477,19 @@ class DeviceSequenceLoader:
         # ONE pinned int64 tensor per epoch, copied without blocking; this generator's frame keeps it alive until the epoch ends
         pinned = torch.from_numpy(np.concatenate(batches)).pin_memory()
         rows = pinned.to(self.device, non_blocking=True)
+        if self.augment is not None:
+            T, _, H, W = self.x_all.shape[1:]
+            shape = self.augment.output_shape(T, H, W)
+            self.last_augment = epoch_augment(len(pinned), T, H, W, self.augment, self.augment_generator)
+            flags = int(bool(self.augment.transpose)) | (0 if (self.last_augment[:, 2] % 4).any() else 2)
+            pinned_aug = torch.from_numpy(self.last_augment).pin_memory()          # kept alive like the rows
+            aug = pinned_aug.to(self.device, non_blocking=True)
         s = 0
         for b in [len(b) for b in batches]:
-            yield _gather_transform(self.root, self.x_all, self.y_all, rows[s:s + b], b, out)
+            if self.augment is None:
+                yield _gather_transform(self.root, self.x_all, self.y_all, rows[s:s + b], b, out)
+            else:
+                yield _gather_augment(self.root, self.x_all, self.y_all, rows[s:s + b], aug[s:s + b], b, shape, flags, out)
             s += b
         del pinned
 
@@ -489,16 +676,16 @@ def train_one_epoch(model, loader, optimizer, device, dataset_obj, use_mask=True
 
 
 @torch.no_grad()
-def evaluate(model, loader, device, dataset_obj, use_mask=True):
-    """Reference main.py:150-205."""
+def evaluate(model, loader, device, dataset_obj, use_mask=True, tta=None):
+    """Reference main.py:150-205.  ``tta``: None, or the ``codes`` of ``predict_tta`` (``"flips"``, ``"d4"``, an iterable): the
+    prediction is then the test-time-augmented mean."""
     model.eval()
     total = torch.zeros((), dtype=torch.float64, device=device)
     n = 0
     met = _Metrics(device)
     for x, y, mask in loader:
         x, y, mask = x.to(device, non_blocking=True), y.to(device, non_blocking=True), mask.to(device, non_blocking=True)
-        output, _ = model(x)
-        y_pred = _stack(output)
+        y_pred = _stack(model(x)[0]) if tta is None else predict_tta(model, x, tta)
         loss = compute_loss(y_pred, y, mask, use_mask)
         total += loss.double() * x.size(0)
         n += x.size(0)
@@ -691,13 +878,13 @@ class EvalReport:
 
 
 @torch.no_grad()
-def evaluate_report(model, loader, device, dataset_obj, use_mask=True, **report_kwargs):
+def evaluate_report(model, loader, device, dataset_obj, use_mask=True, tta=None, **report_kwargs):
     """``evaluate()``'s loop with an ``EvalReport`` fed from the same ``y_pred``: returns ``(avg_loss, mae, rmse, me, report)``.
     The first four are computed as ``evaluate`` computes them, from the same launches as the report (``report`` is the dict
     of ``EvalReport.result``).  Against a SEPARATE ``evaluate()`` pass they agree as far as ``evaluate`` agrees with itself:
     its loss and metric kernels add block partials with f64 atomics in arrival order, so two passes can differ in the last
     bits (~1e-13 relative); the report's own sums do not have that freedom.  (In deterministic mode, ``ops.deterministic()``, those
-    kernels add their block partials in a fixed order and two passes are identical.)"""
+    kernels add their block partials in a fixed order and two passes are identical.)  ``tta``: as in ``evaluate``."""
     model.eval()
     total = torch.zeros((), dtype=torch.float64, device=device)
     n = 0
@@ -705,8 +892,7 @@ def evaluate_report(model, loader, device, dataset_obj, use_mask=True, **report_
     rep = EvalReport(dataset_obj, device=device, **report_kwargs)
     for x, y, mask in loader:
         x, y, mask = x.to(device, non_blocking=True), y.to(device, non_blocking=True), mask.to(device, non_blocking=True)
-        output, _ = model(x)
-        y_pred = _stack(output)
+        y_pred = _stack(model(x)[0]) if tta is None else predict_tta(model, x, tta)
         loss = compute_loss(y_pred, y, mask, use_mask)
         total += loss.double() * x.size(0)
         n += x.size(0)
