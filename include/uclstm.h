@@ -573,6 +573,20 @@ int32_t uclstm_dataset_gather_augment(const float* x_all, const float* y_all, co
  * [n_planes][H][W], or [n_planes][W][H] for codes with t.  src and dst must not overlap.  Requires n_planes * H * W < 2^31. */
 int32_t uclstm_plane_d4(const float* src, float* dst, int64_t n_planes, int32_t H, int32_t W, int32_t code, int32_t accumulate,
                         float scale, void* stream);
+/* Moving-sprite sequences rendered on the device (digits/build_moving_mnist.py:16-47), one launch per batch.
+ * bank: uint8 [n_glyph][gh][gw]; table: int32 [n_out][D][5], rows {glyph, x0, y0, vx, vy}.  Per sequence, sprites d = 0..D-1 in
+ * order, frames t = 0..T-1: where the glyph byte g > 0 inside the box at (x, y): frame = g / 255 (a later sprite overwrites) and
+ * vmap += vx (the CURRENT vx); then x += vx, y += vy; if x < 0 or x > W - gw: vx = -vx and x is clamped into [0, W - gw]; the same
+ * for y with H - gh.  Outputs (f32, every element written, background = 0): x [n_out][T][C][H][W] = frame in every channel,
+ * y [n_out][T][1][H][W] = vmap / v_scale (an IEEE division), mask [n_out][T][1][H][W] = frame > 0 as 0 / 1, and, unless NULL,
+ * raw [n_out][T][2][H][W] = {frame, vmap} (the reference's `data` layout).  Bit-identical to the host generator.
+ * The kernel clamps what it reads from the table (the caller validates): glyph into [0, n_glyph), x0 / y0 into the frame, vx / vy
+ * into [-127, 127].  16-byte stores when W % 4 == 0 and every output pointer is 16-byte aligned, a scalar path otherwise.
+ * f32 only (no _f16 twin).  UCLSTM_E_BADARG before any launch for: a NULL bank / table / x / y / mask, gh or gw outside [1, 64],
+ * gw > W, gh > H, D outside [1, 8], T < 1, C < 1, n_glyph < 1, n_out < 1, v_scale == 0, n_out * T * H * W >= 2^31. */
+int32_t uclstm_sprites_render(const uint8_t* bank, int32_t n_glyph, int32_t gh, int32_t gw, const int32_t* table, int64_t n_out,
+                              int32_t D, int32_t T, int32_t C, int32_t H, int32_t W, float v_scale, float* x, float* y,
+                              float* mask, float* raw, void* stream);
 /* Epoch metric block of main.py:114-142 as running sums: sums[0..3] += sum|d|m, sum d^2 m, sum d m, sum m with
  * d = denormalize(y_pred) - denormalize(y) (train/unet.py:316-319, asinh transform); mask may be NULL. */
 int32_t uclstm_metric_sums(const float* y_pred, const float* y, const float* mask, double* sums, int64_t n, float y_scale,

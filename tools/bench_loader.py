@@ -17,8 +17,14 @@ events, ``--kernel-rounds`` rounds, the arms alternating inside a round), at the
 (through the LDS tile), and a crop to half the frame size (128 -> 64 at the second shape) with all eight codes -- each against the
 plain gather kernel writing the same OUTPUT bytes in the same run.
 
+``--sprites`` times the moving-sprite render kernel (``uclstm_sprites_render``) alone, same protocol, against the plain gather
+kernel writing the same OUTPUT shape in the same run (both write 16 B per pixel; the gather also reads 12), with and without the
+optional raw planes; then an epoch of ``train_one_epoch`` fed by ``render_sprites_host`` plus a pinned host-to-device copy per
+batch against one fed by ``DeviceSpriteLoader`` (same model, the arms alternating epoch by epoch).
+
     python tools/bench_loader.py [--epochs 3] [--out profiles/device_loader_ab.txt]
     python tools/bench_loader.py --augment [--out profiles/device_loader_augment_ab.txt]
+    python tools/bench_loader.py --sprites [--out profiles/sprites_ab.txt]
 """
 import argparse
 import os
@@ -42,6 +48,8 @@ ap.add_argument("--base-ch", type=int, default=64)
 ap.add_argument("--shapes", default="20x64,12x128", help="comma-separated TxS: T frames of 2 x S x S")
 ap.add_argument("--kernel-rounds", type=int, default=9)
 ap.add_argument("--augment", action="store_true", help="time the augmenting gather kernel against the plain one, nothing else")
+ap.add_argument("--sprites", action="store_true", help="time the sprite render kernel against the plain gather kernel, and an epoch "
+                "fed by the host mirror against one fed by DeviceSpriteLoader")
 ap.add_argument("--out", default=None, help="also append the table to this file")
 a = ap.parse_args()
 if a.epochs < 3:
@@ -161,6 +169,102 @@ def augment_kernel(T, S, tmp):
     del flush
 
 
+class HostSpriteLoader:
+    """The host way to the same batches: per batch the table is drawn, ``render_sprites_host`` renders it in numpy, (x, y, mask)
+    are assembled in pinned memory and copied to the device."""
+
+    def __init__(self, bank, batch, steps, T, S, seed):
+        self.bank, self.batch, self.steps, self.T, self.S = bank, batch, steps, T, S
+        self.g = torch.Generator().manual_seed(seed)
+
+    def __len__(self):
+        return self.steps
+
+    def __iter__(self):
+        K, gh, gw = self.bank.shape
+        for _ in range(self.steps):
+            tab = E.epoch_sprites(self.batch, 2, K, self.S, self.S, gh, gw, 5, self.g)
+            data = torch.from_numpy(E.render_sprites_host(self.bank, tab, self.T, self.S, self.S))
+            frame, vmap = data[:, :, 0:1], data[:, :, 1:2]
+            host = (frame.expand(-1, -1, 2, -1, -1).contiguous().pin_memory(), (vmap / 5.0).pin_memory(),
+                    (frame > 0).float().pin_memory())
+            yield tuple(t.to(dev, non_blocking=True) for t in host)
+
+
+def sprites(T, S, tmp):
+    """The render kernel against the plain gather kernel at equal output shape (cold caches, the arms alternating inside a round),
+    then the two ways to feed an epoch."""
+    path = os.path.join(tmp, f"consts_{T}x{S}.npz")
+    write_npz(path, 4, T, S)
+    ds = U.NPZSequenceDataset(path)
+    g = torch.Generator(device=dev).manual_seed(0)
+    x_all = torch.rand((a.n, T, 2, S, S), device=dev, generator=g) * 30
+    y_all = torch.randn((a.n, T, 1, S, S), device=dev, generator=g) * 2
+    idx = torch.randperm(a.n, generator=torch.Generator().manual_seed(1))[:a.batch].to(dev)
+    bank_host = U.procedural_glyphs(64, 28, seed=0)
+    bank = torch.from_numpy(bank_host).to(dev)
+    table = torch.from_numpy(E.epoch_sprites(a.batch, 2, 64, S, S, 28, 28, 5, torch.Generator().manual_seed(2))).to(dev)
+    out = tuple(torch.empty((a.batch, T, c, S, S), device=dev) for c in (2, 1, 1))
+    raw = torch.empty((a.batch, T, 2, S, S), device=dev)
+    arms = {
+        "plain gather": (lambda: E._gather_transform(ds, x_all, y_all, idx, a.batch, out), 28, 16),
+        "sprites render": (lambda: E._render_sprites(bank, table, a.batch, (T, 2, S, S), 5.0, out), 16, 16),
+        "sprites render + raw planes": (lambda: E._render_sprites(bank, table, a.batch, (T, 2, S, S), 5.0, out, raw), 24, 24),
+    }
+    flush = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+    st = torch.cuda.current_stream()
+    ts = {k: [] for k in arms}
+    for r in range(a.kernel_rounds + 1):
+        for name, (launch, _, _) in arms.items():
+            flush.fill_(1.0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            launch()
+            e1.record(st)
+            torch.cuda.synchronize()
+            if r:                               # round 0 warms up (code-object load)
+                ts[name].append(e0.elapsed_time(e1) * 1e3)
+    del flush
+    px = a.batch * T * S * S
+    say(f"shape: [{a.batch},{T},2,{S},{S}], 2 sprites of 28 x 28; cold caches, {a.kernel_rounds} rounds, us")
+    say(f"  {'arm':30s} {'median':>8s} {'min':>8s} {'max':>8s} {'MB moved':>9s} {'TB/s':>6s} {'MB written':>11s} {'TB/s':>6s}   against the plain gather kernel")
+    base = ts["plain gather"]
+    for name, v in ts.items():
+        med, (_, moved, written) = statistics.median(v), arms[name]
+        if name == "plain gather":
+            note = "the yardstick"
+        else:
+            where = "inside" if min(base) <= med <= max(base) else ("below" if med < min(base) else "above")
+            note = f"{med / statistics.median(base):.3f} x its median; {where} its min-max spread [{min(base):.1f}, {max(base):.1f}]"
+        say(f"  {name:30s} {med:8.1f} {min(v):8.1f} {max(v):8.1f} {px * moved / 1e6:9.1f} {px * moved / med / 1e6:6.2f} "
+            f"{px * written / 1e6:11.1f} {px * written / med / 1e6:6.2f}   {note}")
+    del x_all, y_all
+    # ---- an epoch fed either way
+    steps = a.n // a.batch
+    device_loader = U.DeviceSpriteLoader(bank_host, a.batch, steps, T=T, H=S, W=S, generator=torch.Generator().manual_seed(7))
+    host_loader = HostSpriteLoader(bank_host, a.batch, steps, T, S, 7)
+    torch.manual_seed(0)
+    model = U.TemporalUNetDualView(1, 1, base_ch=a.base_ch, lstm_layers=1, use_skip_lstm=True, use_attention=False).to(dev)
+    opt = U.FusedAdamW(model.parameters(), lr=1e-3, weight_decay=1e-4, max_grad_norm=1.0)
+    loaders = {"render_sprites_host + H2D": host_loader, "DeviceSpriteLoader": device_loader}
+    times = {k: [] for k in loaders}
+    for r in range(2 + a.epochs):
+        for name, loader in loaders.items():
+            t = epoch_seconds(model, loader, opt, device_loader)
+            if r >= 2:
+                times[name].append(t)
+    say(f"  epochs of {steps} steps, base_ch {a.base_ch}, bf16 ({a.epochs} timed epochs per arm, alternating, after 2 warm-up epochs each)")
+    say(f"  {'arm':30s} {'ms/step':>9s} {'min':>8s} {'max':>8s} {'frames/s':>10s}")
+    for name, v in times.items():
+        per = [t / steps * 1e3 for t in v]
+        med = statistics.median(per)
+        say(f"  {name:30s} {med:9.2f} {min(per):8.2f} {max(per):8.2f} {a.batch * T / med * 1e3:10.0f}")
+    h, d = (statistics.median(times[k]) for k in loaders)
+    say(f"  device arm / host arm = {d / h:.3f} (median epoch time)")
+    step_alone(model, opt, device_loader)
+    say()
+
+
 def step_alone(model, opt, loader):
     x, y, m = next(iter(loader))
     for _ in range(3):
@@ -223,6 +327,8 @@ with tempfile.TemporaryDirectory() as tmp:
         T, S = (int(v) for v in shape.split("x"))
         if a.augment:
             augment_kernel(T, S, tmp)
+        elif a.sprites:
+            sprites(T, S, tmp)
         else:
             one_shape(T, S, tmp)
         torch.cuda.empty_cache()

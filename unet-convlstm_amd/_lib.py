@@ -184,6 +184,7 @@ _PROTOS = {
     "uclstm_dataset_gather_transform": [_P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _I, _F, _F, _F, _P],
     "uclstm_dataset_gather_augment": [_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _I, _F, _F, _F, _P],
     "uclstm_plane_d4": [_P, _P, _L, _I, _I, _I, _I, _F, _P],
+    "uclstm_sprites_render": [_P, _I, _I, _I, _P, _L, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P],
     "uclstm_metric_sums": [_P, _P, _P, _P, _L, _F, _F, _F, _P],
     "uclstm_metric_sums_ordered_rows": [_L],
     "uclstm_metric_sums_ordered": [_P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _P],

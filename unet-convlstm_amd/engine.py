@@ -495,6 +495,259 @@ class DeviceSequenceLoader:
 
 
 # ---------------------------------------------------------------------------------------------
+# moving sprites (Moving-MNIST, digits/build_moving_mnist.py) rendered on the device
+# ---------------------------------------------------------------------------------------------
+MAX_SPRITES, MAX_GLYPH, MAX_SPRITE_SPEED = 8, 64, 127          # what uclstm_sprites_render accepts / clamps to
+
+
+def _glyph_bank(bank) -> np.ndarray:
+    """``bank`` (numpy array or CPU tensor) as a contiguous uint8 ``[n_glyph, gh, gw]`` array; ``ValueError`` otherwise."""
+    b = bank.detach().cpu().numpy() if isinstance(bank, torch.Tensor) else np.asarray(bank)
+    if b.dtype != np.uint8 or b.ndim != 3 or min(b.shape) < 1:
+        raise ValueError(f"glyph bank: expected uint8 [n_glyph, gh, gw], got {b.dtype} {tuple(b.shape)}")
+    if max(b.shape[1:]) > MAX_GLYPH:
+        raise ValueError(f"glyph bank: glyphs of {b.shape[1]} x {b.shape[2]} exceed {MAX_GLYPH} x {MAX_GLYPH}")
+    return np.ascontiguousarray(b)
+
+
+def load_idx_images(path) -> np.ndarray:
+    """An MNIST IDX image file the user already has (``train-images-idx3-ubyte``, plain or ``.gz``) as uint8
+    ``[n, rows, cols]``: big-endian header {magic 2051, n, rows, cols}, then the bytes.  Nothing is ever downloaded."""
+    import gzip
+    path = str(path)
+    with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
+        head = f.read(16)
+        if len(head) != 16:
+            raise ValueError(f"{path}: not an IDX image file (header of {len(head)} bytes)")
+        magic, n, rows, cols = (int(v) for v in np.frombuffer(head, dtype=">u4"))
+        if magic != 2051:
+            raise ValueError(f"{path}: not an IDX image file (magic {magic}, expected 2051)")
+        data = f.read(n * rows * cols + 1)
+    if len(data) != n * rows * cols:
+        raise ValueError(f"{path}: header says {n} images of {rows} x {cols}, the file holds "
+                         f"{'more' if len(data) > n * rows * cols else len(data)} bytes")
+    return np.frombuffer(data, dtype=np.uint8).reshape(n, rows, cols).copy()
+
+
+def procedural_glyphs(n: int, size: int = 28, seed: int = 0) -> np.ndarray:
+    """A built-in glyph bank, uint8 ``[n, size, size]``: per glyph three soft strokes (bumps ``1 / (1 + q)^2`` along line
+    segments) inside a margin of background, quantised to bytes with everything below 0.2 cut to 0.  IEEE basic operations
+    (+, -, *, /, min, max, floor) in f64 only and ``torch.rand`` of a seeded CPU generator for the stroke ends, so the bank is
+    identical on every host (``exp()`` and friends differ by an ulp between vector ISAs).  Tests and tools use it in place of
+    MNIST digits."""
+    n, size = int(n), int(size)
+    if n < 1 or not 8 <= size <= MAX_GLYPH:
+        raise ValueError(f"procedural_glyphs: n >= 1 and 8 <= size <= {MAX_GLYPH} are required, got n {n}, size {size}")
+    ends = torch.rand((n, 3, 4), generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float64).numpy()
+    lo, span = 0.18 * size, 0.64 * size
+    ends = lo + span * ends                                              # [n, stroke, (ax, ay, bx, by)] in pixels
+    yy, xx = np.meshgrid(np.arange(size, dtype=np.float64), np.arange(size, dtype=np.float64), indexing="ij")
+    width = 0.045 * size + 0.4
+    img = np.zeros((n, size, size), dtype=np.float64)
+    for s in range(3):
+        ax, ay, bx, by = (ends[:, s, i][:, None, None] for i in range(4))
+        ex, ey = bx - ax, by - ay
+        u = ((xx - ax) * ex + (yy - ay) * ey) / (ex * ex + ey * ey + 1e-9)
+        u = np.minimum(np.maximum(u, 0.0), 1.0)                          # the nearest point of the segment
+        dx, dy = xx - (ax + u * ex), yy - (ay + u * ey)
+        q = (dx * dx + dy * dy) / (2.0 * width * width)
+        img = np.maximum(img, 1.0 / ((1.0 + q) * (1.0 + q)))
+    img = np.where(img < 0.2, 0.0, img)
+    return np.floor(img * 255.0 + 0.5).astype(np.uint8)
+
+
+def check_sprite_table(table, n_glyph: int, H: int, W: int, gh: int, gw: int, max_speed: int = MAX_SPRITE_SPEED) -> np.ndarray:
+    """Validate a sprite table (integer ``[n, D, 5]`` rows ``{glyph, x0, y0, vx, vy}``) before anything is uploaded and return
+    it as a contiguous int32 array.  ``ValueError`` for a wrong shape or dtype, ``D`` outside 1..8, a glyph outside
+    ``[0, n_glyph)``, ``x0`` outside ``[0, W - gw]``, ``y0`` outside ``[0, H - gh]`` or a speed above ``max_speed`` (at most
+    127, the kernel's own clamp).  The kernel clamps the same quantities, so a bad table is never a wild access -- this
+    function is what refuses it."""
+    t = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    if t.dtype.kind not in "iu" or t.ndim != 3 or t.shape[2] != 5:
+        raise ValueError(f"sprite table: expected integers [n, D, 5], got {t.dtype} {tuple(t.shape)}")
+    if not 1 <= t.shape[1] <= MAX_SPRITES:
+        raise ValueError(f"sprite table: D must be in 1..{MAX_SPRITES}, got {t.shape[1]}")
+    if gw > W or gh > H or not 0 <= int(max_speed) <= MAX_SPRITE_SPEED:
+        raise ValueError(f"sprite table: glyphs of {gh} x {gw} must fit the {H} x {W} frame and max_speed be in "
+                         f"0..{MAX_SPRITE_SPEED}, got {max_speed}")
+    t64 = t.astype(np.int64)
+    for col, name, lo, hi in ((0, "glyph", 0, int(n_glyph) - 1), (1, "x0", 0, W - gw), (2, "y0", 0, H - gh),
+                              (3, "vx", -int(max_speed), int(max_speed)), (4, "vy", -int(max_speed), int(max_speed))):
+        bad = (t64[..., col] < lo) | (t64[..., col] > hi)
+        if bad.any():
+            i, d = (int(v[0]) for v in np.nonzero(bad))
+            raise ValueError(f"sprite table: {name} = {int(t64[i, d, col])} of sequence {i}, sprite {d} is outside [{lo}, {hi}]")
+    return np.ascontiguousarray(t64.astype(np.int32))
+
+
+def epoch_sprites(n: int, D: int, n_glyph: int, H: int, W: int, gh: int, gw: int, max_speed: int = 5, generator=None) -> np.ndarray:
+    """The sprite table of one epoch: int32 ``[n, D, 5]`` rows ``{glyph, x0, y0, vx, vy}`` -- a pure function of its arguments
+    and the generator's state.  Drawn with ``torch.randint(..., (n, D), generator=generator)`` on the CPU in this order: all
+    glyph indices (uniform over ``[0, n_glyph)``), then all ``x0`` (uniform over ``[0, W - gw]``), then all ``y0``
+    (``[0, H - gh]``), then all ``vx``, then all ``vy`` (uniform integers in ``[-max_speed, max_speed]``; the reference uses
+    5, build_moving_mnist.py:17-21).  A column with a single possible value (``W == gw``, one glyph, ``max_speed == 0``) is
+    that value and draws nothing.  So a seeded generator reproduces an epoch, and the next call continues the stream."""
+    n, D, max_speed = int(n), int(D), int(max_speed)
+    if not 1 <= D <= MAX_SPRITES or n_glyph < 1 or gw > W or gh > H or min(gh, gw) < 1 or not 0 <= max_speed <= MAX_SPRITE_SPEED:
+        raise ValueError(f"epoch_sprites: D in 1..{MAX_SPRITES}, n_glyph >= 1, glyphs that fit the frame and max_speed in "
+                         f"0..{MAX_SPRITE_SPEED} are required, got D {D}, n_glyph {n_glyph}, {gh} x {gw} in {H} x {W}, speed {max_speed}")
+    tab = np.zeros((max(n, 0), D, 5), dtype=np.int32)
+    if n <= 0:
+        return tab
+    for col, lo, count in ((0, 0, int(n_glyph)), (1, 0, W - gw + 1), (2, 0, H - gh + 1), (3, -max_speed, 2 * max_speed + 1),
+                           (4, -max_speed, 2 * max_speed + 1)):
+        if count > 1:
+            tab[:, :, col] = torch.randint(0, count, (n, D), generator=generator).numpy().astype(np.int32) + lo
+    return tab
+
+
+def render_sprites_host(bank, table, T: int, H: int, W: int) -> np.ndarray:
+    """Host mirror of ``uclstm_sprites_render`` in numpy: f32 ``[n, T, 2, H, W]``, channel 0 the frame and channel 1 the raw
+    velocity map -- the ``data`` array of the reference's ``generate_moving_mnist`` (digits/build_moving_mnist.py:5-58) for the
+    draws recorded in ``table``, for any frame and glyph size.  Per sequence, sprites in table order, frames in time order:
+    where the glyph byte is non-zero the frame takes ``byte / 255`` (a later sprite overwrites) and the map adds the sprite's
+    current ``vx``; then the sprite moves, and a position outside ``[0, W - gw]`` / ``[0, H - gh]`` flips that velocity
+    component and is clamped.  Vectorised over sequences and glyph pixels; the table is validated first."""
+    bank = _glyph_bank(bank)
+    K, gh, gw = bank.shape
+    tab = check_sprite_table(table, K, H, W, gh, gw).astype(np.int64)
+    n, D = tab.shape[:2]
+    out = np.zeros((n, int(T), 2, H, W), dtype=np.float32)
+    level = (np.arange(256, dtype=np.float64) / 255.0).astype(np.float32)       # build_moving_mnist.py:26, stored as f32 (:10)
+    for d in range(D):
+        glyph = bank[tab[:, d, 0]]                                               # [n, gh, gw]
+        ni, ri, ci = np.nonzero(glyph)                                           # the covered pixels, the same in every frame
+        value = level[glyph[ni, ri, ci]]
+        px, py, vx, vy = (tab[:, d, c].copy() for c in (1, 2, 3, 4))
+        for t in range(int(T)):
+            out[ni, t, 0, py[ni] + ri, px[ni] + ci] = value
+            out[ni, t, 1, py[ni] + ri, px[ni] + ci] += vx[ni].astype(np.float32)
+            px, py = px + vx, py + vy
+            hit = (px < 0) | (px > W - gw)
+            vx = np.where(hit, -vx, vx)
+            px = np.clip(px, 0, W - gw)
+            hit = (py < 0) | (py > H - gh)
+            vy = np.where(hit, -vy, vy)
+            py = np.clip(py, 0, H - gh)
+    return out
+
+
+def _render_sprites(bank, table, n_out, shape, v_scale, out=None, raw=None):
+    """One launch of ``uclstm_sprites_render``: device ``bank`` (uint8 ``[n_glyph, gh, gw]``) and ``table`` (int32
+    ``[>= n_out, D, 5]``) -> ``(x [n_out,T,C,H,W], y, mask [n_out,T,1,H,W])``; ``shape = (T, C, H, W)``.  ``out``: caller-owned
+    ``(x, y, mask)`` to write into, fresh tensors on the current stream otherwise; ``raw``: an optional ``[n_out,T,2,H,W]``
+    buffer for the reference's ``data`` layout.  Nothing is pre-zeroed: the kernel writes every element."""
+    from . import _lib as L
+    T, Cc, H, W = (int(v) for v in shape)
+    if not (isinstance(bank, torch.Tensor) and bank.is_cuda and bank.dtype == torch.uint8 and bank.dim() == 3 and bank.is_contiguous()):
+        raise L.UclstmError("_render_sprites: bank must be a contiguous uint8 [n_glyph, gh, gw] HIP device tensor")
+    table = ops._dev(table, torch.int32, "sprite table")
+    if table.dim() != 3 or table.shape[2] != 5 or table.shape[0] < n_out or table.device != bank.device:
+        raise L.UclstmError(f"_render_sprites: table must be int32 [>= {n_out}, D, 5] on {bank.device}, got {tuple(table.shape)}")
+    if out is None:
+        x = torch.empty((n_out, T, Cc, H, W), dtype=torch.float32, device=bank.device)
+        y = torch.empty((n_out, T, 1, H, W), dtype=torch.float32, device=bank.device)
+        mask = torch.empty_like(y)
+    else:
+        x, y, mask = out
+    for t, want, what in ((x, (n_out, T, Cc, H, W), "x"), (y, (n_out, T, 1, H, W), "y"), (mask, (n_out, T, 1, H, W), "mask"),
+                          (raw, (n_out, T, 2, H, W), "raw")):
+        if t is None and what == "raw":
+            continue
+        ops._dev(t, torch.float32, what)
+        if tuple(t.shape) != want or t.device != bank.device:
+            raise L.UclstmError(f"_render_sprites: {what} must be {want} on {bank.device}, got {tuple(t.shape)} on {t.device}")
+    L.check(L.lib.uclstm_sprites_render(ops._p(bank), bank.shape[0], bank.shape[1], bank.shape[2], ops._p(table), n_out,
+                                        table.shape[1], T, Cc, H, W, float(v_scale), ops._p(x), ops._p(y), ops._p(mask),
+                                        ops._p(raw), ops._stream()), "sprites_render")
+    return x, y, mask
+
+
+class DeviceSpriteLoader:
+    """An endless Moving-MNIST source (digits/build_moving_mnist.py) that behaves like a ``DataLoader``: every batch is
+    RENDERED on the GPU by one launch of ``uclstm_sprites_render`` -- no file, no host arithmetic, no host-to-device copy of
+    pixels.  Yields ``(x [b,T,C,H,W], y [b,T,1,H,W], mask [b,T,1,H,W])`` as fresh f32 device tensors on the current stream:
+    ``x`` is the frame in every channel (both "satellite" views see the same scene, as ``SyntheticSequences(kind="blobs")``
+    has it), ``y`` the per-pixel map of summed horizontal velocities over ``v_scale``, ``mask`` the sprite pixels.
+
+    ``bank``: uint8 ``[n_glyph, gh, gw]`` glyphs (``load_idx_images`` of an MNIST file, ``procedural_glyphs``), uploaded once.
+    ``len()`` is ``steps_per_epoch``.  Each epoch draws ONE table for ``steps_per_epoch * batch_size`` sequences with
+    ``epoch_sprites(..., generator)``, validates it (``check_sprite_table``) and uploads it as one pinned int32 tensor;
+    ``last_table`` keeps the host copy, and ``render_sprites_host(bank, last_table, T, H, W)`` is the epoch bit for bit.  Per
+    batch nothing is copied and nothing synchronises.  ``fixed=True`` draws the table once at construction: every epoch is
+    then the same set -- a validation set.
+
+    It also stands in for the ``dataset_obj`` of ``train_one_epoch`` / ``evaluate`` / ``EvalReport``: ``y_transform = None``,
+    ``y_scale = 1.0``, ``trans_min = -v_scale``, ``trans_max = +v_scale`` and ``denormalize(y) = y * v_scale`` (pixels per
+    frame), so ``train_one_epoch(model, loader, opt, dev, loader)`` runs unchanged.
+
+    Under ``FlatDDP`` every rank constructs its own loader and passes its OWN seeded generator (for instance
+    ``torch.Generator().manual_seed(seed + rank)``): ranks that share a seed would render the same sequences."""
+
+    y_transform = None
+    y_scale = 1.0
+
+    def __init__(self, bank, batch_size: int, steps_per_epoch: int, T: int = 20, H: int = 64, W: int = 64, num_sprites: int = 2,
+                 max_speed: int = 5, channels: int = 2, v_scale: float = 5.0, generator=None, fixed: bool = False, device="cuda"):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ops.L.UclstmError(f"DeviceSpriteLoader: a HIP device is required, got {dev} (this package has no CPU path)")
+        host = _glyph_bank(bank)
+        self.batch_size, self.steps_per_epoch = int(batch_size), int(steps_per_epoch)
+        self.T, self.H, self.W, self.channels = int(T), int(H), int(W), int(channels)
+        self.num_sprites, self.max_speed, self.v_scale = int(num_sprites), int(max_speed), float(v_scale)
+        if self.batch_size <= 0 or self.steps_per_epoch <= 0 or self.T < 1 or self.channels < 1 or not self.v_scale > 0.0:
+            raise ValueError("DeviceSpriteLoader: batch_size, steps_per_epoch, T, channels and v_scale must be positive")
+        epoch_sprites(0, self.num_sprites, host.shape[0], self.H, self.W, host.shape[1], host.shape[2], self.max_speed)   # validates
+        self.trans_min, self.trans_max = -self.v_scale, self.v_scale
+        self.generator, self.fixed, self.last_table = generator, bool(fixed), None
+        self.device = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+        self.bank_host = host
+        self.bank = torch.from_numpy(host).to(self.device)
+        self._fixed = self._draw() if self.fixed else None
+
+    def _draw(self):
+        """Draw, validate and upload one epoch's table: (pinned host tensor, device tensor)."""
+        K, gh, gw = self.bank_host.shape
+        tab = epoch_sprites(self.steps_per_epoch * self.batch_size, self.num_sprites, K, self.H, self.W, gh, gw, self.max_speed,
+                            self.generator)
+        self.last_table = check_sprite_table(tab, K, self.H, self.W, gh, gw, self.max_speed)
+        pinned = torch.from_numpy(self.last_table).pin_memory()
+        return pinned, pinned.to(self.device, non_blocking=True)
+
+    def denormalize(self, y_norm):
+        """``y * v_scale``: summed horizontal velocity in pixels per frame (numpy or torch, any device)."""
+        return y_norm * self.v_scale
+
+    def __len__(self):
+        return self.steps_per_epoch
+
+    def __iter__(self):
+        return self.batches()
+
+    def batches(self, out=None):
+        """The epoch's batches.  ``out=(x, y, mask)``: every batch is rendered into these caller-owned contiguous f32 device
+        buffers, which are yielded themselves -- the static inputs of a ``GraphedTrainStep``."""
+        b, shape = self.batch_size, (self.T, self.channels, self.H, self.W)
+        if out is not None:
+            want = ((b, self.T, self.channels, self.H, self.W), (b, self.T, 1, self.H, self.W), (b, self.T, 1, self.H, self.W))
+            if len(out) != 3:
+                raise ValueError("batches(out=...): expected (x, y, mask)")
+            for t, w, what in zip(out, want, ("out x", "out y", "out mask")):
+                ops._dev(t, torch.float32, what)
+                if tuple(t.shape) != w or t.device != self.device:
+                    raise ValueError(f"batches(out=...): {what} must be {w} on {self.device}, got {tuple(t.shape)} on {t.device}")
+        return self._run(out, b, shape)
+
+    def _run(self, out, b, shape):
+        # ONE pinned int32 tensor per epoch, copied without blocking; this generator's frame keeps it alive until the epoch ends
+        pinned, table = self._fixed if self.fixed else self._draw()
+        for s in range(self.steps_per_epoch):
+            yield _render_sprites(self.bank, table[s * b:(s + 1) * b], b, shape, self.v_scale, out)
+        del pinned
+
+
+# ---------------------------------------------------------------------------------------------
 # step / epoch loops
 # ---------------------------------------------------------------------------------------------
 def _stack(output):
