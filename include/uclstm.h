@@ -155,7 +155,7 @@ typedef struct {
     uclstm_seg seg[4];
     float* dwp;
     int32_t splits;
-    int32_t accumulate;
+    int32_t accumulate; /* reserved: no kernel reads it.  Atomic mode (slab == 0) always ADDS to dwp, slab mode always STORES */
     int32_t overlapped; /* != 0: the launch runs beside other GEMMs (side stream): the automatic range count (splits = 0) then
                          * minimises interference (few slabs, grid below the CU count) instead of the kernel's own duration */
     int32_t reserved_;

@@ -784,3 +784,94 @@ def test_igemm_forward_contracts_are_checked_before_launch():
     assert blocks(ok * 2) == -1                                          # more than four members
     for K in (L.lib, L.lib16):
         assert K.uclstm_igemm_fwd_group((L.IgemmDesc * 4)(*(ok + [IC.dummy_desc(plan["A-k0-s2"])])), 4, None) == -1
+
+
+# ---------------------------------------------------------------------------------------------
+# the f64 reference, the dispatch plan and the argument contracts of tests/test_gpu_wgrad_abi.py
+# ---------------------------------------------------------------------------------------------
+def _autograd_panel(c, xs, dys):
+    """f64 weight-gradient panel [N][Ktot] of a tests/wgrad_cases.py case from torch autograd on sum(op(x, w) * dy), placed with
+    igemm_cases.host_panel.  Sources are put on the pixel frame with F.pad (a negative pad crops); dY comes from plain slices."""
+    import torch.nn.functional as F
+    import igemm_cases as IC
+    nchw = lambda t: t.permute(0, 3, 1, 2)
+    if c.kind == "convt":
+        x, du = nchw(xs[0]), nchw(dys[0])
+        Ci, Cop = x.shape[1], du.shape[1]
+        w = torch.zeros(Ci, Cop, 2, 2, dtype=torch.float64, requires_grad=True)
+        (F.conv_transpose2d(x, w, stride=2) * du).sum().backward()
+        return IC.host_panel(w.grad.permute(2, 3, 1, 0).reshape(4 * Cop, Ci, 1, 1), [Ci], 1, c.N)       # row (ty*2 + tx)*Cop + co
+    hh, ww = (c.H - 1) * c.scale + c.ktap, (c.W - 1) * c.scale + c.ktap       # frame rows / columns -pad ... that the taps reach
+    frame = []
+    for x, (_, Hs, Ws, offY, offX) in zip(xs, c.srcs):
+        top, left = c.pad + offY, c.pad + offX
+        frame.append(F.pad(nchw(x), [left, ww - left - Ws, top, hh - top - Hs]))
+    dy = torch.zeros(c.n_img, c.N, c.H, c.W, dtype=torch.float64)
+    for n0, n1, ti, c_off, sc, oy, ox in c.segments():
+        assert (sc, oy, ox) == (1, 0, 0)
+        dy[:, n0:n1] = nchw(dys[ti])[:, c_off:c_off + n1 - n0]
+    cs = [s[0] for s in c.srcs]
+    w = torch.zeros(c.N, sum(cs), c.ktap, c.ktap, dtype=torch.float64, requires_grad=True)
+    (F.conv2d(torch.cat(frame, 1), w, stride=c.scale) * dy).sum().backward()
+    return IC.host_panel(w.grad, cs, c.ktap, c.N)
+
+
+def test_wgrad_f64_reference_equals_pytorch_autograd():
+    """The host reference of the direct weight-gradient tests against f64 autograd: 3x3 with one and two sources, padded (F.pad)
+    and cropped second source, ConvTranspose2d (four scale-2 dY segments, also with a row tile that spans segments), 5x5 / 7x7,
+    the scale-2 gather, dY as channel slices of wider tensors with uncovered rows, two segments, the gate convolution over
+    cat(x, h), 1x1 and an image smaller than a stage.  Valid elements agree to 1e-12; padding elements are exactly 0."""
+    import igemm_cases as IC
+    import wgrad_cases as WC
+    for name in WC.AUTOGRAD_CASES:
+        c = WC.case(name)
+        xs, dys = WC.make_operands(c, torch.float64)
+        ref, mag = WC.case_ref(c, xs, dys)
+        want = _autograd_panel(c, xs, dys)
+        assert ref.shape == want.shape == (c.N, c.Ktot), name
+        # padding: K columns beyond a source's channels, rows that no segment covers
+        valid = IC.host_panel(torch.ones(c.N, sum(s[0] for s in c.srcs), c.ktap, c.ktap, dtype=torch.float64), [s[0] for s in c.srcs],
+                              c.ktap, c.N) != 0
+        covered = torch.zeros(c.N, dtype=torch.bool)
+        for n0, n1, *_ in c.segments():
+            covered[n0:n1] = True
+        valid &= covered[:, None]
+        assert int(valid.sum()) == sum(n1 - n0 for n0, n1, *_ in c.segments()) * c.ktap ** 2 * sum(s[0] for s in c.srcs), name
+        assert bool((ref[~valid] == 0).all()) and bool((mag[~valid] == 0).all()) and bool((want[~valid] == 0).all()), name
+        assert bool((mag[valid] > 0).all()) and bool((mag >= ref.abs() * (1 - 1e-12)).all()), name
+        torch.testing.assert_close(ref[valid], want[valid], rtol=1e-12, atol=1e-12, msg=lambda m: f"{name}: {m}")
+
+
+def test_wgrad_parity_cases_dispatch_plan_and_rejected_descriptors():
+    """Every case of tests/test_gpu_wgrad_abi.py reaches the kernel it is meant for (validation-only entry points, dummy aligned
+    pointers), both tiles of the C_out <= 64 kernel are taken, and the broken descriptors are refused by the query."""
+    import wgrad_cases as WC
+    names = [c.name for c in WC.ALL_CASES]
+    assert len(set(names)) == len(names)
+    for c in WC.ALL_CASES:
+        d = WC.build_wgrad_desc(c)
+        assert WC.wgrad_shape(d) == c.shape, c.name
+        assert WC.wgrad_splits(d) >= 1, c.name
+        assert c.M * c.N * c.Ktot <= 4e9, c.name
+    assert {c.shape for c in WC.ALL_CASES} == {0, 1, 2, 3, 4}
+    assert set(WC.MODE_CASES) == {0, 1, 2, 3} and all(WC.case(n).shape == k for k, n in WC.MODE_CASES.items())
+    # 64 x 192 when 192 | Ktot (every 3x3 gradient: Ktot = 576 * chunks), else 64 x 256
+    assert {c.name: c.Ktot % 192 == 0 for c in WC.P64_CASES} == {
+        "W1-576": True, "W1-two-1152": True, "W1-two-k1-128": False, "W1-c64": True, "W1-k1": False, "W1-small-image": True,
+        "W1-lstm16": True}
+    # generic addressing: both instantiations (PLAIN = every operand dense on the output grid)
+    plain = lambda c: c.scale == 1 and all(s[1:] == (c.H, c.W, 0, 0) for s in c.srcs) and \
+        all(t[1:] == (c.H, c.W) for t in c.dy_tensors()) and all(s[4:] == (1, 0, 0) for s in c.segments())
+    assert {plain(c) for c in WC.GENERIC_CASES} == {True, False}
+    # the ring kernel needs slab mode: with slab = 0 the same descriptor goes where the case says
+    for c in WC.RING_CASES:
+        assert WC.wgrad_shape(WC.build_wgrad_desc(c, slab=0)) == c.atomic_shape != 4, c.name
+        grid = WC.wgrad_splits(WC.build_wgrad_desc(c))
+        assert WC.wgrad_splits(WC.build_wgrad_desc(c, splits=grid + 1)) == grid
+    # the power-of-two image with two dY segments would be a fast-path case with one
+    c = WC.case("W0-pow2-nseg2")
+    d = WC.build_wgrad_desc(c)
+    d.nseg, d.seg[0].n_end, d.seg[0].C = 1, 24, 24
+    assert WC.wgrad_shape(d) == 1
+    for what, d in WC.rejected_descriptors():
+        assert WC.wgrad_splits(d) == -1 and WC.wgrad_shape(d) == -1, what
