@@ -875,3 +875,255 @@ def test_wgrad_parity_cases_dispatch_plan_and_rejected_descriptors():
     assert WC.wgrad_shape(d) == 1
     for what, d in WC.rejected_descriptors():
         assert WC.wgrad_splits(d) == -1 and WC.wgrad_shape(d) == -1, what
+
+
+# ---------------------------------------------------------------------------------------------
+# the f64 references, the planted inputs and the argument contracts of tests/test_gpu_boundary_abi.py
+# ---------------------------------------------------------------------------------------------
+def test_boundary_layout_and_im2col_references_equal_pytorch():
+    """nchw <-> nhwc against permute (time-major order through a transposed view) and the first-layer gather against F.unfold,
+    in f64, exactly; pad channels / pad taps exactly zero.  The over-the-cap shapes are left to the GPU test."""
+    import torch.nn.functional as F
+    import boundary_cases as BC
+    for case in BC.LAYOUT_CASES:
+        if case in BC.LAYOUT_OVER_CAP:
+            continue
+        n_img, Cc, Cp, H, W, inner = case
+        x = BC.layout_input(case, torch.bfloat16).double()
+        x = torch.where(torch.isfinite(x), x, torch.zeros_like(x))
+        ordered = x.view(inner, n_img // inner, Cc, H, W).transpose(0, 1).reshape(n_img, Cc, H, W)
+        got = BC.nchw_to_nhwc_ref(x, Cp, inner)
+        assert torch.equal(got, F.pad(ordered.permute(0, 2, 3, 1), (0, Cp - Cc))), case
+        assert torch.equal(BC.nhwc_to_nchw_ref(got, Cc), ordered), case
+        assert BC.layout_strides(case) == (inner, Cc * H * W, (n_img // inner) * Cc * H * W)
+    for n_img, Cc, Cp, H, W in BC.LAYOUT_F32_CASES[:3]:
+        x = torch.randn(n_img, Cc, H, W, dtype=torch.float64)
+        got = BC.nchw_to_nhwc_ref(x, Cp)
+        assert torch.equal(got, F.pad(x.permute(0, 2, 3, 1), (0, Cp - Cc))) and torch.equal(BC.nhwc_to_nchw_ref(got, Cc), x)
+    for case in BC.IM2COL_CASES:
+        if case in BC.IM2COL_OVER_CAP:
+            continue
+        n_img, Cc, Kp, H, W, inner = case
+        BC.manual_seed(7, *case)
+        x = torch.randn(n_img, Cc, H, W, dtype=torch.float64)
+        ordered = x.view(inner, n_img // inner, Cc, H, W).transpose(0, 1).reshape(n_img, Cc, H, W)
+        cols = F.unfold(ordered, 3, padding=1).view(n_img, Cc, 9, H, W).permute(0, 3, 4, 2, 1).reshape(n_img, H, W, 9 * Cc)
+        assert torch.equal(BC.im2col_ref(x, Kp, inner), F.pad(cols, (0, Kp - 9 * Cc))), case
+    # C = 3, 5, 7: a tap boundary inside an 8-element chunk; one-row and one-column images
+    assert {c[1] for c in BC.IM2COL_CASES} >= {1, 2, 3, 5, 7} and any(c[3] == 1 for c in BC.IM2COL_CASES) and any(c[4] == 1 for c in BC.IM2COL_CASES)
+
+
+def test_boundary_maxpool_reference_equals_pytorch_autograd():
+    """Both directions against F.max_pool2d and its autograd in f64 (ATen routes a tie to the first element in scan order), with and
+    without the fused second gradient, on inputs that hold every non-empty subset of the four window positions as the set of
+    maximal elements, in the windows and channels the pattern table names."""
+    import torch.nn.functional as F
+    import boundary_cases as BC
+    nchw = lambda t: t.permute(0, 3, 1, 2)
+    for case in BC.MAXPOOL_CASES:
+        if case in BC.MAXPOOL_OVER_CAP:
+            continue
+        for dtype in (torch.bfloat16, torch.float16):
+            n_img, H, W, Cp = case
+            a = BC.maxpool_input(case, dtype).double()
+            # the planted sets are the sets of maximal elements
+            w = BC.windows(a)
+            pat = BC.maxpool_pattern(case)
+            at_max = sum((w[k] == w.max(0).values).long() << k for k in range(4))
+            assert bool((at_max[pat != 0] == pat[pat != 0]).all()), case
+            want_patterns = set(range(1, 16)) if pat.numel() >= 16 else set(range(1, pat.numel()))
+            assert set(at_max.flatten().tolist()) >= want_patterns, case
+            p, best = BC.maxpool_ref(a)
+            dp = torch.randn(p.shape, dtype=torch.float64)
+            leaf = nchw(a).clone().requires_grad_(True)
+            pooled = F.max_pool2d(leaf, 2)
+            (pooled * nchw(dp)).sum().backward()
+            assert torch.equal(nchw(p), pooled.detach()), case
+            da, written = BC.maxpool_bwd_ref(a, dp)
+            assert torch.equal(nchw(da), leaf.grad), case
+            assert int(written.sum()) == n_img * (H // 2) * (W // 2) * 4 and bool((da[~written] == 0).all())
+            if case in BC.MAXPOOL_ADD_CASES:
+                add = torch.randn(a.shape, dtype=torch.float64)
+                da2, written2 = BC.maxpool_bwd_ref(a, dp, add)
+                assert bool(written2.all()) and torch.equal(da2, add + da)
+    assert all(c[1] % 2 == 0 and c[2] % 2 == 0 for c in BC.MAXPOOL_ADD_CASES) and len(BC.MAXPOOL_ADD_CASES) == 3
+    assert {(c[1] % 2, c[2] % 2) for c in BC.MAXPOOL_CASES} == {(0, 0), (1, 0), (0, 1), (1, 1)}
+
+
+def test_boundary_outconv_reference_equals_pytorch_autograd():
+    """y, da, dw and db against F.conv2d with a 1x1 kernel and its autograd in f64; the magnitudes bound the values; the lane table
+    and the chain lengths of the forward bound."""
+    import torch.nn.functional as F
+    import boundary_cases as BC
+    small = lambda c: c[0] * c[1] <= 4096
+    for case in [c for c in BC.OUTCONV_FWD_CASES + BC.OUTCONV_DA_CASES if small(c)] + [c + (None,) for c in BC.OUTCONV_DW_CASES if small(c)]:
+        n_img, HW, Cc, Cp, Co = case[:5]
+        a, w, b, dy = BC.outconv_operands(case, torch.bfloat16)
+        assert bool((a[:, Cc:] == 0).all())
+        leaf_a = a.double().view(n_img, HW, 1, Cp).permute(0, 3, 1, 2)[:, :Cc].clone().requires_grad_(True)
+        leaf_w, leaf_b = w.double()[:, :, None, None].clone().requires_grad_(True), b.double().clone().requires_grad_(True)
+        y = F.conv2d(leaf_a, leaf_w, leaf_b)
+        (y * dy.double().view(n_img, Co, HW, 1)).sum().backward()
+        ref_y, mag_y = BC.outconv_fwd_ref(a, w, b, n_img, HW)
+        torch.testing.assert_close(ref_y, y.detach().view(n_img, Co, HW), rtol=1e-12, atol=1e-12)
+        ref_nb, mag_nb = BC.outconv_fwd_ref(a, w, None, n_img, HW)
+        torch.testing.assert_close(ref_nb + b.double()[None, :, None], ref_y, rtol=1e-12, atol=1e-12)
+        da, da_mag, dw, dw_terms, db, db_terms = BC.outconv_bwd_ref(a, w, dy, Cp)
+        torch.testing.assert_close(da[:, :Cc], leaf_a.grad.permute(0, 2, 3, 1).reshape(n_img * HW, Cc), rtol=1e-12, atol=1e-12)
+        torch.testing.assert_close(dw, leaf_w.grad[:, :, 0, 0], rtol=1e-12, atol=1e-12)
+        torch.testing.assert_close(db, leaf_b.grad, rtol=1e-12, atol=1e-12)
+        assert bool((da[:, Cc:] == 0).all()) and bool((da_mag[:, Cc:] == 0).all())
+        for v, m in ((ref_y, mag_y), (da, da_mag), (dw, dw_terms), (db, db_terms)):
+            assert bool((m >= v.abs() * (1 - 1e-12)).all())
+    assert [BC.outconv_lanes(Cp) for Cp in (8, 16, 24, 32, 64, 128, 200, 256, 512)] == [0, 2, 0, 4, 8, 16, 0, 32, 0]
+    assert BC.outconv_fwd_chain(12, 16) == 10 and BC.outconv_fwd_chain(250, 256) == 14 and BC.outconv_fwd_chain(200, 200) == 201
+    assert [BC.outconv_dw_blocks(c[0] * c[1]) for c in BC.OUTCONV_DW_CASES] == [1, 3, 1, 1, 1024]
+    assert sum(c[5] is False for c in BC.OUTCONV_FWD_CASES) == 2 and \
+        {BC.outconv_lanes(c[3]) > 0 for c in BC.OUTCONV_FWD_CASES if not c[5]} == {True, False}
+
+
+def test_boundary_attention_reference_equals_the_oracle_autograd():
+    """out, dx and dw against oracle.unet_oracle.spatial_attention and its autograd in f64 (torch.max(dim=1) routes the gradient to
+    the first maximal channel), and the planted ties are where the table says: the first of the tied channels is the arg-max."""
+    import boundary_cases as BC
+    from oracle import unet_oracle as O
+    kinds = set()
+    for case in BC.ATTN_CASES:
+        if case[0] * case[1] * case[2] > 1024:
+            continue
+        n_img, H, W, Cc, Cp, k = case
+        x, planted = BC.attn_input(case, torch.bfloat16)
+        assert bool((x[..., Cc:] == 0).all())
+        w = BC.attn_weight(case).double()
+        dout = torch.randn(n_img, H, W, Cp, dtype=torch.float64)
+        fwd = BC.attn_fwd_ref(x, w, Cc)
+        bwd = BC.attn_bwd_ref(x, dout, w, Cc, fwd)
+        arg, mx = fwd["arg"].view(-1), fwd["max"].view(-1)
+        for pix, (kind, first) in planted.items():
+            kinds.add(kind)
+            if first is None:
+                assert mx[pix] < 0 and bool((x.view(-1, Cp)[pix, Cc:] == 0).all()) and Cp > Cc, (case, kind)
+            else:
+                assert int(arg[pix]) == first and int((x.view(-1, Cp)[pix, :Cc] == mx[pix]).sum()) == 2, (case, kind)
+        leaf = x.double().permute(0, 3, 1, 2)[:, :Cc].clone().requires_grad_(True)
+        leaf_w = w[None].clone().requires_grad_(True)
+        out = O.spatial_attention(leaf, {"sa.conv.weight": leaf_w}, "sa")
+        (out * dout.permute(0, 3, 1, 2)[:, :Cc]).sum().backward()
+        torch.testing.assert_close(fwd["out"][..., :Cc], out.detach().permute(0, 2, 3, 1), rtol=1e-12, atol=1e-12)
+        torch.testing.assert_close(bwd["dx"][..., :Cc], leaf.grad.permute(0, 2, 3, 1), rtol=1e-11, atol=1e-11)
+        torch.testing.assert_close(bwd["dw"], leaf_w.grad[0], rtol=1e-11, atol=1e-11)
+        assert bool((bwd["dx"][..., Cc:] == 0).all()) and bool((fwd["out"][..., Cc:] == 0).all())
+    assert kinds == {"one chunk", "two lanes", "two rounds", "first and last channel", "negative beside zero pads"}
+    assert {c[5] for c in BC.ATTN_CASES} >= {1, 3, 7, 15}
+
+
+def test_boundary_loss_gradient_reference_equals_the_oracle_autograd():
+    """The closed form of the loss gradient against f64 autograd of oracle.unet_oracle.compute_loss, masked and unmasked (the
+    unmasked gradient term of a one-row or one-column plane is an empty mean and is left out); the inputs sit on the 1/64 grid, so
+    every difference is exact in f32, and sign(0) occurs in the L1 term and in both kinds of gradient term."""
+    import boundary_cases as BC
+    from oracle import unet_oracle as O
+    for case in BC.LOSS_BWD_CASES:
+        if case in BC.LOSS_BWD_OVER_CAP:
+            continue
+        planes, H, W = case
+        for masked in (False, True):
+            yp, y, mask = BC.loss_input(case, masked)
+            for t in (yp, y):
+                assert bool(((t * 64).round() == t * 64).all()) and float(t.abs().max()) <= 4.0
+            d = yp - y
+            assert torch.equal(d.double(), yp.double() - y.double())
+            if planes * H * W >= 64:
+                assert bool((d == 0).any())
+                if H > 1 and W > 1:
+                    assert bool((d[:, :-1, 1:] == d[:, :-1, :-1]).any()) and bool((d[:, 1:, :-1] == d[:, :-1, :-1]).any())
+            if masked:
+                assert set(mask.flatten().tolist()) <= set(BC.MASK_VALUES)
+            elif H == 1 or W == 1:
+                continue
+            leaf = yp.double().view(planes, 1, 1, H, W).clone().requires_grad_(True)
+            y5 = y.double().view(planes, 1, 1, H, W)
+            m5 = mask.double().view(planes, 1, 1, H, W) if masked else None
+            O.compute_loss(leaf, y5, m5, use_mask=masked).backward()
+            wgt = 1.0 + 4.0 * y5.abs() ** 3
+            if masked:
+                c1 = 1.0 / float((m5 * wgt).sum() + 1e-8)
+                c2 = 0.005 / float(m5[..., :H - 1, :W - 1].sum() + 1e-8)
+            else:
+                c1, c2 = 1.0 / (planes * H * W), 0.005 / (planes * (H - 1) * (W - 1))
+            ref, mag = BC.loss_bwd_ref(yp, y, mask, c1, c2)
+            torch.testing.assert_close(ref, leaf.grad.view(planes, H, W), rtol=1e-12, atol=1e-15, msg=lambda s: f"{case} {masked}: {s}")
+            assert bool((mag >= ref.abs() * (1 - 1e-12)).all())
+
+
+def test_boundary_kernel_contracts_are_checked_before_launch():
+    """UCLSTM_E_BADARG from the shape or the alignment alone: every pointer is a non-null, 16-byte aligned address that is never
+    dereferenced because nothing is launched; each call differs from an accepted shape in the one thing named."""
+    P, ODD = C.c_void_p(1 << 20), C.c_void_p((1 << 20) + 8)
+    big = 1 << 16
+    for K in (L.lib, L.lib16):
+        # layout converters: (n_img, C, Cp, H, W)
+        assert K.uclstm_nchw_to_nhwc(P, P, 6, 5, 12, 4, 4, 1, 80, 480, None) == -1            # Cp % 8
+        assert K.uclstm_nchw_to_nhwc(P, P, 6, 9, 8, 4, 4, 1, 144, 864, None) == -1            # Cp < C
+        assert K.uclstm_nchw_to_nhwc(P, P, 6, 5, 8, 4, 4, 4, 80, 480, None) == -1             # inner does not divide n_img
+        assert K.uclstm_nchw_to_nhwc(P, P, 6, 5, 8, 4, 4, 0, 80, 480, None) == -1
+        assert K.uclstm_nchw_to_nhwc(P, ODD, 6, 5, 8, 4, 4, 1, 80, 480, None) == -1           # misaligned activation
+        assert K.uclstm_nchw_to_nhwc(None, P, 6, 5, 8, 4, 4, 1, 80, 480, None) == -1
+        assert K.uclstm_nchw_to_nhwc(P, P, 8, 8, 8, big, big // 2, 1, 0, 0, None) == -1       # 2^31 items
+        assert K.uclstm_nchw_grad_to_nhwc(P, P, 6, 5, 12, 4, 4, None) == -1
+        assert K.uclstm_nchw_grad_to_nhwc(P, ODD, 6, 5, 8, 4, 4, None) == -1
+        assert K.uclstm_nhwc_to_nchw(P, P, 6, 5, 12, 4, 4, None) == -1
+        assert K.uclstm_nhwc_to_nchw(ODD, P, 6, 5, 8, 4, 4, None) == -1
+        assert K.uclstm_nhwc_to_nchw(P, P, 8, 8, 8, big, big // 2, None) == -1
+        # im2col: (n_img, C, Kp, H, W, inner)
+        assert K.uclstm_im2col3x3_first(P, P, 6, 2, 16, 4, 4, 1, 32, 192, None) == -1         # Kp < 9*C
+        assert K.uclstm_im2col3x3_first(P, P, 6, 2, 20, 4, 4, 1, 32, 192, None) == -1         # Kp % 8
+        assert K.uclstm_im2col3x3_first(P, P, 6, 2, 24, 4, 4, 4, 32, 192, None) == -1         # inner
+        assert K.uclstm_im2col3x3_first(P, ODD, 6, 2, 24, 4, 4, 1, 32, 192, None) == -1
+        assert K.uclstm_im2col3x3_first(P, P, 8, 1, 16, big, big // 4, 1, 0, 0, None) == -1   # 2^31 items
+        # MaxPool: (n_img, H, W, Cp)
+        assert K.uclstm_maxpool2_fwd(P, P, 2, 4, 4, 12, None) == -1
+        assert K.uclstm_maxpool2_fwd(ODD, P, 2, 4, 4, 8, None) == -1
+        assert K.uclstm_maxpool2_fwd(P, P, 2, 1, 4, 8, None) == -1                            # no window
+        assert K.uclstm_maxpool2_fwd(P, P, 8, 2 * big, big, 8, None) == -1                    # 2^31 chunks
+        assert K.uclstm_maxpool2_bwd(P, P, None, P, 2, 4, 4, 12, None) == -1
+        assert K.uclstm_maxpool2_bwd(P, P, P, P, 2, 5, 4, 8, None) == -1                      # add with odd H
+        assert K.uclstm_maxpool2_bwd(P, P, P, P, 2, 4, 7, 8, None) == -1                      # add with odd W
+        assert K.uclstm_maxpool2_bwd(P, P, ODD, P, 2, 4, 4, 8, None) == -1
+        assert K.uclstm_maxpool2_bwd(P, P, None, ODD, 2, 4, 4, 8, None) == -1
+        assert K.uclstm_maxpool2_bwd(P, P, None, P, 8, 2 * big, big, 8, None) == -1
+        # OutConv: (n_img, HW, Cp, C, Co)
+        assert K.uclstm_outconv_fwd(P, P, P, P, 2, 16, 12, 12, 1, None) == -1                 # Cp % 8
+        assert K.uclstm_outconv_fwd(P, P, P, P, 2, 16, 8, 9, 1, None) == -1                   # C > Cp
+        assert K.uclstm_outconv_fwd(ODD, P, P, P, 2, 16, 8, 5, 1, None) == -1
+        assert K.uclstm_outconv_fwd(P, P, P, P, 2, 16, 8, 5, 0, None) == -1
+        assert K.uclstm_outconv_fwd(P, P, P, P, big, big // 2, 8, 5, 1, None) == -1           # 2^31 pixels
+        assert K.uclstm_outconv_bwd(P, P, P, P, P, P, 2, 16, 2056, 2056, 1, None) == -1       # Cp / 8 > 256
+        assert K.uclstm_outconv_bwd(P, P, P, P, P, P, 2, 16, 12, 12, 1, None) == -1
+        assert K.uclstm_outconv_bwd(ODD, P, P, P, P, P, 2, 16, 8, 5, 1, None) == -1
+        assert K.uclstm_outconv_bwd(P, P, P, ODD, P, P, 2, 16, 8, 5, 1, None) == -1
+        assert K.uclstm_outconv_bwd(P, P, P, P, P, P, big, big // 2, 8, 5, 1, None) == -1     # 2^31 chunks
+        # attention: (n_img, H, W, Cp, C, k)
+        for k in (0, 2, 4, 16, 17, -1):
+            assert K.uclstm_attention_fwd(P, P, P, P, P, P, 2, 4, 4, 8, 5, k, None) == -1, k
+            assert K.uclstm_attention_bwd(P, P, P, P, P, P, P, P, 0, P, 2, 4, 4, 8, 5, k, None) == -1, k
+        assert K.uclstm_attention_fwd(P, P, P, P, P, P, 2, 4, 4, 12, 5, 3, None) == -1
+        assert K.uclstm_attention_fwd(P, P, P, P, P, P, 2, 4, 4, 8, 9, 3, None) == -1
+        assert K.uclstm_attention_fwd(ODD, P, P, P, P, P, 2, 4, 4, 8, 5, 3, None) == -1
+        assert K.uclstm_attention_fwd(P, P, ODD, P, P, P, 2, 4, 4, 8, 5, 3, None) == -1
+        assert K.uclstm_attention_fwd(P, P, P, P, C.c_void_p((1 << 20) + 4), P, 2, 4, 4, 8, 5, 3, None) == -1     # desc: float2 loads
+        assert K.uclstm_attention_fwd(P, P, P, P, P, P, 8, big, big // 4, 8, 5, 3, None) == -1                    # 2^31 chunks
+        assert K.uclstm_attention_bwd(P, P, P, P, P, P, P, P, 0, P, 2, 4, 4, 12, 5, 3, None) == -1
+        assert K.uclstm_attention_bwd(P, ODD, P, P, P, P, P, P, 0, P, 2, 4, 4, 8, 5, 3, None) == -1
+        assert K.uclstm_attention_bwd(P, P, P, P, P, P, ODD, P, 0, P, 2, 4, 4, 8, 5, 3, None) == -1
+        assert K.uclstm_attention_bwd(P, P, P, P, P, P, P, P, 0, None, 2, 4, 4, 8, 5, 3, None) == -1              # scratch required
+        assert K.uclstm_attention_bwd(P, P, P, P, P, P, P, P, 0, P, 8, big, big // 4, 8, 5, 3, None) == -1
+    # the f32 pair and the loss gradient exist once
+    assert L.lib.uclstm_nchw_to_nhwc_f32(P, P, 2, 9, 8, 4, 4, None) == -1
+    assert L.lib.uclstm_nhwc_to_nchw_f32(P, P, 2, 9, 8, 4, 4, None) == -1
+    assert L.lib.uclstm_nchw_to_nhwc_f32(P, None, 2, 5, 8, 4, 4, None) == -1
+    assert L.lib.uclstm_nchw_to_nhwc_f32(P, P, 8, 5, 8, big, big // 2, None) == -1
+    assert L.lib.uclstm_nhwc_to_nchw_f32(P, P, 8, 8, 8, big, big // 2, None) == -1
+    assert L.lib.uclstm_loss_bwd(P, P, None, None, P, 3, 8, 8, None) == -1                    # coefs required
+    assert L.lib.uclstm_loss_bwd(P, P, None, P, P, 3, 0, 8, None) == -1
+    assert L.lib.uclstm_loss_bwd(P, P, None, P, P, 2, big, big // 4, None) == -1              # 2^31 elements
