@@ -489,7 +489,9 @@ int32_t uclstm_sumsq(const float* g, int64_t n, double* out /* accumulates, call
  * The clip coefficient of main.py:106 is derived from this sum, so it reaches every parameter. */
 int64_t uclstm_sumsq_ordered_rows(int64_t n);
 int32_t uclstm_sumsq_ordered(const float* g, int64_t n, double* partials, double* out, int32_t accumulate, void* stream);
-/* p,m,v,g flat f32 [n]; grad is scaled by min(1, max_norm/(sqrt(*sumsq)+1e-6)) read on device (no host sync). */
+/* p,m,v,g flat f32 [n]; grad is scaled by min(1, max_norm/(sqrt(*sumsq)+1e-6)) read on device (no host sync); sumsq == NULL
+ * or max_norm <= 0: no clipping.  Adam's bias corrections 1 - beta^step are computed in double and rounded to f32 once, here and
+ * in every entry point below. */
 int32_t uclstm_adamw_step(float* p, float* m, float* v, const float* g, int64_t n, const double* sumsq, float max_norm,
                           float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, void* stream);
 
@@ -512,8 +514,9 @@ int32_t uclstm_adamw_step_dev(float* p, float* m, float* v, const float* g, int6
  * scale_state == NULL: bias corrections from hyper[1] + 1, computed as uclstm_adamw_step_dev does, and hyper[1] is
  * incremented on the device after the sweep; with one run and one group the result equals uclstm_adamw_step_dev bit for bit.
  * scale_state != NULL (DEVICE f32[3], layout below; sumsq required): the semantics of uclstm_adamw_step_scaled -- update
- * on g / scale, clip on the unscaled norm, NOTHING is touched when *sumsq is not finite, the bias-correction step is
- * scale_state[2] + 1 -- and hyper[1] is left alone: uclstm_loss_scale_update, still a launch of its own, counts the step. */
+ * on g / scale, clip on the unscaled norm, NOTHING is touched on an overflowed step (*sumsq NaN or infinite), the
+ * bias-correction step is scale_state[2] + 1 -- and hyper[1] is left alone: uclstm_loss_scale_update, still a launch of its
+ * own, counts the step.  With one run and one group the result equals uclstm_adamw_step_scaled bit for bit. */
 int32_t uclstm_adamw_step_groups(float* p, float* m, float* v, const float* g, int64_t n, const double* sumsq,
                                  const int64_t* runs, int32_t n_runs, float* hyper, int32_t n_groups,
                                  const float* scale_state, void* stream);
@@ -521,9 +524,12 @@ int32_t uclstm_adamw_step_groups(float* p, float* m, float* v, const float* g, i
 /* fp16 training (the _f16 twins below): the backward pass runs on loss * scale so that fp16 activation gradients stay out of
  * the subnormal range, and g holds scale x the true gradient.  scale_state = DEVICE f32[3] {scale, growth tracker, successful
  * steps}.  uclstm_adamw_step_scaled is uclstm_adamw_step on g / scale (clip on the unscaled norm when max_norm > 0, Adam's
- * bias correction from the device-side count of successful steps) and does NOTHING when *sumsq (of the scaled gradients;
- * required) is not finite; uclstm_loss_scale_update then halves the scale (x backoff) after such a step, or counts a good
- * step and multiplies the scale by `growth` every `interval` good steps in a row.  No host synchronisation. */
+ * bias correction from the device-side count of successful steps, scale_state[2] + 1, computed as everywhere else) to within
+ * f32 rounding of the update, and does NOTHING on an OVERFLOWED step: *sumsq (of the scaled gradients; required) is NaN or
+ * infinite.  uclstm_loss_scale_update applies the same test to the same *sumsq: after an overflowed step it multiplies the
+ * scale by `backoff` (not below 1) and counts nothing; otherwise it counts a successful step and multiplies the scale by
+ * `growth` (not above 2^24) every `interval` good steps in a row.  A step is therefore never skipped and counted, or applied and
+ * backed off.  No host synchronisation. */
 int32_t uclstm_adamw_step_scaled(float* p, float* m, float* v, const float* g, int64_t n, const double* sumsq, float max_norm,
                                  float lr, float beta1, float beta2, float eps, float weight_decay, const float* scale_state,
                                  void* stream);

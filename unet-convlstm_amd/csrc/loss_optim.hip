@@ -137,11 +137,16 @@ __global__ void sumsq_kernel(const float* __restrict__ g, int64_t n, double* __r
     }
 }
 
+// An OVERFLOWED step of fp16 training: the sum of squares of the scaled gradients is NaN or infinite.  The one predicate of the
+// kernels that skip such a step (adamw_scaled_kernel, adamw_groups_kernel with state) and of the one that backs the scale off
+// and does not count it (loss_scale_update_kernel): a step is never skipped and counted, or applied and backed off.
+__device__ __forceinline__ bool step_overflowed(double ss) { return !(fabs(ss) <= 1.7976931348623157e308); }
+
 __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g,
                              int64_t n, const double* __restrict__ sumsq, float max_norm, float lr, float b1, float b2, float eps,
                              float wd, float inv_bc1, float inv_sqrt_bc2) {
     float coef = 1.f;
-    if (sumsq) {
+    if (sumsq && max_norm > 0.f) {                               // max_norm <= 0: no clipping, as in every sibling
         const float total = (float)sqrt(*sumsq);
         coef = fminf(max_norm / (total + 1e-6f), 1.f);          // torch.nn.utils.clip_grad_norm_ (main.py:106)
     }
@@ -190,17 +195,21 @@ __global__ void adamw_advance_kernel(float* hyper) {
 
 // fp16 training: the gradient buffer holds scale x the true gradient (loss scaling keeps fp16 activation gradients out of the
 // subnormal range).  state = {scale, growth tracker, successful steps}.  Same update as adamw_kernel on g / scale; nothing is
-// touched when the scaled sum of squares is not finite (an overflowed step is skipped, the scale backs off in
-// loss_scale_update_kernel); Adam's bias-correction step is the device-side count of successful steps.
+// touched on an overflowed step (step_overflowed: it is skipped, the scale backs off in loss_scale_update_kernel); Adam's
+// bias-correction step is the device-side count of successful steps, the corrections are computed as adamw_dev_kernel computes
+// them (pow in double, rounded once).  The arithmetic is adamw_groups_kernel's, spelled out in the same way with contraction
+// off: that kernel with state, one run and one group gives the same bits.
 __global__ void adamw_scaled_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g,
                                     int64_t n, const double* __restrict__ sumsq, float max_norm, float lr, float b1, float b2, float eps,
                                     float wd, const float* __restrict__ state) {
+#pragma clang fp contract(off)
     const double ss = *sumsq;
-    if (!(ss == ss) || ss > 1.0e300 || isinf(ss)) return;
+    if (step_overflowed(ss)) return;
     const float inv_scale = 1.f / state[0];
-    const float step = state[2] + 1.f;
-    const float inv_bc1 = 1.f / (1.f - exp2f(step * log2f(b1)));
-    const float inv_sqrt_bc2 = rsqrtf(1.f - exp2f(step * log2f(b2)));
+    const double step = (double)state[2] + 1.0;
+    const float lr_bc1 = lr * (float)(1.0 / (1.0 - pow((double)b1, step)));
+    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
+    const float decay = __builtin_fmaf(-lr, wd, 1.f);            // decoupled decay factor 1 - lr * wd
     float coef = inv_scale;
     if (max_norm > 0.f) {
         const float total = (float)sqrt(ss) * inv_scale;
@@ -208,12 +217,10 @@ __global__ void adamw_scaled_kernel(float* __restrict__ p, float* __restrict__ m
     }
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
         const float gi = g[i] * coef;
-        float w = p[i] * (1.f - lr * wd);
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-        w -= lr * inv_bc1 * mi / denom;
-        p[i] = w;
+        const float mi = __builtin_fmaf(1.f - b1, gi, b1 * m[i]);
+        const float vi = b2 * v[i] + ((1.f - b2) * gi) * gi;
+        const float denom = __builtin_fmaf(sqrtf(vi), inv_sqrt_bc2, eps);
+        p[i] = decay * p[i] - (lr_bc1 * mi) / denom;
         m[i] = mi;
         v[i] = vi;
     }
@@ -240,7 +247,7 @@ __global__ void adamw_groups_kernel(float* __restrict__ p, float* __restrict__ m
     double step;
     if (state) {
         const double ss = *sumsq;
-        if (!(ss == ss) || ss > 1.0e300 || isinf(ss)) return;    // overflowed step: touch nothing (uniform over the grid)
+        if (step_overflowed(ss)) return;                         // touch nothing (uniform over the grid)
         const float inv_scale = 1.f / state[0];
         step = (double)state[2] + 1.0;
         coef = inv_scale;
@@ -343,7 +350,7 @@ __global__ void loss_scale_update_kernel(float* __restrict__ state, const double
                                          int interval) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const double ss = *sumsq;
-    if (!(ss == ss) || isinf(ss)) {
+    if (step_overflowed(ss)) {
         state[0] = fmaxf(state[0] * backoff, 1.f);
         state[1] = 0.f;
     } else {

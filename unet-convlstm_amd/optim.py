@@ -167,9 +167,12 @@ class FusedAdamW(torch.optim.Optimizer):
                      for g in self.param_groups)
 
     def steps_done(self) -> int:
-        """Optimiser steps applied so far (with loss scaling: the successful ones).  Reads the device where the count lives."""
+        """Optimiser steps applied so far (with loss scaling: the successful ones, ``scale_state[2]``; ``step_count`` also counts
+        the skipped ones).  Reads the device where the count lives."""
+        if self.scale_state is not None:
+            return int(self.scale_state[2].item())
         if self.uses_groups:
-            return int((self.group_hyper[0, 1] if self.scale_state is None else self.scale_state[2]).item())
+            return int(self.group_hyper[0, 1].item())
         if self.capturable:
             return int(self.hyper[6].item())
         return int(self.step_count)
@@ -209,8 +212,8 @@ class FusedAdamW(torch.optim.Optimizer):
     # otherwise a save / load / resume would silently restart Adam.
     def state_dict(self):
         sd = super().state_dict()
-        if self.capturable or self.uses_groups:
-            self.step_count = self.steps_done()                  # the device-side count is the truth in capturable mode
+        if self.capturable or self.uses_groups or self.scale_state is not None:
+            self.step_count = self.steps_done()                  # the device-side count is the truth wherever there is one
         sd["fused"] = {"exp_avg": self.m.detach().clone(), "exp_avg_sq": self.v.detach().clone(), "step": int(self.step_count),
                        "numel": int(self.flat.numel),
                        "scale_state": None if self.scale_state is None else self.scale_state.detach().clone(),
