@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from pack_cases import index_map            # noqa: F401  (tests/test_gpu_deterministic.py imports it from here)
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
@@ -14,45 +16,6 @@ if torch.cuda.is_available():
     L = U._lib
 
 DEV = "cuda"
-
-
-def index_map(d):
-    """(valid [N,Ktot] bool, offset [N,Ktot] int64) of the descriptor, straight from include/uclstm.h's definition."""
-    N, K = d.N, d.Ktot
-    n = np.arange(N)[:, None]
-    k = np.arange(K)[None, :]
-    tapn = np.zeros_like(n)
-    if d.n_mode == L.NMODE_IDENTITY:
-        n_ent, ok_n = n, n < d.n_valid
-    elif d.n_mode == L.NMODE_LSTM:
-        hb, gate, j = n >> 6, (n & 63) >> 4, n & 15
-        hc = hb * 16 + j
-        n_ent, ok_n = gate * d.n_valid + hc, hc < d.n_valid
-    else:
-        tapn = n // d.n_cp
-        n_ent = n - tapn * d.n_cp
-        ok_n = n_ent < d.n_valid
-    per_tap = d.kseg[0] + d.kseg[1]
-    tap = k // per_tap
-    kr = k - tap * per_tap
-    s = (kr >= d.kseg[0]).astype(np.int64)
-    c = np.where(s == 1, kr - d.kseg[0], kr)
-    cvalid = np.where(s == 1, d.cvalid[1], d.cvalid[0])
-    choff = np.where(s == 1, d.choff[1], d.choff[0])
-    if d.k_mode == L.KMODE_IDENTITY:
-        ok_k, k_ent = c < cvalid, choff + c
-        ntap = d.taps
-    elif d.k_mode == L.KMODE_GATES:
-        gate, hc = c // d.k_hdp, c % d.k_hdp
-        ok_k, k_ent = (gate < 4) & (hc < d.k_hd), choff + gate * d.k_hd + hc
-        ntap = d.taps
-    else:
-        tk = c // d.k_hd
-        ok_k, k_ent, tap, ntap = tk < d.k_hdp, c - tk * d.k_hd, tk, d.k_hdp
-    tap_eff = (ntap - 1 - tap) if d.tap_flip else tap
-    off = n_ent * d.stride_n + k_ent * d.stride_k + tap_eff * d.stride_tap + tapn * d.stride_ntap
-    valid = ok_n & ok_k
-    return valid, np.where(valid, off, 0)
 
 
 CASES = {
