@@ -223,6 +223,13 @@ KERNEL_LOG: Optional[list] = None
 LAUNCH_LOG: Optional[list] = None
 
 
+# Optional record of what the ConvLSTM recurrence stored per step: when it is a list, ConvLSTMSeq.forward and
+# convlstm_group_forward (once per member) append ("fwd", h_hist, c_hist, gates) and ConvLSTMSeq.backward appends
+# ("bwd", dgates) after its loop -- the tensors themselves, not copies.  tests/test_gpu_recurrence.py checks every step of a
+# sequence against an f64 cell on these stored inputs.  None (the default): nothing is recorded and no launch changes.
+RECURRENCE_TRACE: Optional[list] = None
+
+
 def _log_shape(d) -> None:
     if SHAPE_LOG is not None or KERNEL_LOG is not None or LAUNCH_LOG is not None:
         shp = int(L.lib.uclstm_igemm_fwd_shape(C.byref(d)))
@@ -1928,6 +1935,8 @@ class ConvLSTMSeq(torch.autograd.Function):
                                                         _p(h_hist[t + 1]), _p(g_t), pixels, Hdp, _stream()), "lstm_fwd_pointwise")
             else:
                 igemm_lstm(None if hoist else x_all[t], h_prev, wp, bp, c_prev, c_hist[t + 1], h_hist[t + 1], g_t, ks, pre_add=px_t)
+        if RECURRENCE_TRACE is not None:
+            RECURRENCE_TRACE.append(("fwd", h_hist, c_hist, gates))
         if need_grad:
             ctx.save_for_backward(x_all, weight, h_hist, c_hist, gates, bias)
             ctx.cfg = (Hd, Cx, c0 is not None, bias is not None, ks)
@@ -1980,6 +1989,8 @@ class ConvLSTMSeq(torch.autograd.Function):
                                  slabs=True)
                 else:
                     igemm_store([SrcView(dgates[t])], wd_h, (H, W), B, [(dh_rec, 0, ddh.N, 0, 1, 0, 0)], ktap=ks, pad=ks // 2)
+        if RECURRENCE_TRACE is not None:
+            RECURRENCE_TRACE.append(("bwd", dgates))
         dg_flat = dgates.view(T * B, H, W, 4 * Hdp)
         x_flat = x_all.reshape(T * B, H, W, Cxp)
         hprev_flat = h_hist[:T].reshape(T * B, H, W, Hdp)
@@ -2127,6 +2138,9 @@ def convlstm_group_forward(members, need_grad: bool):
         if pws:
             arr = (L.LstmFwdPwArgs * len(pws))(*pws)
             L.check(K.uclstm_lstm_fwd_pointwise_group(arr, len(pws), _stream()), "lstm_fwd_pointwise_group")
+    if RECURRENCE_TRACE is not None:
+        for m in ms:
+            RECURRENCE_TRACE.append(("fwd", m.h_hist, m.c_hist, m.gates))
     return [(m.h_hist, m.c_hist, m.gates) for m in ms]
 
 
