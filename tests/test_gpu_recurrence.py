@@ -364,6 +364,55 @@ def test_group_step_against_f64_and_its_refusals(dtype):
         report(f"group step {c.name}", dtype, f"group step, {ks} K range(s)", worst)
 
 
+def group_ksplits(cases):
+    return ops.plan_group_ksplit([(((ops.lstm_pack_desc(c.Hd, c.Cx, 3).N + 127) // 128) * (c.pixels // 256),
+                                   ops.lstm_pack_desc(c.Hd, c.Cx, 3).Ktot // (64 * 9)) for c in cases])
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=RC.tag)
+def test_single_sequence_equals_its_group_member_bit_for_bit(dtype):
+    """A group member is by construction a patch-shape launch on its own: ConvLSTMSeq with the member's planned K-range count stores
+    the same bits in every slot of h_hist, c_hist and gates as convlstm_group_forward, through kernel shape 2 with the planned epilogue."""
+    ops.GROUP_LSTM, ops.HOIST_X = True, False
+    members = [m[2] for m in group_members(dtype, GROUP)]
+    ksplits = group_ksplits(GROUP)
+    with torch.no_grad():
+        ops.RECURRENCE_TRACE = grouped = []
+        ops.convlstm_group_forward(members, True)
+        assert [e[0] for e in grouped] == ["fwd"] * 3
+        for c, mem, ks, (_, h_g, c_g, g_g) in zip(GROUP, members, ksplits, grouped):
+            ops.RECURRENCE_TRACE, ops.KERNEL_LOG = single, klog = [], []
+            ops.split_k_factor = lambda *a, _ks=ks, **k: _ks
+            ops.ConvLSTMSeq.apply(*mem, True)
+            assert klog == [(L.EPI_ATOMIC if ks > 1 else L.EPI_LSTM, 2)] * c.T, f"{c.name}: single launches {klog}"
+            (_, h_s, c_s, g_s), = single
+            torch.cuda.synchronize()
+            zero_c0 = mem[2] is None                                 # slot 0 of c_hist is never written nor read for a zero cell state
+            assert torch.equal(h_s, h_g), f"{c.name}: h_hist differs"
+            assert torch.equal(c_s[int(zero_c0):], c_g[int(zero_c0):]), f"{c.name}: c_hist differs"
+            assert torch.equal(g_s, g_g), f"{c.name}: gates differ"
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=RC.tag)
+def test_group_step_equals_a_group_forward_of_one_step(dtype):
+    """convlstm_group_step with carried state into NaN-filled buffers against convlstm_group_forward on x_t[None], h0, c0: the new
+    state is slot 1 of the histories, bit for bit."""
+    ops.GROUP_LSTM, ops.HOIST_X = True, False
+    cases = [RCase(**{**c.__dict__, "T": 1, "state": True}) for c in GROUP]
+    ds = [{k: (None if v is None else v.to(DEV)) for k, v in RC.make_inputs(c, dtype).items()} for c in cases]
+    outs = [(torch.full_like(d["h0"], float("nan")), torch.full_like(d["c0"], float("nan"))) for d in ds]
+    with torch.no_grad():
+        assert ops.convlstm_group_step([(d["x_all"][0], d["h0"], d["c0"], h_out, c_out, d["weight"], d["bias"], c.Hd, c.Cx)
+                                        for c, d, (h_out, c_out) in zip(cases, ds, outs)]) is True
+        res = ops.convlstm_group_forward([(d["x_all"][0][None], d["h0"], d["c0"], d["weight"], d["bias"], c.Hd, c.Cx) for c, d in zip(cases, ds)],
+                                         False)
+        torch.cuda.synchronize()
+    for c, (h_out, c_out), (h_hist, c_hist, gates) in zip(cases, outs, res):
+        assert gates is None
+        assert torch.equal(h_out, h_hist[1]), f"{c.name}: h_out differs from h_hist[1]"
+        assert torch.equal(c_out, c_hist[1]), f"{c.name}: c_out differs from c_hist[1]"
+
+
 # ---------------------------------------------------------------------------------------------
 # 5. inference forms
 # ---------------------------------------------------------------------------------------------

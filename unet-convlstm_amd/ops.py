@@ -9,6 +9,8 @@ tensors: ``_dev`` raises.
 from __future__ import annotations
 
 import ctypes as C
+import heapq
+import itertools
 import os
 from typing import List, Optional, Sequence, Tuple
 
@@ -1045,33 +1047,47 @@ def igemm_atomic(srcs: Sequence[SrcView], wp: torch.Tensor, out_hw: Tuple[int, i
     """Split-K convolution as `ksplit` K ranges.  ``slabs=False``: acc_out[pixel, n] += ... with f32 atomics
     (acc_out f32 [pixels, ld>=N], zeroed by the caller).  ``slabs=True``: acc_out is [ksplit_used, pixels, ld]; range r
     stores into acc_out[r] and the consumer adds the slabs (plain stores run ~4.6x faster than float atomics)."""
-    d, flops, nbytes, note = _atomic_desc(srcs, wp, out_hw, n_img, acc_out, ksplit, ktap=ktap, scale=scale, pad=pad, slabs=slabs)
+    _igemm_launch(_atomic_desc(srcs, wp, out_hw, n_img, acc_out, ksplit, ktap=ktap, scale=scale, pad=pad, slabs=slabs), _k(wp), kind,
+                  "igemm_fwd(atomic)")
+
+
+def _igemm_launch(item, K, kind: str, what: str) -> None:
+    """One uclstm_igemm_fwd launch of a (desc, flops, nbytes, note) item of _atomic_desc / _lstm_desc."""
+    d, flops, nbytes, note = item
     _log_shape(d)
-    K = _k(wp)
-    _timed(_kernel_kind(kind, d), flops, lambda: L.check(K.uclstm_igemm_fwd(C.byref(d), _stream()), "igemm_fwd(atomic)"), note, nbytes=nbytes)
+    _timed(_kernel_kind(kind, d), flops, lambda: L.check(K.uclstm_igemm_fwd(C.byref(d), _stream()), what), note, nbytes=nbytes)
 
 
 def _lstm_desc(x: Optional[torch.Tensor], h_prev: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], c_prev: Optional[torch.Tensor],
-               c_out: torch.Tensor, h_out: torch.Tensor, gates_out: Optional[torch.Tensor], ksize: int = 3,
-               pre_add: Optional[torch.Tensor] = None):
+               c_out: Optional[torch.Tensor], h_out: Optional[torch.Tensor], gates_out: Optional[torch.Tensor], ksize: int = 3,
+               pre_add: Optional[torch.Tensor] = None, probe: Optional[tuple] = None):
+    """Descriptor of a fused ConvLSTM cell step, as (desc, flops, nbytes, note).  ``probe`` = (B, H, W, source channel counts, N, Ktot,
+    placeholder pointer) instead of the tensors: the same descriptor for the library's planners, which read the shapes and
+    dereference no pointer."""
     d = L.IgemmDesc()
-    B, H, W, _ = h_prev.shape
+    if probe is not None:
+        B, H, W, chans, d.N, d.Ktot, ptr = probe
+        d.nsrc = len(chans)
+        for i, cch in enumerate(chans):
+            d.src[i].ptr, d.src[i].C, d.src[i].Hs, d.src[i].Ws = ptr, cch, H, W
+        d.wp = d.c_out = d.h_out = ptr
+    else:
+        B, H, W, _ = h_prev.shape
+        srcs = [h_prev] if x is None else [x, h_prev]
+        d.nsrc = len(srcs)
+        for i, t in enumerate(srcs):
+            SrcView(t).fill(d.src[i])
+        d.wp, d.N, d.Ktot = wp.data_ptr(), wp.shape[0], wp.shape[1]
+        d.c_out, d.h_out = c_out.data_ptr(), h_out.data_ptr()
     d.n_img, d.H, d.W, d.groups = B, H, W, 1
     d.ktap, d.scale, d.pad = ksize, 1, ksize // 2
-    if x is not None:
-        d.nsrc = 2
-        SrcView(x).fill(d.src[0])
-        SrcView(h_prev).fill(d.src[1])
-    else:
-        d.nsrc = 1
-        SrcView(h_prev).fill(d.src[0])
-    d.pre_add = None if pre_add is None else _dev(pre_add, F32, "pre_add").data_ptr()
-    d.wp, d.N, d.Ktot = wp.data_ptr(), wp.shape[0], wp.shape[1]
-    d.bias = None if bias is None else bias.data_ptr()
     d.relu, d.epi, d.nseg = 0, L.EPI_LSTM, 0
-    d.Hd_p = h_prev.shape[3]
+    d.Hd_p = d.src[d.nsrc - 1].C
+    if probe is not None:
+        return d, 0.0, 0.0, "probe"
+    d.pre_add = None if pre_add is None else _dev(pre_add, F32, "pre_add").data_ptr()
+    d.bias = None if bias is None else bias.data_ptr()
     d.c_prev = None if c_prev is None else c_prev.data_ptr()
-    d.c_out, d.h_out = c_out.data_ptr(), h_out.data_ptr()
     d.gates_out = None if gates_out is None else gates_out.data_ptr()
     flops = 2.0 * B * H * W * (4 * d.Hd_p) * ksize * ksize * ((x.shape[3] if x is not None else 0) + h_prev.shape[3])
     _same_act_dtype([h_prev, wp, h_out] + ([x] if x is not None else []) + ([gates_out] if gates_out is not None else []), "igemm_fwd(lstm)")
@@ -1084,11 +1100,7 @@ def igemm_lstm(x: Optional[torch.Tensor], h_prev: torch.Tensor, wp: torch.Tensor
                pre_add: Optional[torch.Tensor] = None) -> None:
     """Fused ConvLSTM cell step.  ``x`` given: gate conv over (x_t, h_{t-1}) with the two-source panel.  ``x=None``: the
     launch carries W_h * h_{t-1} only and ``pre_add`` (f32 [pixels, N]) holds the hoisted W_x * x_t."""
-    d, flops, nbytes, note = _lstm_desc(x, h_prev, wp, bias, c_prev, c_out, h_out, gates_out, ksize, pre_add)
-    _log_shape(d)
-    K = _k(wp)
-    _timed(_kernel_kind("igemm_fwd_lstm", d), flops, lambda: L.check(K.uclstm_igemm_fwd(C.byref(d), _stream()), "igemm_fwd(lstm)"), note,
-           nbytes=nbytes)
+    _igemm_launch(_lstm_desc(x, h_prev, wp, bias, c_prev, c_out, h_out, gates_out, ksize, pre_add), _k(wp), "igemm_fwd_lstm", "igemm_fwd(lstm)")
 
 
 def igemm_group(items, K, kind: str = "igemm_fwd_group") -> None:
@@ -1850,6 +1862,122 @@ class SpatialAttn(_GradAwareFunction):
 # ---------------------------------------------------------------------------------------------
 # ConvLSTM layer over a whole sequence  (train/unet.py:21-36 x T, :55-57)
 # ---------------------------------------------------------------------------------------------
+class _LstmLayerFwd:
+    """The forward recurrence of ONE ConvLSTM layer: panels, state storage and the descriptors of every step.  ConvLSTMSeq.forward
+    launches its steps one by one, convlstm_group_forward / convlstm_group_step those of 2 to 4 layers as group launches.
+
+    x_all [T,B,H,W,Cxp]; h0 [B,H,W,Hdp] / c0 f32 or None (zero state).  State storage:
+      training / plain    h_hist, c_hist of T+1 slots, slot 0 a copy of h0 / c0 (zeros for h0 = None; c_hist[0] is not read for c0 = None)
+      direct (inference)  the same, but step 0 reads h0 / c0 where they lie (``in_place``; slot 0 is then not written)
+      out = (h, c)        one step with a carried state that writes the caller's buffers (h_out must not be h0: the convolution reads
+                          h0's neighbourhoods while h_out is written; c_out may be c0 itself, the cell update is element-wise)
+    ``hoist`` (single sequences only, T >= 2): W_x * x_t for ALL timesteps as one GEMM over T*B*H*W pixels, launched here (f32
+    pre-activations in panel-row order); the recurrence then multiplies only by W_h: K and the weight bytes re-read per step halve
+    (SURVEY.md section 7-4)."""
+
+    def __init__(self, x_all, h0, c0, weight, bias, Hd, Cx, need_grad, out=None, hoist=False, in_place=True):
+        _dev(x_all, ACT, "x_all")
+        adt, dev = x_all.dtype, x_all.device
+        T, B, H, W, Cxp = x_all.shape
+        self.x_all, self.h0, self.T, self.B, self.H, self.W = x_all, h0, T, B, H, W
+        self.ks = ks = weight.shape[-1]
+        self.Hdp = Hdp = cpad(Hd)
+        self.pixels = pixels = B * H * W
+        pd = lstm_pack_desc(Hd, Cx, ks)
+        self.bp = pack_bias(pd, bias) if bias is not None else None
+        state = (B, H, W, Hdp)
+        fits = lambda t, dt: t.is_contiguous() and t.dtype == dt and tuple(t.shape) == state
+        if out is not None:
+            if need_grad or T != 1 or h0 is None:
+                raise L.UclstmError("ConvLSTMSeq: out= is for one-step inference with a carried state")
+            if not (fits(out[0], adt) and fits(out[1], F32)):
+                raise L.UclstmError("ConvLSTMSeq: out buffers must be contiguous [B,H,W,Hd_p] (h: activation dtype, c: f32)")
+            if out[0].data_ptr() == h0.data_ptr():
+                raise L.UclstmError("ConvLSTMSeq: h_out aliases h0")
+        # inference (nothing saved): step 0 reads the caller's state tensors where they lie instead of copies in slot 0
+        direct = in_place and not need_grad and h0 is not None and fits(h0, adt) and (c0 is None or fits(c0, F32))
+        if out is not None and not direct:
+            raise L.UclstmError("ConvLSTMSeq: out= needs the carried state as contiguous [B,H,W,Hd_p] tensors (h: activation dtype, c: f32)")
+        self.h_hist = torch.empty((T + 1,) + state, dtype=adt, device=dev) if out is None else (None, out[0])
+        self.c_hist = torch.empty((T + 1,) + state, dtype=F32, device=dev) if out is None else (None, out[1])
+        if h0 is None:
+            self.h_hist[0].zero_()
+        elif not direct:
+            self.h_hist[0].copy_(h0)
+        if c0 is not None and not direct:
+            self.c_hist[0].copy_(c0)
+        self.h_first = h0 if direct else self.h_hist[0]
+        self.c_first = None if c0 is None else (c0 if direct else self.c_hist[0])
+        self.gates = torch.empty((T, B, H, W, 4, Hdp), dtype=adt, device=dev) if need_grad else None
+        self.pre_x = None
+        if hoist and T >= 2:
+            wx = pack_weights(lstm_half_pack_desc(Hd, Cx, "x", ks), weight, 0, adt)
+            self.wp = pack_weights(lstm_half_pack_desc(Hd, Cx, "h", ks), weight, 0, adt)
+            N = self.wp.shape[0]
+            pre_x = torch.empty((1, T * pixels, N), dtype=F32, device=dev)
+            for i0, i1 in _img_chunks(T * B, 1, max(_bytes_per_img(x_all[0]), H * W * N * 4), "convlstm x half"):
+                igemm_atomic([SrcView(x_all.view(T * B, H, W, Cxp)[i0:i1])], wx, (H, W), i1 - i0,
+                             pre_x[:, i0 * H * W:i1 * H * W], 1, ktap=ks, pad=ks // 2, slabs=True, kind="igemm_fwd_xhoist")
+            self.pre_x = pre_x.view(T, pixels, N)
+        else:
+            self.wp = pack_weights(pd, weight, 0, adt)
+        self.N, self.Ktot = self.wp.shape
+        # this layer's entry of plan_group_ksplit's argument: (128 x 256 output tiles, chunks of 64 channels x 9 taps)
+        self.group_plan_input = ((self.N + 127) // 128) * (pixels // 256), self.Ktot // (64 * 9)
+        # the point-wise kernel's arguments: the constants here, the step's slots in step()
+        self.pw = a = L.LstmFwdPwArgs()
+        a.clear, a.pixels, a.Hd_p = 0, pixels, Hdp
+        a.bias = None if self.bp is None else self.bp.data_ptr()
+
+    def split(self, ksplit: int) -> None:
+        """K ranges per step, from the caller's planner.  More than one: one f32 slab per K range (plain stores; the point-wise
+        kernel adds them): no atomics, nothing to zero."""
+        self.ksplit = ksplit
+        nsl = ksplit_used(self.Ktot, ksplit, self.ks) if ksplit > 1 else 0
+        self.pre = torch.empty((nsl, self.pixels, self.N), dtype=F32, device=self.x_all.device) if ksplit > 1 else None
+
+    def step(self, t: int):
+        """Step t as (igemm item, point-wise arguments): the fused cell (item, None), split-K slabs + the point-wise kernel
+        (item, args), or -- hoisted with a zero initial state (train/unet.py:23-25): W_h * 0 = 0, the step is the point-wise update
+        of W_x * x_0 -- (None, args).  The arguments are this layer's one struct: use them before the next call."""
+        h_prev, c_prev = (self.h_first, self.c_first) if t == 0 else (self.h_hist[t], self.c_hist[t])
+        c_out, h_out = self.c_hist[t + 1], self.h_hist[t + 1]
+        g_t = None if self.gates is None else self.gates[t]
+        hoist = self.pre_x is not None
+        px_t = self.pre_x[t] if hoist else None
+        ks = self.ks
+        alone = hoist and t == 0 and self.h0 is None
+        if self.ksplit == 1 and not alone:
+            return _lstm_desc(None if hoist else self.x_all[t], h_prev, self.wp, self.bp, c_prev, c_out, h_out, g_t, ks, pre_add=px_t), None
+        pre = None if alone else self.pre
+        item = None if alone else _atomic_desc(([] if hoist else [SrcView(self.x_all[t])]) + [SrcView(h_prev)], self.wp, (self.H, self.W),
+                                               self.B, pre, self.ksplit, ktap=ks, pad=ks // 2, slabs=True)
+        a = self.pw
+        a.pre, a.nslab, a.slab = (None, 0, 0) if alone else (pre.data_ptr(), pre.shape[0], pre.stride(0))
+        a.pre_add = None if px_t is None else px_t.data_ptr()
+        a.c_prev = None if c_prev is None else c_prev.data_ptr()
+        a.c_out, a.h_out = c_out.data_ptr(), h_out.data_ptr()
+        a.gates_out = None if g_t is None else g_t.data_ptr()
+        return item, a
+
+
+def _lstm_launch_one(K, item, pw) -> None:
+    """One step of one layer: a launch of its own, then the point-wise kernel where the step has one."""
+    if item is not None:
+        _igemm_launch(item, K, *(("igemm_fwd_lstm", "igemm_fwd(lstm)") if pw is None else ("igemm_fwd_atomic", "igemm_fwd(atomic)")))
+    if pw is not None:
+        L.check(K.uclstm_lstm_fwd_pointwise(pw.pre, pw.nslab, pw.slab, pw.clear, pw.pre_add, pw.bias, pw.c_prev, pw.c_out, pw.h_out,
+                                            pw.gates_out, pw.pixels, pw.Hd_p, _stream()), "lstm_fwd_pointwise")
+
+
+def _lstm_launch_group(K, steps) -> None:
+    """One step of several layers (``steps``: what each layer's step() returned): ONE group launch, then at most one point-wise launch."""
+    igemm_group([item for item, _ in steps], K)
+    pws = [pw for _, pw in steps if pw is not None]
+    if pws:
+        L.check(K.uclstm_lstm_fwd_pointwise_group((L.LstmFwdPwArgs * len(pws))(*pws), len(pws), _stream()), "lstm_fwd_pointwise_group")
+
+
 class ConvLSTMSeq(torch.autograd.Function):
     """All T steps of one ConvLSTM layer.
 
@@ -1864,86 +1992,23 @@ class ConvLSTMSeq(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_all, h0, c0, weight, bias, Hd, Cx, need_grad, out=None):
         ctx.set_materialize_grads(False)
-        _dev(x_all, ACT, "x_all")
-        adt = x_all.dtype
-        K = _k(x_all)
-        T, B, H, W, Cxp = x_all.shape
-        Hdp = cpad(Hd)
-        dev = x_all.device
-        ks = weight.shape[-1]
-        pd = lstm_pack_desc(Hd, Cx, ks)
-        bp = pack_bias(pd, bias) if bias is not None else None
-        if out is not None:
-            # streaming inference: the single step writes the caller's state buffers (h_out must not be h0: the convolution
-            # reads h0's neighbourhoods while h_out is written; c_out may be c0 itself, the cell update is element-wise)
-            if need_grad or T != 1 or h0 is None:
-                raise L.UclstmError("ConvLSTMSeq: out= is for one-step inference with a carried state")
-            for t_, dt_ in ((out[0], adt), (out[1], F32)):
-                if not (t_.is_contiguous() and t_.dtype == dt_ and tuple(t_.shape) == (B, H, W, Hdp)):
-                    raise L.UclstmError("ConvLSTMSeq: out buffers must be contiguous [B,H,W,Hd_p] (h: activation dtype, c: f32)")
-            if out[0].data_ptr() == h0.data_ptr():
-                raise L.UclstmError("ConvLSTMSeq: h_out aliases h0")
-        h_hist = torch.empty((T + 1, B, H, W, Hdp), dtype=adt, device=dev) if out is None else (None, out[0])
-        c_hist = torch.empty((T + 1, B, H, W, Hdp), dtype=F32, device=dev) if out is None else (None, out[1])
-        # inference (nothing saved): step 0 reads the caller's state tensors where they lie instead of copies in slot 0
-        direct = (not need_grad and h0 is not None and h0.is_contiguous() and h0.dtype == adt and tuple(h0.shape) == (B, H, W, Hdp)
-                  and (c0 is None or (c0.is_contiguous() and c0.dtype == F32 and tuple(c0.shape) == (B, H, W, Hdp))))
-        if out is not None and not direct:
-            raise L.UclstmError("ConvLSTMSeq: out= needs the carried state as contiguous [B,H,W,Hd_p] tensors (h: activation dtype, c: f32)")
-        if h0 is None:
-            h_hist[0].zero_()
-        elif not direct:
-            h_hist[0].copy_(h0)
-        if c0 is not None and not direct:
-            c_hist[0].copy_(c0)
-        gates = torch.empty((T, B, H, W, 4, Hdp), dtype=adt, device=dev) if need_grad else None
-        pixels = B * H * W
+        m = _LstmLayerFwd(x_all, h0, c0, weight, bias, Hd, Cx, need_grad, out, hoist=HOIST_X)
         # Per-step GEMM M = B*H*W.  When its tile grid cannot fill the chip (bottleneck LSTM: M = 512), run the gate
         # convolution as split-K partial tiles in f32 slabs and apply the cell update in a point-wise kernel; otherwise one
         # fused kernel per step (gates never leave registers).
-        hoist = HOIST_X and T >= 2
-        if hoist:
-            # W_x * x_t for ALL timesteps as one GEMM over T*B*H*W pixels (f32 pre-activations in panel-row order); the
-            # recurrence then multiplies only by W_h: K and the weight bytes re-read per step halve
-            wx = pack_weights(lstm_half_pack_desc(Hd, Cx, "x", ks), weight, 0, adt)
-            wp = pack_weights(lstm_half_pack_desc(Hd, Cx, "h", ks), weight, 0, adt)
-            N = wp.shape[0]
-            pre_x = torch.empty((1, T * pixels, N), dtype=F32, device=dev)
-            for i0, i1 in _img_chunks(T * B, 1, max(_bytes_per_img(x_all[0]), H * W * N * 4), "convlstm x half"):
-                igemm_atomic([SrcView(x_all.view(T * B, H, W, Cxp)[i0:i1])], wx, (H, W), i1 - i0,
-                             pre_x[:, i0 * H * W:i1 * H * W], 1, ktap=ks, pad=ks // 2, slabs=True, kind="igemm_fwd_xhoist")
-            pre_x = pre_x.view(T, pixels, N)
-        else:
-            wp = pack_weights(pd, weight, 0, adt)
-        ksplit = split_k_factor(pixels, wp.shape[0], wp.shape[1] // 64)
-        # one f32 slab per K range (plain stores; the point-wise kernel adds them): no atomics, nothing to zero
-        nsl = ksplit_used(wp.shape[1], ksplit, ks) if ksplit > 1 else 0
-        pre = torch.empty((nsl, pixels, wp.shape[0]), dtype=F32, device=dev) if ksplit > 1 else None
-        for t in range(T):
-            c_prev = (c0 if (direct and t == 0) else c_hist[t]) if (c0 is not None or t > 0) else None
-            h_prev = h0 if (direct and t == 0) else h_hist[t]
-            g_t = gates[t] if need_grad else None
-            px_t = pre_x[t] if hoist else None
-            srcs = ([] if hoist else [SrcView(x_all[t])]) + [SrcView(h_prev)]
-            if hoist and t == 0 and h0 is None:
-                # zero initial state (train/unet.py:23-25): W_h * 0 = 0, the step is the point-wise update of W_x * x_0
-                L.check(K.uclstm_lstm_fwd_pointwise(None, 0, 0, 0, _p(px_t), _p(bp), _p(c_prev), _p(c_hist[1]), _p(h_hist[1]),
-                                                        _p(g_t), pixels, Hdp, _stream()), "lstm_fwd_pointwise")
-            elif ksplit > 1:
-                igemm_atomic(srcs, wp, (H, W), B, pre, ksplit, ktap=ks, pad=ks // 2, slabs=True)
-                L.check(K.uclstm_lstm_fwd_pointwise(_p(pre), nsl, pre.stride(0), 0, _p(px_t), _p(bp), _p(c_prev), _p(c_hist[t + 1]),
-                                                        _p(h_hist[t + 1]), _p(g_t), pixels, Hdp, _stream()), "lstm_fwd_pointwise")
-            else:
-                igemm_lstm(None if hoist else x_all[t], h_prev, wp, bp, c_prev, c_hist[t + 1], h_hist[t + 1], g_t, ks, pre_add=px_t)
+        m.split(split_k_factor(m.pixels, m.N, m.Ktot // 64))
+        K = _k(x_all)
+        for t in range(m.T):
+            _lstm_launch_one(K, *m.step(t))
         if RECURRENCE_TRACE is not None:
-            RECURRENCE_TRACE.append(("fwd", h_hist, c_hist, gates))
+            RECURRENCE_TRACE.append(("fwd", m.h_hist, m.c_hist, m.gates))
         if need_grad:
-            ctx.save_for_backward(x_all, weight, h_hist, c_hist, gates, bias)
-            ctx.cfg = (Hd, Cx, c0 is not None, bias is not None, ks)
+            ctx.save_for_backward(x_all, weight, m.h_hist, m.c_hist, m.gates, bias)
+            ctx.cfg = (Hd, Cx, c0 is not None, bias is not None, m.ks)
             note_use(weight, bias)
         if out is not None:
             return out[0].unsqueeze(0), out[1]
-        return h_hist[1:], c_hist[T]
+        return m.h_hist[1:], m.c_hist[m.T]
 
     @staticmethod
     def backward(ctx, dh_all, dc_T):
@@ -2032,7 +2097,6 @@ _BLOCK_OVERHEAD_STEPS = 12.0          # prologue + epilogue of a patch-shape blo
 
 def _lpt_makespan(blocks: List[Tuple[float, int]], cus: int = _CUS) -> float:
     """Makespan of (duration, count) block classes handed out longest first to ``cus`` one-block-at-a-time workers."""
-    import heapq
     free = [0.0] * cus
     for dur, cnt in sorted(blocks, reverse=True):
         for _ in range(cnt):
@@ -2050,7 +2114,6 @@ def plan_group_ksplit(members: Sequence[Tuple[int, int]]) -> Tuple[int, ...]:
     hit = _GROUP_PLANS.get(key)
     if hit is not None:
         return hit
-    import itertools
     options = []
     for tiles, chunks in members:
         ks = sorted({k for k in range(1, min(chunks, 16) + 1) if (chunks + k - 1) // k != (chunks + k - 2) // max(k - 1, 1) or k == 1})
@@ -2074,9 +2137,22 @@ def plan_group_ksplit(members: Sequence[Tuple[int, int]]) -> Tuple[int, ...]:
     return best
 
 
-class _LstmMember:
-    """Per-member state of ConvLSTMGroup (what ConvLSTMSeq keeps in locals)."""
-    pass
+def _group_shapes_ok(ms) -> bool:
+    """Can 2 to 4 layers' step GEMMs take the patch shape together?  ``ms``: (x [..., B,H,W,Cxp], weight, Hd) per layer: one dtype, 3x3
+    gate convolution, channel counts multiples of 64 (no padded hidden channels), B*H*W a multiple of 256."""
+    if not GROUP_LSTM or not 2 <= len(ms) <= 4:
+        return False
+    for x, weight, Hd in ms:
+        B, H, W, Cxp = x.shape[-4:]
+        if x.dtype != ms[0][0].dtype or weight.shape[-1] != 3 or cpad(Hd) != Hd or Hd % 64 or Cxp % 64 or (B * H * W) % 256:
+            return False
+    return True
+
+
+def _group_split(ms) -> None:
+    """K ranges of every layer of a group from plan_group_ksplit."""
+    for m, ksplit in zip(ms, plan_group_ksplit([m.group_plan_input for m in ms])):
+        m.split(ksplit)
 
 
 def convlstm_group_forward(members, need_grad: bool):
@@ -2088,56 +2164,11 @@ def convlstm_group_forward(members, need_grad: bool):
     the side stream together at the end instead of each overlapping the next LSTM's backward recurrence.)
     Same arithmetic as ConvLSTMSeq: a member's step is the fused cell kernel or split-K slabs + the point-wise kernel; only the
     K-range counts are planned for the group (plan_group_ksplit), i.e. results agree to f32 summation order of the K ranges."""
-    ms = []
-    for x_all, h0, c0, weight, bias, Hd, Cx in members:
-        m = _LstmMember()
-        m.x_all, m.h0, m.c0, m.weight, m.bias, m.Hd, m.Cx = x_all, h0, c0, weight, bias, Hd, Cx
-        _dev(m.x_all, ACT, "x_all")
-        m.T, m.B, m.H, m.W, m.Cxp = m.x_all.shape
-        m.Hdp = cpad(Hd)
-        m.pixels = m.B * m.H * m.W
-        m.pd = lstm_pack_desc(Hd, Cx, 3)
-        m.bp = pack_bias(m.pd, m.bias) if m.bias is not None else None
-        m.wp = pack_weights(m.pd, m.weight, 0, m.x_all.dtype)
-        ms.append(m)
-    T, adt, dev = ms[0].T, ms[0].x_all.dtype, ms[0].x_all.device
-    K = L.kernels(adt)
-    plan = plan_group_ksplit([(((m.wp.shape[0] + 127) // 128) * (m.pixels // 256), m.wp.shape[1] // (64 * 9)) for m in ms])
-    for m, ks in zip(ms, plan):
-        m.h_hist = torch.empty((T + 1, m.B, m.H, m.W, m.Hdp), dtype=adt, device=dev)
-        m.c_hist = torch.empty((T + 1, m.B, m.H, m.W, m.Hdp), dtype=F32, device=dev)
-        if m.h0 is None:
-            m.h_hist[0].zero_()
-        else:
-            m.h_hist[0].copy_(m.h0)
-        if m.c0 is not None:
-            m.c_hist[0].copy_(m.c0)
-        m.gates = torch.empty((T, m.B, m.H, m.W, 4, m.Hdp), dtype=adt, device=dev) if need_grad else None
-        m.ksplit = ks
-        m.nsl = ksplit_used(m.wp.shape[1], ks, 3) if ks > 1 else 0
-        m.pre = torch.empty((m.nsl, m.pixels, m.wp.shape[0]), dtype=F32, device=dev) if ks > 1 else None
-    for t in range(T):
-        items, pws = [], []
-        for m in ms:
-            c_prev = m.c_hist[t] if (m.c0 is not None or t > 0) else None
-            g_t = m.gates[t] if need_grad else None
-            if m.ksplit > 1:
-                items.append(_atomic_desc([SrcView(m.x_all[t]), SrcView(m.h_hist[t])], m.wp, (m.H, m.W), m.B, m.pre, m.ksplit, ktap=3, pad=1,
-                                          slabs=True))
-                a = L.LstmFwdPwArgs()
-                a.pre, a.nslab, a.slab, a.clear, a.pre_add = m.pre.data_ptr(), m.nsl, m.pre.stride(0), 0, None
-                a.bias = None if m.bp is None else m.bp.data_ptr()
-                a.c_prev = None if c_prev is None else c_prev.data_ptr()
-                a.c_out, a.h_out = m.c_hist[t + 1].data_ptr(), m.h_hist[t + 1].data_ptr()
-                a.gates_out = None if g_t is None else g_t.data_ptr()
-                a.pixels, a.Hd_p = m.pixels, m.Hdp
-                pws.append(a)
-            else:
-                items.append(_lstm_desc(m.x_all[t], m.h_hist[t], m.wp, m.bp, c_prev, m.c_hist[t + 1], m.h_hist[t + 1], g_t, 3))
-        igemm_group(items, K)
-        if pws:
-            arr = (L.LstmFwdPwArgs * len(pws))(*pws)
-            L.check(K.uclstm_lstm_fwd_pointwise_group(arr, len(pws), _stream()), "lstm_fwd_pointwise_group")
+    ms = [_LstmLayerFwd(*mem, need_grad, in_place=False) for mem in members]       # the caller gets the histories: slot 0 is the state
+    _group_split(ms)
+    K = _k(ms[0].x_all)
+    for t in range(ms[0].T):
+        _lstm_launch_group(K, [m.step(t) for m in ms])
     if RECURRENCE_TRACE is not None:
         for m in ms:
             RECURRENCE_TRACE.append(("fwd", m.h_hist, m.c_hist, m.gates))
@@ -2149,45 +2180,17 @@ def convlstm_group_step(members) -> bool:
     BASELINE configs[4]).  ``members``: (x_t [B,H,W,Cxp], h_prev, c_prev, h_out, c_out, weight, bias, Hd, Cx); the new state is
     written into h_out / c_out (h_out must not alias h_prev; c_out may be c_prev).  Returns False -- nothing launched -- when the
     members cannot form a group (the caller then steps them one by one)."""
-    if not GROUP_LSTM or not 2 <= len(members) <= 4:
+    if not _group_shapes_ok([(mem[0], mem[5], mem[7]) for mem in members]):
         return False
-    ms = []
-    for x_t, h_prev, c_prev, h_out, c_out, weight, bias, Hd, Cx in members:
-        if (weight.shape[-1] != 3 or cpad(Hd) != Hd or Hd % 64 or x_t.shape[3] % 64 or (x_t.shape[0] * x_t.shape[1] * x_t.shape[2]) % 256
-                or h_prev is None or c_prev is None or h_out.data_ptr() == h_prev.data_ptr() or x_t.dtype != members[0][0].dtype):
-            return False
-        m = _LstmMember()
-        m.x_t, m.h_prev, m.c_prev, m.h_out, m.c_out, m.Hd = x_t, h_prev, c_prev, h_out, c_out, Hd
-        m.B, m.H, m.W, _ = x_t.shape
-        m.pixels = m.B * m.H * m.W
-        m.pd = lstm_pack_desc(Hd, Cx, 3)
-        m.bp = pack_bias(m.pd, bias) if bias is not None else None
-        m.wp = pack_weights(m.pd, weight, 0, x_t.dtype)
-        ms.append(m)
-    adt, dev = ms[0].x_t.dtype, ms[0].x_t.device
-    K = L.kernels(adt)
-    plan = plan_group_ksplit([(((m.wp.shape[0] + 127) // 128) * (m.pixels // 256), m.wp.shape[1] // (64 * 9)) for m in ms])
-    items, pws, keep = [], [], []
-    for m, ks in zip(ms, plan):
-        if ks > 1:
-            nsl = ksplit_used(m.wp.shape[1], ks, 3)
-            pre = torch.empty((nsl, m.pixels, m.wp.shape[0]), dtype=F32, device=dev)
-            keep.append(pre)
-            items.append(_atomic_desc([SrcView(m.x_t), SrcView(m.h_prev)], m.wp, (m.H, m.W), m.B, pre, ks, ktap=3, pad=1, slabs=True))
-            a = L.LstmFwdPwArgs()
-            a.pre, a.nslab, a.slab, a.clear, a.pre_add = pre.data_ptr(), nsl, pre.stride(0), 0, None
-            a.bias = None if m.bp is None else m.bp.data_ptr()
-            a.c_prev, a.c_out, a.h_out, a.gates_out = m.c_prev.data_ptr(), m.c_out.data_ptr(), m.h_out.data_ptr(), None
-            a.pixels, a.Hd_p = m.pixels, m.Hd
-            pws.append(a)
-        else:
-            items.append(_lstm_desc(m.x_t, m.h_prev, m.wp, m.bp, m.c_prev, m.c_out, m.h_out, None, 3))
-    if not group_launchable([it[0] for it in items]):
+    if any(h_prev is None or c_prev is None or h_out.data_ptr() == h_prev.data_ptr() for _, h_prev, c_prev, h_out, *_ in members):
         return False
-    igemm_group(items, K)
-    if pws:
-        arr = (L.LstmFwdPwArgs * len(pws))(*pws)
-        L.check(K.uclstm_lstm_fwd_pointwise_group(arr, len(pws), _stream()), "lstm_fwd_pointwise_group")
+    ms = [_LstmLayerFwd(x_t.unsqueeze(0), h_prev, c_prev, weight, bias, Hd, Cx, False, (h_out, c_out))
+          for x_t, h_prev, c_prev, h_out, c_out, weight, bias, Hd, Cx in members]
+    _group_split(ms)
+    steps = [m.step(0) for m in ms]
+    if not group_launchable([item[0] for item, _ in steps]):
+        return False
+    _lstm_launch_group(_k(ms[0].x_all), steps)
     return True
 
 
@@ -2211,31 +2214,19 @@ class ConvLSTMSeqPre(torch.autograd.Function):
 
 
 def convlstm_group_ok(members) -> bool:
-    """Can these (x_all, h0, c0, weight, bias, Hd, Cx) single-layer ConvLSTMs run as ConvLSTMGroup?  Every per-step GEMM must
-    take the patch shape (3x3 gate convolution, channel counts multiples of 64, B*h*w a multiple of 256, ...) -- checked with the
-    library's own planner on the step-0 descriptors -- and all members share T, B and the activation dtype."""
-    if not GROUP_LSTM or len(members) < 2 or len(members) > 4:
-        return False
-    x0 = members[0][0]
+    """Can these (x_all, h0, c0, weight, bias, Hd, Cx) single-layer ConvLSTMs run through convlstm_group_forward?  Every per-step
+    GEMM must take the patch shape (_group_shapes_ok) -- checked with the library's own planner on the step-0 descriptors -- and all
+    members share T, B and the activation dtype."""
     try:
+        x0 = members[0][0]
+        if any(m[0].dim() != 5 or m[0].shape[:2] != x0.shape[:2] for m in members) or not _group_shapes_ok([(m[0], m[3], m[5]) for m in members]):
+            return False
         descs = []
         for x_all, h0, c0, weight, bias, Hd, Cx in members:
-            if x_all.dim() != 5 or x_all.shape[0] != x0.shape[0] or x_all.shape[1] != x0.shape[1] or x_all.dtype != x0.dtype:
-                return False
-            if weight.shape[-1] != 3 or cpad(Hd) != Hd or Hd % 64 or x_all.shape[4] % 64 or (x_all.shape[1] * x_all.shape[2] * x_all.shape[3]) % 256:
-                return False
             T, B, H, W, Cxp = x_all.shape
             pd = lstm_pack_desc(Hd, Cx, 3)
-            # a descriptor with the right shapes (the planner does not dereference the pointers): x_t, h, panel geometry
-            d = L.IgemmDesc()
-            d.n_img, d.H, d.W, d.groups = B, H, W, 1
-            d.ktap, d.scale, d.pad, d.nsrc = 3, 1, 1, 2
-            for i, cch in enumerate((Cxp, Hd)):
-                d.src[i].ptr, d.src[i].C, d.src[i].Hs, d.src[i].Ws = x_all.data_ptr(), cch, H, W
-            d.wp, d.N, d.Ktot = x_all.data_ptr(), pd.N, pd.Ktot
-            d.epi, d.Hd_p = L.EPI_LSTM, Hd
-            d.c_out = d.h_out = x_all.data_ptr()
-            descs.append(d)
+            # the step's descriptor with the right shapes (the planner does not dereference the pointers): x_t, h, panel geometry
+            descs.append(_lstm_desc(*(None,) * 8, 3, probe=(B, H, W, (Cxp, Hd), pd.N, pd.Ktot, x_all.data_ptr()))[0])
         return group_launchable(descs)
     except Exception:
         return False
