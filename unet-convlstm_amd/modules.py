@@ -147,15 +147,9 @@ class DoubleConv(nn.Module):
             mom = -float(int(bn.num_batches_tracked) + 1)
         else:
             mom = 0.0
-        if head is not None:
-            a = ops.ConvBNReLU.apply(x0, x1, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                     tuple(c_valid), tuple(off), groups, training, mom, bn.eps, im2col, head.weight, head.bias)
-        elif pool:
-            a = ops.ConvBNReLU.apply(x0, x1, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                     tuple(c_valid), tuple(off), groups, training, mom, bn.eps, im2col, None, None, True)
-        else:
-            a = ops.ConvBNReLU.apply(x0, x1, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                     tuple(c_valid), tuple(off), groups, training, mom, bn.eps, im2col)
+        head_w, head_b = (None, None) if head is None else (head.weight, head.bias)
+        a = ops.ConvBNReLU.apply(x0, x1, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                 tuple(c_valid), tuple(off), groups, training, mom, bn.eps, im2col, head_w, head_b, bool(pool) and head is None)
         if training and bn.num_batches_tracked is not None:
             if _DEFERRED_COUNTERS is not None:
                 _DEFERRED_COUNTERS.append((bn.num_batches_tracked, groups))      # one multi-tensor add per model forward

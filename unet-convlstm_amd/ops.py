@@ -627,8 +627,8 @@ def prepack_begin() -> None:
         for key in _PACK_BATCH.panels:
             _PACK_READY[key] = _PACK_BATCH
         return
-    side.wait_stream(main)                       # the optimiser step that produced these weights
-    with torch.cuda.stream(side):
+
+    def pack_all():
         for key, desc, w, off in plan:
             if key in _PACK_READY or w.data_ptr() != key[0]:
                 continue
@@ -638,6 +638,8 @@ def prepack_begin() -> None:
             ev = torch.cuda.Event()
             ev.record(side)
             _PACK_READY[key] = (wp, ev)
+
+    _on_side(dev, pack_all)                      # after the optimiser step that produced these weights
 
 
 def prepack_end() -> None:
@@ -830,29 +832,39 @@ def _schedule_join(device) -> None:
     torch.autograd.Variable._execution_engine.queue_callback(join)
 
 
+def _on_side(device, launch, keep=()) -> None:
+    """``launch()`` with the side stream current, after everything enqueued on the current stream so far.  ``keep``: the tensors
+    (or None) it reads, which the caching allocator must not recycle under the side stream.  The caller says where the current
+    stream joins again: ``_FWD_SIDE_PENDING`` in a forward pass, ``_schedule_join`` in a backward pass."""
+    side = side_stream(device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        launch()
+        for t in keep:
+            if t is not None:
+                t.record_stream(side)
+
+
 def wgrad_into_param(weight: torch.Tensor, desc: L.PackDesc, inputs: Sequence[torch.Tensor], run_gemm) -> Optional[torch.Tensor]:
     """Weight gradient of one layer.  ``run_gemm()`` launches the weight-gradient GEMM and returns the f32 panel.
     Returns the gradient tensor for autograd, or ``None`` after accumulating into ``weight.grad`` on the side stream."""
     g = weight.grad
     if not (ASYNC_WGRAD and g is not None and g.dtype == F32 and g.is_contiguous() and g.shape == weight.shape):
         return unpack_wgrad(desc, run_gemm(), weight)
-    dev = weight.device
-    main, side = torch.cuda.current_stream(dev), side_stream(dev)
-    side.wait_stream(main)                      # dz / activations produced so far are visible to the side stream
-    global _WGRAD_OVERLAPPED
-    with torch.cuda.stream(side):
+
+    def launch():
+        global _WGRAD_OVERLAPPED
         _WGRAD_OVERLAPPED = True
         try:
             dwp = run_gemm()
         finally:
             _WGRAD_OVERLAPPED = False
         _unpack_wgrad_launch(desc, dwp, g, 1)           # (scratch of the ordered form: allocated and freed under the side stream)
-        for t in inputs:
-            if t is not None:
-                t.record_stream(side)           # the caching allocator must not recycle them under the side stream
         for hook in GRAD_SIDE_HOOKS:
             hook(weight)
-    _schedule_join(dev)
+
+    _on_side(weight.device, launch, inputs)
+    _schedule_join(weight.device)
     return None
 
 
@@ -865,6 +877,18 @@ def direct_grad(param: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     if g is None or g.dtype != F32 or not g.is_contiguous() or g.shape != param.shape:
         return None
     return g
+
+
+def direct_grad_pair(weight: torch.Tensor, bias: Optional[torch.Tensor], need_w: bool, need_b: bool):
+    """``(weight.grad, bias.grad)`` where ONE kernel that adds into both may write the two gradients directly, else ``None``
+    (the kernel then gets scratch buffers and autograd the results).  All or nothing: both trainable and both with an attached
+    buffer (``direct_grad``); an absent bias does not stand in the way."""
+    if not (need_w and (need_b or bias is None)):
+        return None
+    gw, gb = direct_grad(weight), direct_grad(bias)
+    if gw is None or (bias is not None and gb is None):
+        return None
+    return gw, gb
 
 
 def grad_written(param: torch.Tensor) -> None:
@@ -1353,6 +1377,69 @@ def _will_backward(ctx) -> bool:
     return _OUTER_GRAD and any(ctx.needs_input_grad)
 
 
+def _conv_geometry(x0, x1, weight, c_valid, off, im2col):
+    """(pack descriptor, sources, ktap, pad) of the stage's convolution, for the forward GEMM and the weight gradient alike:
+    the pre-gathered first layer as a plain GEMM, or 3x3 taps over one or two sources."""
+    Co, Ci_total = weight.shape[0], weight.shape[1]
+    if im2col:
+        return im2col_pack_desc(Co, Ci_total, x0.shape[3]), [SrcView(x0)], 1, 0
+    if x1 is None:
+        return conv_pack_desc(Co, Ci_total, list(c_valid), [x0.shape[3]]), [SrcView(x0)], 3, 1
+    return conv_pack_desc(Co, Ci_total, list(c_valid), [x0.shape[3], x1.shape[3]]), [SrcView(x0), SrcView(x1, off[0], off[1])], 3, 1
+
+
+def _bn_forward_stats(stats, n_img, H, W, groups, Co, gamma, beta, running_mean, running_var, momentum, eps, variant):
+    """From the convolution's partial sums ``stats`` [groups, tiles, Cop, 2] to ``par`` = (scale, shift, mean, rstd), each
+    [groups, Cop], and the running-statistics update.  ``stats`` None: frozen statistics, par from the running ones.
+    Returns (par, sync): sync = (process group, world size) where the statistics are those of all ranks (the sync_batchnorm
+    switch; ``variant`` goes to LAUNCH_LOG), else None."""
+    Cop = cpad(Co)
+    par = torch.empty((4, groups, Cop), dtype=F32, device=gamma.device)
+    pp = (_p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]))
+    if stats is None:
+        L.check(L.lib.uclstm_bn_finalize(None, 1, 0, Cop, Co, 0, _p(gamma), _p(beta), _p(running_mean), _p(running_var), momentum, eps,
+                                         *pp, _stream()), "bn_finalize(eval)")
+        return par, None
+    tpg, ppg = stats.shape[1], (n_img // groups) * H * W
+    sync, count, on_side = None, ppg, ASYNC_WGRAD and BN_RUNNING_ON_SIDE
+    if _SYNC_BN:
+        # statistics over all ranks: f64 sums of this rank -> all-reduce -> scale / shift / mean / rstd from the sums of
+        # all ranks.  `stats` then holds (mean, variance) of the global batch in its tile-0 slots, and the running
+        # statistics below are updated from them with the global count.
+        if torch.cuda.is_current_stream_capturing():
+            raise L.UclstmError("sync_batchnorm: a step with collectives cannot be captured in a HIP graph")
+        world = _sync_bn_check_equal(_SYNC_BN_GROUP, n_img, H, W, groups)
+        sync, count = (_SYNC_BN_GROUP, world), world * ppg
+        sums64 = torch.empty((groups, Cop, 2), dtype=torch.float64, device=gamma.device)
+        if LAUNCH_LOG is not None:
+            LAUNCH_LOG.append(("syncbn", "bn_stats_partial", variant))
+        L.check(L.lib.uclstm_bn_stats_partial(_p(stats), groups, tpg, Cop, _p(sums64), _stream()), "bn_stats_partial")
+        _sync_bn_all_reduce(sums64, _SYNC_BN_GROUP, "bn_stats")
+        if LAUNCH_LOG is not None:
+            LAUNCH_LOG.append(("syncbn", "bn_stats_from_sums", variant))
+        L.check(L.lib.uclstm_bn_stats_from_sums(_p(sums64), count, _p(stats), groups, tpg, Cop, Co, _p(gamma), _p(beta), eps, *pp, _stream()),
+                "bn_stats_from_sums")
+    elif on_side and not torch.cuda.is_current_stream_capturing():
+        # critical part in one launch (reduction + scale / shift / mean / rstd); the in-order running-statistics recursion,
+        # which nothing in this step waits for, on the second stream (joined at the end of the forward pass: join_forward_side)
+        L.check(L.lib.uclstm_bn_stats_fwd(_p(stats), groups, tpg, Cop, Co, ppg, _p(gamma), _p(beta), eps, *pp, _stream()), "bn_stats_fwd")
+    else:
+        L.check(L.lib.uclstm_bn_finalize(_p(stats), groups, tpg, Cop, Co, ppg, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+                                         momentum, eps, *pp, _stream()), "bn_finalize")
+        return par, None
+
+    def running_stats():          # the one-launch route's counterpart: the same momentum steps
+        L.check(L.lib.uclstm_bn_running_stats(_p(stats), groups, tpg, Cop, Co, count, _p(running_mean), _p(running_var), momentum,
+                                              _stream()), "bn_running_stats")
+
+    if on_side:
+        _on_side(gamma.device, running_stats, (stats,))
+        _FWD_SIDE_PENDING.add(str(gamma.device))
+    else:
+        running_stats()
+    return par, sync
+
+
 class ConvBNReLU(_GradAwareFunction):
     """One (conv3x3 pad 1 + bias -> BatchNorm2d -> ReLU) stage on NHWC bf16.
 
@@ -1370,85 +1457,40 @@ class ConvBNReLU(_GradAwareFunction):
         # head_w / head_b: the model's 1x1 output convolution (ONE output channel) fused into this stage (training mode only,
         # uclstm_bn_head_*): the stage then returns y f32 [n_img, 1, H, W] instead of its activation, which never exists.
         _dev(x0, ACT, "x0")
-        Co, Ci_total = weight.shape[0], weight.shape[1]
-        Cop = cpad(Co)
-        n_img, H, W, _ = x0.shape
-        dev = x0.device
-        if im2col:
-            pd = im2col_pack_desc(Co, Ci_total, x0.shape[3])
-            srcs = [SrcView(x0)]
-            ktap, pad = 1, 0
-        else:
-            c_pad = [x0.shape[3]] + ([x1.shape[3]] if x1 is not None else [])
-            pd = conv_pack_desc(Co, Ci_total, list(c_valid), c_pad)
-            srcs = [SrcView(x0)] + ([SrcView(x1, off[0], off[1])] if x1 is not None else [])
-            ktap, pad = 3, 1
+        Co, Ci_total, Cop = weight.shape[0], weight.shape[1], cpad(weight.shape[0])
+        (n_img, H, W, _), dev = x0.shape, x0.device
+        if head_w is not None and not training:
+            raise L.UclstmError("ConvBNReLU: the fused output head is a training-mode path")
+        # which BatchNorm kernels the stage takes, decided here once: the fused head, the fused pooling (training mode, even
+        # sizes, at most 256 channel chunks per pixel: uclstm_bn_pool_bwd_rows refuses more) or the plain ones
+        variant = "head" if head_w is not None else \
+            "pool" if (pool and training and H % 2 == 0 and W % 2 == 0 and Cop // 8 <= 256) else "plain"
+        pd, srcs, ktap, pad = _conv_geometry(x0, x1, weight, c_valid, off, im2col)
         wp = pack_weights(pd, weight, 0, x0.dtype)
         bp = pack_bias(pd, bias) if bias is not None else None
         out = torch.empty((n_img, H, W, Cop), dtype=x0.dtype, device=dev)
         K = _k(x0)
         need_bw = _will_backward(ctx)
-        pooled = None
-        sync = None                     # (process group, world size) where this stage's statistics are those of all ranks
-        if training:
-            ppg = (n_img // groups) * H * W
-            tpg = L.lib.uclstm_igemm_tiles_per_group(n_img, H, W, groups, Cop)
-            stats = torch.empty((groups, tpg, Cop, 2), dtype=F32, device=dev)
+        pooled = sync = None            # sync: (process group, world size) where this stage's statistics are those of all ranks
+        if training or need_bw:
+            stats = None
+            if training:
+                stats = torch.empty((groups, L.lib.uclstm_igemm_tiles_per_group(n_img, H, W, groups, Cop), Cop, 2), dtype=F32, device=dev)
+            else:
+                # evaluation-mode statistics WITH a backward pass (fine-tuning through frozen BatchNorm): keep the pre-BN conv
+                # output like the training path does, normalise with the running statistics as one group
+                join_forward_side(dev)
+                groups = 1
+            pixels, ppg = n_img * H * W, (n_img // groups) * H * W
             z = out
             igemm_store(srcs, wp, (H, W), n_img, [(z, 0, Cop, 0, 1, 0, 0)], ktap=ktap, pad=pad, groups=groups, bias=bp, stats=stats)
-            par = torch.empty((4, groups, Cop), dtype=F32, device=dev)     # scale, shift, mean, rstd
-            if _SYNC_BN:
-                # statistics over all ranks: f64 sums of this rank -> all-reduce -> scale / shift / mean / rstd from the sums of
-                # all ranks.  `stats` then holds (mean, variance) of the global batch in its tile-0 slots, and the running
-                # statistics below are updated from them with the global count.
-                if torch.cuda.is_current_stream_capturing():
-                    raise L.UclstmError("sync_batchnorm: a step with collectives cannot be captured in a HIP graph")
-                variant = "head" if head_w is not None else ("pool" if (pool and H % 2 == 0 and W % 2 == 0 and Cop // 8 <= 256) else "plain")
-                world = _sync_bn_check_equal(_SYNC_BN_GROUP, n_img, H, W, groups)
-                sync = (_SYNC_BN_GROUP, world)
-                sums64 = torch.empty((groups, Cop, 2), dtype=torch.float64, device=dev)
-                if LAUNCH_LOG is not None:
-                    LAUNCH_LOG.append(("syncbn", "bn_stats_partial", variant))
-                L.check(L.lib.uclstm_bn_stats_partial(_p(stats), groups, tpg, Cop, _p(sums64), _stream()), "bn_stats_partial")
-                _sync_bn_all_reduce(sums64, _SYNC_BN_GROUP, "bn_stats")
-                if LAUNCH_LOG is not None:
-                    LAUNCH_LOG.append(("syncbn", "bn_stats_from_sums", variant))
-                L.check(L.lib.uclstm_bn_stats_from_sums(_p(sums64), world * ppg, _p(stats), groups, tpg, Cop, Co, _p(gamma), _p(beta), eps,
-                                                        _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _stream()), "bn_stats_from_sums")
-                if ASYNC_WGRAD and BN_RUNNING_ON_SIDE:
-                    main, side = torch.cuda.current_stream(dev), side_stream(dev)
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side):
-                        L.check(L.lib.uclstm_bn_running_stats(_p(stats), groups, tpg, Cop, Co, world * ppg, _p(running_mean),
-                                                              _p(running_var), momentum, _stream()), "bn_running_stats")
-                        stats.record_stream(side)
-                    _FWD_SIDE_PENDING.add(str(dev))
-                else:
-                    # the one-launch route's counterpart: the same momentum steps, on the main stream
-                    L.check(L.lib.uclstm_bn_running_stats(_p(stats), groups, tpg, Cop, Co, world * ppg, _p(running_mean), _p(running_var),
-                                                          momentum, _stream()), "bn_running_stats")
-            elif ASYNC_WGRAD and BN_RUNNING_ON_SIDE and not torch.cuda.is_current_stream_capturing():
-                # critical part in one launch (reduction + scale / shift / mean / rstd); the in-order running-statistics recursion,
-                # which nothing in this step waits for, on the second stream (joined at the end of the forward pass: join_forward_side)
-                L.check(L.lib.uclstm_bn_stats_fwd(_p(stats), groups, tpg, Cop, Co, ppg, _p(gamma), _p(beta), eps, _p(par[0]), _p(par[1]),
-                                                  _p(par[2]), _p(par[3]), _stream()), "bn_stats_fwd")
-                main, side = torch.cuda.current_stream(dev), side_stream(dev)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    L.check(L.lib.uclstm_bn_running_stats(_p(stats), groups, tpg, Cop, Co, ppg, _p(running_mean), _p(running_var), momentum,
-                                                          _stream()), "bn_running_stats")
-                    stats.record_stream(side)
-                _FWD_SIDE_PENDING.add(str(dev))
-            else:
-                L.check(L.lib.uclstm_bn_finalize(_p(stats), groups, tpg, Cop, Co, ppg, _p(gamma), _p(beta), _p(running_mean),
-                                                 _p(running_var), momentum, eps, _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]),
-                                                 _stream()), "bn_finalize")
-            if head_w is not None:
+            par, sync = _bn_forward_stats(stats, n_img, H, W, groups, Co, gamma, beta, running_mean, running_var, momentum, eps, variant)
+            if variant == "head":
                 a = torch.empty((n_img, 1, H, W), dtype=F32, device=dev)
-                _timed_hbm("bn_head_fwd", 2.0 * z.numel() + 4.0 * n_img * H * W,
-                           lambda: L.check(K.uclstm_bn_head_fwd(_p(z), _p(par[0]), _p(par[1]), _p(head_w), _p(head_b), _p(a), n_img * H * W, ppg,
+                _timed_hbm("bn_head_fwd", 2.0 * z.numel() + 4.0 * pixels,
+                           lambda: L.check(K.uclstm_bn_head_fwd(_p(z), _p(par[0]), _p(par[1]), _p(head_w), _p(head_b), _p(a), pixels, ppg,
                                                                 Cop, Co, _stream()), "bn_head_fwd"))
-            elif pool and H % 2 == 0 and W % 2 == 0 and Cop // 8 <= 256:
+            elif variant == "pool":
                 a = torch.empty_like(z)
                 pooled = torch.empty((n_img, H // 2, W // 2, Cop), dtype=z.dtype, device=dev)
                 _timed_hbm("bn_apply_relu_pool", 4.5 * z.numel(),
@@ -1457,28 +1499,11 @@ class ConvBNReLU(_GradAwareFunction):
             else:
                 a = torch.empty_like(z)
                 _timed_hbm("bn_apply_relu", 4.0 * z.numel(),        # 2 B read + 2 B written per element
-                           lambda: L.check(K.uclstm_bn_apply_relu(_p(z), _p(a), _p(par[0]), _p(par[1]), n_img * H * W, ppg, Cop, _stream()),
+                           lambda: L.check(K.uclstm_bn_apply_relu(_p(z), _p(a), _p(par[0]), _p(par[1]), pixels, ppg, Cop, _stream()),
                                            "bn_apply_relu"))
             ctx.save_for_backward(x0, x1, weight, z, par, gamma, beta, bias, head_w, head_b)
             if need_bw:
                 note_use(weight, gamma, beta, bias, head_w, head_b)
-        elif head_w is not None:
-            raise L.UclstmError("ConvBNReLU: the fused output head is a training-mode path")
-        elif need_bw:
-            join_forward_side(dev)
-            # evaluation-mode statistics WITH a backward pass (fine-tuning through frozen BatchNorm): keep the pre-BN conv
-            # output like the training path does, normalise with the running statistics as one group
-            groups = 1
-            z = out
-            igemm_store(srcs, wp, (H, W), n_img, [(z, 0, Cop, 0, 1, 0, 0)], ktap=ktap, pad=pad, groups=1, bias=bp)
-            par = torch.empty((4, 1, Cop), dtype=F32, device=dev)
-            L.check(L.lib.uclstm_bn_finalize(None, 1, 0, Cop, Co, 0, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
-                                             momentum, eps, _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _stream()), "bn_finalize(eval)")
-            a = torch.empty_like(z)
-            L.check(K.uclstm_bn_apply_relu(_p(z), _p(a), _p(par[0]), _p(par[1]), n_img * H * W, n_img * H * W, Cop, _stream()),
-                    "bn_apply_relu")
-            ctx.save_for_backward(x0, x1, weight, z, par, gamma, beta, bias, None, None)
-            note_use(weight, gamma, beta, bias)
         else:
             join_forward_side(dev)
             par = _eval_bn_constants(gamma, beta, running_mean, running_var, eps, momentum, Co, Cop)
@@ -1487,55 +1512,47 @@ class ConvBNReLU(_GradAwareFunction):
                         col_scale=par[0], col_shift=par[1], relu=True)
             ctx.save_for_backward(x0, x1, weight, None, None, gamma, beta, bias, None, None)
         ctx.cfg = (tuple(c_valid), tuple(off), groups, training, im2col, Co, Ci_total, bias is not None)
-        ctx.pool = bool(pool)
-        ctx.sync_bn = sync
-        if pool:
-            ctx.pool_fused = pooled is not None
-            if pooled is None:          # evaluation mode, odd sizes: the stand-alone pooling kernel on the finished activation
-                pooled = torch.empty((n_img, H // 2, W // 2, Cop), dtype=a.dtype, device=dev)
-                L.check(K.uclstm_maxpool2_fwd(_p(a), _p(pooled), n_img, H, W, Cop, _stream()), "maxpool2_fwd")
-                if need_bw:
-                    ctx.pool_act = a
-            return a, pooled
-        return a
+        ctx.variant, ctx.sync_bn, ctx.pool_act = variant, sync, None
+        if not pool:
+            return a
+        if variant != "pool":           # evaluation mode, odd sizes: the stand-alone pooling kernel on the finished activation
+            pooled = _maxpool2_fwd(a)
+            if need_bw:
+                ctx.pool_act = a
+        return a, pooled
 
     @staticmethod
-    def backward(ctx, da, dp=None):
-        x0, x1, weight, z, par, gamma, beta, bias, head_w, head_b = ctx.saved_tensors
-        c_valid, off, groups, training, im2col, Co, Ci_total, has_bias = ctx.cfg
-        n_img, H, W, Cop = z.shape
-        dev = z.device
+    def _bn_backward(ctx, z, par, head_w, head_b, da, dp):
+        """Part 1: (dz, sums, d_head_w, d_head_b) -- the gradient of the conv output and the per-group sums (dbeta, dgamma)."""
+        groups, training, Co = ctx.cfg[2], ctx.cfg[3], ctx.cfg[5]
+        (n_img, H, W, Cop), dev = z.shape, z.device
         pixels, ppg = n_img * H * W, (n_img // groups) * H * W
         sums = torch.empty((groups, Cop, 2), dtype=F32, device=dev)
         partials = torch.empty((int(L.lib.uclstm_bn_bwd_reduce_rows(pixels, ppg)), Cop, 2), dtype=F32, device=dev)
         K = _k(z)
         dz = torch.empty_like(z)
+        pz, pq = _p(z), (_p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]))
         d_head_w = d_head_b = None
-        if head_w is not None:
+        variant = ctx.variant if (ctx.variant != "pool" or dp is not None) else "plain"          # pooled output unused
+        if variant == "head":
             # fused output head: `da` is dy f32 [n_img, 1, H, W]; the activation gradient bf16(dy * w) is formed on the fly
             dy = _dev(da.contiguous().float(), F32, "dy")
-            gw, gb = direct_grad(head_w), (direct_grad(head_b) if head_b is not None else None)
-            direct = gw is not None and gw.is_contiguous() and (head_b is None or gb is not None)
-            dwh = gw if direct else torch.zeros_like(head_w, memory_format=torch.contiguous_format)
-            dbh = gb if (direct and head_b is not None) else torch.zeros((1,), dtype=F32, device=dev)
+            direct = direct_grad_pair(head_w, head_b, ctx.needs_input_grad[15], ctx.needs_input_grad[16])
+            dwh = direct[0] if direct else torch.zeros_like(head_w, memory_format=torch.contiguous_format)
+            dbh = direct[1] if (direct and head_b is not None) else torch.zeros((1,), dtype=F32, device=dev)
             if _DETERMINISTIC:
                 # the head's Co + 1 columns go through partial rows of their own and are finished in row order (dwh / dbh keep +=)
                 head_partials = torch.empty((partials.shape[0], Co + 1), dtype=F32, device=dev)
                 _log_reduce("bn_head_bwd_reduce_ordered")
                 _timed_hbm("bn_head_bwd_reduce", 2.0 * z.numel() + 4.0 * pixels,
                            lambda: L.check(L.lib.uclstm_bn_head_bwd_reduce_ordered(
-                               _p(z), _p(dy), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(head_w), _p(partials), _p(head_partials),
+                               pz, _p(dy), *pq, _p(head_w), _p(partials), _p(head_partials),
                                _p(sums), _p(dwh), _p(dbh), pixels, ppg, Cop, Co, L.act_type(z.dtype), _stream()), "bn_head_bwd_reduce_ordered"))
             else:
                 _log_reduce("bn_head_bwd_reduce")
                 _timed_hbm("bn_head_bwd_reduce", 2.0 * z.numel() + 4.0 * pixels,
-                           lambda: L.check(K.uclstm_bn_head_bwd_reduce(_p(z), _p(dy), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(head_w),
-                                                                       _p(partials), _p(sums), _p(dwh), _p(dbh), pixels, ppg, Cop, Co, _stream()),
-                                           "bn_head_bwd_reduce"))
-            sums_dz = sums if ctx.sync_bn is None else _bn_bwd_sums_over_ranks(sums, ctx.sync_bn, "head")
-            _timed_hbm("bn_head_bwd_apply", 4.0 * z.numel() + 4.0 * pixels,
-                       lambda: L.check(K.uclstm_bn_head_bwd_apply(_p(z), _p(dy), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(sums_dz),
-                                                                  _p(head_w), _p(dz), pixels, ppg, Cop, Co, _stream()), "bn_head_bwd_apply"))
+                           lambda: L.check(K.uclstm_bn_head_bwd_reduce(pz, _p(dy), *pq, _p(head_w), _p(partials), _p(sums), _p(dwh), _p(dbh),
+                                                                       pixels, ppg, Cop, Co, _stream()), "bn_head_bwd_reduce"))
             if direct:
                 grad_written(head_w)
                 if head_b is not None:
@@ -1543,107 +1560,94 @@ class ConvBNReLU(_GradAwareFunction):
             else:
                 d_head_w = dwh if ctx.needs_input_grad[15] else None
                 d_head_b = dbh if (head_b is not None and ctx.needs_input_grad[16]) else None
-        elif ctx.pool and dp is not None and ctx.pool_fused:
+            kind, nbytes = "bn_head_bwd_apply", 4.0 * z.numel() + 4.0 * pixels
+            apply = lambda s: K.uclstm_bn_head_bwd_apply(pz, _p(dy), *pq, _p(s), _p(head_w), _p(dz), pixels, ppg, Cop, Co, _stream())
+        elif variant == "pool":
             # pooling fused: the gradient of the activation is (skip gradient) + scatter(dp), formed inside the BatchNorm kernels
             dsk = None if da is None else da.contiguous()
             dp = dp.contiguous()
             prt = torch.empty((int(L.lib.uclstm_bn_pool_bwd_rows(n_img, H, W, Cop, groups)), Cop, 2), dtype=F32, device=dev)
             _timed_hbm("bn_pool_bwd_reduce", (4.5 if dsk is not None else 2.5) * z.numel(),
-                       lambda: L.check(K.uclstm_bn_pool_bwd_reduce(_p(z), _p(dsk), _p(dp), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]),
-                                                                   _p(prt), _p(sums), n_img, H, W, Cop, groups, _stream()),
-                                       "bn_pool_bwd_reduce"))
-            sums_dz = sums if training else torch.zeros_like(sums)
-            if ctx.sync_bn is not None:
-                sums_dz = _bn_bwd_sums_over_ranks(sums, ctx.sync_bn, "pool")
-            _timed_hbm("bn_pool_bwd_apply", (6.5 if dsk is not None else 4.5) * z.numel(),
-                       lambda: L.check(K.uclstm_bn_pool_bwd_apply(_p(z), _p(dsk), _p(dp), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]),
-                                                                  _p(sums_dz), _p(dz), n_img, H, W, Cop, groups, _stream()),
-                                       "bn_pool_bwd_apply"))
+                       lambda: L.check(K.uclstm_bn_pool_bwd_reduce(pz, _p(dsk), _p(dp), *pq, _p(prt), _p(sums), n_img, H, W, Cop, groups,
+                                                                   _stream()), "bn_pool_bwd_reduce"))
+            kind, nbytes = "bn_pool_bwd_apply", (6.5 if dsk is not None else 4.5) * z.numel()
+            apply = lambda s: K.uclstm_bn_pool_bwd_apply(pz, _p(dsk), _p(dp), *pq, _p(s), _p(dz), n_img, H, W, Cop, groups, _stream())
         else:
-            if ctx.pool and dp is not None:
+            if dp is not None:
                 # pooling not fused (odd sizes / evaluation-mode statistics path): the stand-alone max-pool backward kernel first
-                act = ctx.pool_act
-                odd = bool(H % 2 or W % 2)
-                dfull = torch.zeros_like(act) if odd else torch.empty_like(act)
-                add = da.contiguous() if (da is not None and not odd) else None
-                L.check(K.uclstm_maxpool2_bwd(_p(act), _p(dp.contiguous()), _p(add), _p(dfull), n_img, H, W, Cop, _stream()), "maxpool2_bwd")
-                da = dfull if (da is None or add is not None) else dfull + da
+                da = _maxpool2_bwd(ctx.pool_act, dp, da)
             da = da.contiguous()
             _timed_hbm("bn_bwd_reduce", 4.0 * z.numel(),            # z and da read once
-                       lambda: L.check(K.uclstm_bn_bwd_reduce(_p(z), _p(da), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(partials),
-                                                              _p(sums), pixels, ppg, Cop, _stream()), "bn_bwd_reduce"))
-            # training: dz = scale*(g - s1/n - xhat*s2/n).  Evaluation-mode statistics are constants, the two mean terms vanish:
-            # the same kernel with zero sums gives dz = scale*g (sums itself still holds dbeta / dgamma)
+                       lambda: L.check(K.uclstm_bn_bwd_reduce(pz, _p(da), *pq, _p(partials), _p(sums), pixels, ppg, Cop, _stream()),
+                                       "bn_bwd_reduce"))
+            kind, nbytes = "bn_bwd_apply", 6.0 * z.numel()          # z, da read, dz written
+            apply = lambda s: K.uclstm_bn_bwd_apply(pz, _p(da), *pq, _p(s), _p(dz), pixels, ppg, Cop, _stream())
+        # training: dz = scale*(g - s1/n - xhat*s2/n), with the sums of all ranks where the forward pass had their statistics.
+        # Evaluation-mode statistics are constants, the two mean terms vanish: the same kernel with zero sums gives dz = scale*g
+        # (sums itself still holds dbeta / dgamma)
+        if ctx.sync_bn is not None:
+            sums_dz = _bn_bwd_sums_over_ranks(sums, ctx.sync_bn, variant)
+        else:
             sums_dz = sums if training else torch.zeros_like(sums)
-            if ctx.sync_bn is not None:
-                sums_dz = _bn_bwd_sums_over_ranks(sums, ctx.sync_bn, "plain")
-            _timed_hbm("bn_bwd_apply", 6.0 * z.numel(),             # z, da read, dz written
-                       lambda: L.check(K.uclstm_bn_bwd_apply(_p(z), _p(da), _p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]), _p(sums_dz),
-                                                             _p(dz), pixels, ppg, Cop, _stream()), "bn_bwd_apply"))
-        # training: the conv bias feeds BatchNorm, which removes any per-channel constant -- its gradient is analytically 0.
-        # With frozen statistics it is the column sum of dz.
-        bias_grad = (lambda: colsum(dz)[:Co].contiguous()) if not training else (lambda: torch.zeros((Co,), dtype=F32, device=dev))
-        # a frozen parameter (requires_grad False: fine-tuning) gets nothing launched for it; weight, bias, gamma and beta are
-        # independent of each other
-        need_w, need_b, need_gamma, need_beta = ctx.needs_input_grad[2:6]
-        need_b = need_b and has_bias
+        _timed_hbm(kind, nbytes, lambda: L.check(apply(sums_dz), kind))
+        return dz, sums, d_head_w, d_head_b
+
+    @staticmethod
+    def _param_grads(ctx, dz, sums, gamma, beta, bias):
+        """Part 2: (dbias, dgamma, dbeta) for autograd; None for a frozen parameter (requires_grad False: fine-tuning -- nothing
+        is launched for it; bias, gamma and beta are independent of each other) and for one whose attached gradient was written."""
+        (_, _, groups, training, _, Co, _, has_bias), dev = ctx.cfg, dz.device
+        need_b, need_gamma, need_beta = ctx.needs_input_grad[3:6]
+        dbias = dgamma = dbeta = None
         g_gamma, g_beta = direct_grad(gamma), direct_grad(beta)
-        if not (need_gamma and need_beta):
-            dgamma = dbeta = None
-            if need_gamma or need_beta:
-                tot = sums.sum(dim=0)
-                dbeta = tot[:Co, 0].contiguous() if need_beta else None
-                dgamma = tot[:Co, 1].contiguous() if need_gamma else None
-            dbias = bias_grad() if need_b else None
-        elif g_gamma is not None and g_beta is not None:
+        direct = need_gamma and need_beta and g_gamma is not None and g_beta is not None
+        if direct:
             # one kernel accumulates straight into the attached gradient buffers (instead of sum + 2 copies + 2 accumulates).
             # Nothing in the backward pass waits for it: with the weight-gradient stream in use it goes there (18 small
             # dependent launches off the main stream; joined with the weight gradients at the end of backward).
-            if ASYNC_WGRAD and PARAM_GRADS_ON_SIDE:
-                main, side = torch.cuda.current_stream(dev), side_stream(dev)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    L.check(L.lib.uclstm_bn_bwd_param_grads(_p(sums), groups, Cop, Co, _p(g_gamma), _p(g_beta), 1, _stream()),
-                            "bn_bwd_param_grads")
-                    sums.record_stream(side)
-                    grad_written(gamma)
-                    grad_written(beta)
-                _schedule_join(dev)
-            else:
-                L.check(L.lib.uclstm_bn_bwd_param_grads(_p(sums), groups, Cop, Co, _p(g_gamma), _p(g_beta), 1, _stream()), "bn_bwd_param_grads")
+            def launch():
+                L.check(L.lib.uclstm_bn_bwd_param_grads(_p(sums), groups, sums.shape[1], Co, _p(g_gamma), _p(g_beta), 1, _stream()),
+                        "bn_bwd_param_grads")
                 grad_written(gamma)
                 grad_written(beta)
-            dgamma = dbeta = None
-            dbias = None
-            if need_b:
-                g_bias = direct_grad(bias)
-                if g_bias is not None:
-                    if not training:
-                        g_bias.add_(bias_grad())
-                    grad_written(bias)                          # training: += 0
-                else:
-                    dbias = bias_grad()
-        else:
+
+            if ASYNC_WGRAD and PARAM_GRADS_ON_SIDE:
+                _on_side(dev, launch, (sums,))
+                _schedule_join(dev)
+            else:
+                launch()
+        elif need_gamma or need_beta:
             tot = sums.sum(dim=0)
-            dbeta = tot[:Co, 0].contiguous()
-            dgamma = tot[:Co, 1].contiguous()
-            dbias = bias_grad() if need_b else None
+            dbeta = tot[:Co, 0].contiguous() if need_beta else None
+            dgamma = tot[:Co, 1].contiguous() if need_gamma else None
+        if need_b and has_bias:
+            # training: the conv bias feeds BatchNorm, which removes any per-channel constant -- its gradient is analytically 0.
+            # With frozen statistics it is the column sum of dz.
+            g_bias = direct_grad(bias) if direct else None
+            if not training:
+                dbias = colsum(dz)[:Co].contiguous()
+            elif g_bias is None:
+                dbias = torch.zeros((Co,), dtype=F32, device=dev)
+            if g_bias is not None:
+                if dbias is not None:
+                    g_bias.add_(dbias)
+                grad_written(bias)                          # training: += 0
+                dbias = None
+        return dbias, dgamma, dbeta
 
-        dy_seg = [(dz, 0, Cop, 0, 1, 0, 0)]
-        if not need_w:
-            dweight = None
-        elif im2col:
-            pd = im2col_pack_desc(Co, Ci_total, x0.shape[3])
-            dweight = wgrad_into_param(weight, pd, [x0, dz], lambda: igemm_wgrad([SrcView(x0)], dy_seg, pd.N, pd.Ktot, (H, W), n_img,
-                                                                                 ktap=1, pad=0))
-        else:
-            c_pad = [x0.shape[3]] + ([x1.shape[3]] if x1 is not None else [])
-            pd = conv_pack_desc(Co, Ci_total, list(c_valid), c_pad)
-            srcs = [SrcView(x0)] + ([SrcView(x1, off[0], off[1])] if x1 is not None else [])
-            dweight = wgrad_into_param(weight, pd, [x0, x1, dz], lambda: igemm_wgrad(srcs, dy_seg, pd.N, pd.Ktot, (H, W), n_img,
-                                                                                     ktap=3, pad=1))
-
-        dx0 = dx1 = None
+    @staticmethod
+    def backward(ctx, da, dp=None):
+        x0, x1, weight, z, par, gamma, beta, bias, head_w, head_b = ctx.saved_tensors
+        c_valid, off, _, _, im2col, Co, Ci_total, _ = ctx.cfg
+        n_img, H, W, Cop = z.shape
+        dz, sums, d_head_w, d_head_b = ConvBNReLU._bn_backward(ctx, z, par, head_w, head_b, da, dp)
+        dbias, dgamma, dbeta = ConvBNReLU._param_grads(ctx, dz, sums, gamma, beta, bias)
+        # part 3: the weight gradient (not for a frozen weight) and the input gradients
+        dweight = dx0 = dx1 = None
+        if ctx.needs_input_grad[2]:
+            pd, srcs, ktap, pad = _conv_geometry(x0, x1, weight, c_valid, off, im2col)
+            dweight = wgrad_into_param(weight, pd, [x0, x1, dz], lambda: igemm_wgrad(srcs, [(dz, 0, Cop, 0, 1, 0, 0)], pd.N, pd.Ktot, (H, W),
+                                                                                     n_img, ktap=ktap, pad=pad))
         if ctx.needs_input_grad[0] and not im2col:
             dd = conv_dgrad_pack_desc(Co, Ci_total, c_valid[0])
             wd = pack_weights(dd, weight, 0, dz.dtype)
@@ -1660,24 +1664,35 @@ class ConvBNReLU(_GradAwareFunction):
 # ---------------------------------------------------------------------------------------------
 # MaxPool2d(2)  (train/unet.py:81)
 # ---------------------------------------------------------------------------------------------
+def _maxpool2_fwd(a: torch.Tensor) -> torch.Tensor:
+    _dev(a, ACT, "activation")
+    N, H, W, Cp = a.shape
+    p = torch.empty((N, H // 2, W // 2, Cp), dtype=a.dtype, device=a.device)
+    L.check(_k(a).uclstm_maxpool2_fwd(_p(a), _p(p), N, H, W, Cp, _stream()), "maxpool2_fwd")
+    return p
+
+
+def _maxpool2_bwd(a: torch.Tensor, dp: torch.Tensor, dskip: Optional[torch.Tensor]) -> torch.Tensor:
+    """Gradient of ``a`` from the gradient ``dp`` of MaxPool2d(2)(a) and ``dskip`` (or None), the gradient of its other use.
+    Even sizes: the kernel writes every element and adds ``dskip`` itself.  Odd sizes: the last row / column lies in no window,
+    so the result is zero-filled first and ``dskip`` added afterwards."""
+    N, H, W, Cp = a.shape
+    odd = bool(H % 2 or W % 2)
+    da = torch.zeros_like(a) if odd else torch.empty_like(a)
+    add = dskip.contiguous() if (dskip is not None and not odd) else None
+    L.check(_k(a).uclstm_maxpool2_bwd(_p(a), _p(dp.contiguous()), _p(add), _p(da), N, H, W, Cp, _stream()), "maxpool2_bwd")
+    return da if (dskip is None or add is not None) else da + dskip
+
+
 class MaxPool2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a):
-        _dev(a, ACT, "activation")
-        N, H, W, Cp = a.shape
-        p = torch.empty((N, H // 2, W // 2, Cp), dtype=a.dtype, device=a.device)
-        L.check(_k(a).uclstm_maxpool2_fwd(_p(a), _p(p), N, H, W, Cp, _stream()), "maxpool2_fwd")
         ctx.save_for_backward(a)
-        return p
+        return _maxpool2_fwd(a)
 
     @staticmethod
     def backward(ctx, dp):
-        (a,) = ctx.saved_tensors
-        dp = dp.contiguous()
-        N, H, W, Cp = a.shape
-        da = torch.zeros_like(a) if (H % 2 or W % 2) else torch.empty_like(a)
-        L.check(_k(a).uclstm_maxpool2_bwd(_p(a), _p(dp), None, _p(da), N, H, W, Cp, _stream()), "maxpool2_bwd")
-        return da
+        return _maxpool2_bwd(ctx.saved_tensors[0], dp, None)
 
 
 class MaxPool2Skip(torch.autograd.Function):
@@ -1687,28 +1702,12 @@ class MaxPool2Skip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a):
-        _dev(a, ACT, "activation")
-        N, H, W, Cp = a.shape
-        p = torch.empty((N, H // 2, W // 2, Cp), dtype=a.dtype, device=a.device)
-        L.check(_k(a).uclstm_maxpool2_fwd(_p(a), _p(p), N, H, W, Cp, _stream()), "maxpool2_fwd")
         ctx.save_for_backward(a)
-        return p, a.view_as(a)
+        return _maxpool2_fwd(a), a.view_as(a)
 
     @staticmethod
     def backward(ctx, dp, dskip):
-        (a,) = ctx.saved_tensors
-        N, H, W, Cp = a.shape
-        if dp is None:
-            return dskip
-        dp = dp.contiguous()
-        odd = bool(H % 2 or W % 2)
-        da = torch.zeros_like(a) if odd else torch.empty_like(a)
-        fused = dskip is not None and not odd
-        L.check(_k(a).uclstm_maxpool2_bwd(_p(a), _p(dp), _p(dskip.contiguous()) if fused else None, _p(da), N, H, W, Cp, _stream()),
-                "maxpool2_bwd")
-        if dskip is not None and not fused:
-            da = da + dskip
-        return da
+        return dskip if dp is None else _maxpool2_bwd(ctx.saved_tensors[0], dp, dskip)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1791,9 +1790,8 @@ class OutConv1x1(_GradAwareFunction):
             return da, None, None
         # the kernel ADDS its block sums into dw / db: with attached f32 gradients it adds straight into them (no zero-fill,
         # no accumulate kernels); the weight is a view [Co, Ci] of the parameter [Co, Ci, 1, 1], so is its gradient
-        gw = direct_grad(weight)
-        gb = direct_grad(bias) if ctx.has_bias else None
-        direct = need_w and gw is not None and (gb is not None or not ctx.has_bias) and gw.is_contiguous() and (need_b or not ctx.has_bias)
+        direct = direct_grad_pair(weight, bias, need_w, need_b)
+        gw, gb = direct or (None, None)
         if _DETERMINISTIC:
             dw = gw if direct else torch.empty((Co, Ci), dtype=F32, device=a.device)
             db = gb if (direct and ctx.has_bias) else (torch.empty((Co,), dtype=F32, device=a.device) if need_b else None)
