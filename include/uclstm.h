@@ -664,6 +664,54 @@ int64_t uclstm_eval_stats_rows(int64_t P, int64_t frames);
 int32_t uclstm_stream_spin(int32_t microseconds, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* ResNet18-encoder model (train/resnet18.py: PretrainedTemporalUNet) -- csrc/resnet.hip */
+/* ------------------------------------------------------------------------------------ */
+/* HBM-bound NHWC kernels around the GEMMs of the reference's shipped configuration (smp.Unet("resnet18", in_channels=2,
+ * decoder_channels=(256,128,64,32,16)), train/resnet18.py:26-33).  Its strided convolutions (3x3 / stride 2 / pad 1 and
+ * 1x1 / stride 2) are uclstm_igemm_fwd descriptors with scale = 2; nothing here is a GEMM.  All pointers to 16-bit tensors and
+ * to per-channel f32 vectors must be 16-byte aligned. */
+
+/* conv1 gather (7x7, stride 2, pad 3) of the f32 NCHW input: out[img][yo][xo][tap*C + c] = x[img'][c][2*yo+dy-3][2*xo+dx-3]
+ * (tap = dy*7 + dx; zero outside the image and for the K padding tap*C + c >= 49*C), out bf16 [n_img][Ho][Wo][Kp] with
+ * Ho = (H-1)/2 + 1, Wo = (W-1)/2 + 1, Kp >= 49*C a multiple of 8.  Image addressing (inner, inner_stride, outer_stride) as
+ * uclstm_im2col3x3_first.  The convolution is then a plain GEMM over K = Kp (ktap 1) that can emit BatchNorm partial sums. */
+int32_t uclstm_im2col7x7s2_first(const float* x, void* out, int32_t n_img, int32_t C, int32_t Kp, int32_t H, int32_t W,
+                                 int32_t inner, int64_t inner_stride, int64_t outer_stride, void* stream);
+/* MaxPool2d(3, stride 2, padding 1): p bf16 [n_img][Ho][Wo][Cp], Ho = (H-1)/2 + 1, Wo = (W-1)/2 + 1.  Windows are clipped to the
+ * image (the padding never wins); odd H / W allowed. */
+int32_t uclstm_maxpool3s2_fwd(const void* a, void* p, int32_t n_img, int32_t H, int32_t W, int32_t Cp, void* stream);
+/* Tail of a BasicBlock: a = bf16(relu((z*scale[c] + shift[c]) + (r*rscale[c] + rshift[c]))) in f32 on bf16 [pixels][Cp] tensors,
+ * scale / shift / rscale / rshift f32 [Cp].  A NULL (scale, shift) or (rscale, rshift) pair is the identity on that operand:
+ * the plain residual (r as it is), the downsample branch's BatchNorm (both pairs), and evaluation mode, where the affines
+ * were folded into the convolutions (both NULL).  One of a pair NULL and the other not is UCLSTM_E_BADARG. */
+int32_t uclstm_bn_add_relu(const void* z, const float* scale, const float* shift, const void* r, const float* rscale,
+                           const float* rshift, void* a, int64_t pixels, int32_t Cp, void* stream);
+/* Nearest-neighbour x2 upsampling (smp's decoder block): out bf16 [n_img][2H][2W][Cp], out[2y+i][2x+j] = a[y][x]. */
+int32_t uclstm_upsample2_fwd(const void* a, void* out, int32_t n_img, int32_t H, int32_t W, int32_t Cp, void* stream);
+/* Its gradient: da[y][x] = bf16(((d[2y][2x] + d[2y][2x+1]) + d[2y+1][2x]) + d[2y+1][2x+1]) in f32, in that order. */
+int32_t uclstm_upsample2_bwd(const void* dout, void* da, int32_t n_img, int32_t H, int32_t W, int32_t Cp, void* stream);
+/* Segmentation head: conv3x3 pad 1 with bias, a bf16 [n_img][H][W][Cp] (C <= Cp <= 64 valid channels), w f32 [Co][C][3][3],
+ * b f32 [Co] or NULL, y f32 NCHW [n_img][Co][H][W], Co <= 4.  f32 accumulation: acc = b, then += a*w over (ky, kx, c) in that
+ * order; y is never rounded to 16 bits. */
+int32_t uclstm_head3x3_fwd(const void* a, const float* w, const float* b, float* y, int64_t n_img, int32_t H, int32_t W, int32_t Cp,
+                           int32_t C, int32_t Co, void* stream);
+/* da bf16 [pixels][Cp] (padding channels zero); dw [Co][C][3][3] and db [Co] accumulate (+=) with one f32 atomic per block and
+ * column (caller zeroes, or passes attached gradient buffers).  Any of da / dw / db NULL: that output is skipped; dw and db both
+ * NULL: no parameter-gradient launch. */
+int32_t uclstm_head3x3_bwd(const void* a, const float* w, const float* dy, void* da, float* dw, float* db, int64_t n_img, int32_t H,
+                           int32_t W, int32_t Cp, int32_t C, int32_t Co, void* stream);
+/* Ordered form (deterministic mode; one symbol, act_type as above).  da as uclstm_head3x3_bwd.  Pixel range r (of
+ * uclstm_head3x3_bwd_ordered_rows, a function of the shape alone, 1 .. 1024) stores its block totals to `partials` (f32,
+ * rows*(Co*C*9) + rows*Co elements: the block [rows][Co*C*9] of dw columns in [co][c][ky][kx] order, then the block [rows][Co] of
+ * db columns; caller-owned, need not be initialised, every element is written); then one thread per column adds the rows in
+ * index order, out = (accumulate ? out : 0) + p[0][col] + p[1][col] + ... + p[rows-1][col] (left to right, uclstm_ordered_sum_f32).
+ * dw or db NULL: that output is skipped; both NULL: no parameter-gradient launch, partials unused. */
+int64_t uclstm_head3x3_bwd_ordered_rows(int64_t n_img, int32_t H, int32_t W);
+int32_t uclstm_head3x3_bwd_ordered(const void* a, const float* w, const float* dy, void* da, float* partials, float* dw, float* db,
+                                   int32_t accumulate, int64_t n_img, int32_t H, int32_t W, int32_t Cp, int32_t C, int32_t Co,
+                                   int32_t act_type, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* fp16 twins (BASELINE.json configs[3]: "fp16 MFMA")                                    */
 /* ------------------------------------------------------------------------------------ */
 /* Every entry point above that reads or writes 16-bit activations or weight panels exists a second time with the suffix
@@ -703,6 +751,11 @@ UCLSTM_F16_TWIN(uclstm_outconv_bwd)
 UCLSTM_F16_TWIN(uclstm_colsum)
 UCLSTM_F16_TWIN(uclstm_attention_fwd)
 UCLSTM_F16_TWIN(uclstm_attention_bwd)
+/* the twins of csrc/resnet.hip, as one list (the host mirror keeps the same list: _lib.RESNET_F16_TWINS) */
+#define UCLSTM_RESNET_F16_TWINS(TWIN) \
+    TWIN(uclstm_im2col7x7s2_first) TWIN(uclstm_maxpool3s2_fwd) TWIN(uclstm_bn_add_relu) TWIN(uclstm_upsample2_fwd) \
+    TWIN(uclstm_upsample2_bwd) TWIN(uclstm_head3x3_fwd) TWIN(uclstm_head3x3_bwd)
+UCLSTM_RESNET_F16_TWINS(UCLSTM_F16_TWIN)
 
 /* Library self-description (used by the loader to check the build). */
 int32_t uclstm_abi_version(void);

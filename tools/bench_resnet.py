@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""First record of PretrainedTemporalUNet on the HIP path (profiles/resnet_step.txt).
+
+  * one ``train_step`` of the reference's shipped configuration: B = 32, T = 20, 64 x 64, lstm_layers = 2, frozen encoder, bf16,
+    FusedAdamW with the clip fused -- HIP events around every step, median / min / max over --steps steps after --warmup;
+  * every kernel of csrc/resnet.hip alone at the shapes that step gives it, with cold caches (a 1 GiB fill before every launch, so
+    nothing is served from the 256 MB memory-side cache): median microseconds and achieved TB/s against ALGORITHMIC bytes (every
+    operand read once, every result written once).
+
+There is nothing to compare with: the parent cannot run this model and the eager smp path cannot run here.
+
+    python tools/bench_resnet.py [--steps 10] [--warmup 3] [--batch 32] [--frames 20] [--out FILE]
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import unet_convlstm_amd as U   # noqa: E402
+from unet_convlstm_amd import ops   # noqa: E402
+
+L = U._lib
+ap = argparse.ArgumentParser()
+ap.add_argument("--steps", type=int, default=10)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--batch", type=int, default=32)
+ap.add_argument("--frames", type=int, default=20)
+ap.add_argument("--size", type=int, default=64)
+ap.add_argument("--iters", type=int, default=7)
+ap.add_argument("--out", default=None)
+a = ap.parse_args()
+if not torch.cuda.is_available():
+    raise SystemExit("a HIP device is required (this package has no CPU path)")
+dev = torch.device("cuda:0")
+lines = []
+
+
+def say(s=""):
+    print(s, flush=True)
+    lines.append(s)
+
+
+B, T, HW = a.batch, a.frames, a.size
+say(f"# PretrainedTemporalUNet(lstm_layers=2, freeze_encoder=True), bf16, B={B} T={T} {HW}x{HW}, {torch.cuda.get_device_name(0)}")
+torch.manual_seed(0)
+model = U.PretrainedTemporalUNet(out_channels=1, lstm_layers=2).to(dev).train()
+trainable = [p for p in model.parameters() if p.requires_grad]
+say(f"# parameters: {sum(p.numel() for p in model.parameters())} ({sum(p.numel() for p in trainable)} trainable)")
+opt = U.FusedAdamW(trainable, lr=1e-3, weight_decay=1e-4, max_grad_norm=1.0)
+g = torch.Generator().manual_seed(1)
+x = torch.randn(B, T, 2, HW, HW, generator=g).to(dev)
+y = (torch.randn(B, T, 1, HW, HW, generator=g) * 0.5).to(dev)
+mask = (torch.rand(B, T, 1, HW, HW, generator=g) > 0.2).float().to(dev)
+losses = []
+for _ in range(a.warmup):
+    losses.append(U.train_step(model, opt, x, y, mask, True)[0])
+torch.cuda.synchronize()
+ev = []
+for _ in range(a.steps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    losses.append(U.train_step(model, opt, x, y, mask, True)[0])
+    e1.record()
+    ev.append((e0, e1))
+torch.cuda.synchronize()
+ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+say(f"train_step: median {ms[len(ms) // 2]:.2f} ms, min {ms[0]:.2f}, max {ms[-1]:.2f} over {a.steps} steps after {a.warmup} warm-up steps "
+    f"({B * T / ms[len(ms) // 2] * 1e3:.0f} frames/s); loss {float(losses[0]):.4f} -> {float(losses[-1]):.4f}")
+with torch.no_grad():
+    model.eval()
+    for _ in range(2):
+        model(x)
+    torch.cuda.synchronize()
+    ev = []
+    for _ in range(a.steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        model(x)
+        e1.record()
+        ev.append((e0, e1))
+    torch.cuda.synchronize()
+ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+say(f"eval forward (no_grad): median {ms[len(ms) // 2]:.2f} ms, min {ms[0]:.2f}, max {ms[-1]:.2f}")
+del model, opt
+torch.cuda.empty_cache()
+
+# ---- the kernels of csrc/resnet.hip alone -----------------------------------------------------
+flush = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+st = torch.cuda.current_stream()
+K, S = L.lib, ops._stream()
+n = B * T
+
+
+def timed(fn):
+    t = []
+    for _ in range(a.iters):
+        flush.fill_(1.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        fn()
+        e1.record(st)
+        torch.cuda.synchronize()
+        t.append(e0.elapsed_time(e1) * 1e3)
+    t.sort()
+    return t[len(t) // 2]
+
+
+def act(*shape):
+    return torch.randn(shape, device=dev).to(torch.bfloat16)
+
+
+def nb(*ts):
+    return sum(t.numel() * t.element_size() for t in ts)
+
+
+def report(name, shape, nbytes, fn):
+    t = timed(fn)
+    say(f"{name:24s} {shape:28s} {nbytes / 1e6:9.1f} MB {t:9.1f} us {nbytes / t / 1e6:6.2f} TB/s")
+
+
+say()
+say(f"# kernels alone, cold caches, median of {a.iters}: name, shape, algorithmic bytes, time, achieved bandwidth")
+h2 = HW // 2
+col = torch.empty((n, h2, h2, 104), dtype=torch.bfloat16, device=dev)
+report("im2col7x7s2_first", f"[{n},{h2},{h2},104]", nb(x, col),
+       lambda: L.check(K.uclstm_im2col7x7s2_first(x.data_ptr(), col.data_ptr(), n, 2, 104, HW, HW, B, 2 * HW * HW, T * 2 * HW * HW, S), "im2col"))
+f1 = act(n, h2, h2, 64)
+p = torch.empty((n, h2 // 2, h2 // 2, 64), dtype=torch.bfloat16, device=dev)
+report("maxpool3s2_fwd", f"[{n},{h2},{h2},64]", nb(f1, p), lambda: L.check(K.uclstm_maxpool3s2_fwd(f1.data_ptr(), p.data_ptr(), n, h2, h2, 64, S), "maxpool"))
+for C_, hh in ((64, HW // 4), (128, HW // 8), (512, HW // 32)):
+    z, r, o = act(n * hh * hh, C_), act(n * hh * hh, C_), torch.empty((n * hh * hh, C_), dtype=torch.bfloat16, device=dev)
+    sc = [torch.rand(C_, device=dev) + 0.5 for _ in range(4)]
+    report("bn_add_relu", f"[{n},{hh},{hh},{C_}] both affines", nb(z, r, o),
+           lambda: L.check(K.uclstm_bn_add_relu(z.data_ptr(), sc[0].data_ptr(), sc[1].data_ptr(), r.data_ptr(), sc[2].data_ptr(), sc[3].data_ptr(),
+                                                o.data_ptr(), n * hh * hh, C_, S), "bn_add_relu"))
+for C_, hh in ((32, HW // 2), (512, HW // 32)):
+    lo, hi = act(n, hh, hh, C_), act(n, 2 * hh, 2 * hh, C_)
+    report("upsample2_fwd", f"[{n},{hh},{hh},{C_}] -> x2", nb(lo, hi), lambda: L.check(K.uclstm_upsample2_fwd(lo.data_ptr(), hi.data_ptr(), n, hh, hh, C_, S), "up"))
+    report("upsample2_bwd", f"[{n},{hh},{hh},{C_}] <- x2", nb(lo, hi), lambda: L.check(K.uclstm_upsample2_bwd(hi.data_ptr(), lo.data_ptr(), n, hh, hh, C_, S), "upb"))
+ah, w, b_ = act(n, HW, HW, 16), torch.randn(1, 16, 3, 3, device=dev) * 0.1, torch.zeros(1, device=dev)
+yh, dy, da = torch.empty((n, 1, HW, HW), device=dev), torch.randn(n, 1, HW, HW, device=dev), torch.empty_like(ah)
+dw, db = torch.zeros_like(w), torch.zeros_like(b_)
+geom = (n, HW, HW, 16, 16, 1)
+report("head3x3_fwd", f"[{n},{HW},{HW},16] -> 1", nb(ah, yh),
+       lambda: L.check(K.uclstm_head3x3_fwd(ah.data_ptr(), w.data_ptr(), b_.data_ptr(), yh.data_ptr(), *geom, S), "head_fwd"))
+report("head3x3_bwd (da, dw, db)", f"[{n},{HW},{HW},16]", nb(ah, dy, da),
+       lambda: L.check(K.uclstm_head3x3_bwd(ah.data_ptr(), w.data_ptr(), dy.data_ptr(), da.data_ptr(), dw.data_ptr(), db.data_ptr(), *geom, S), "head_bwd"))
+rows = int(K.uclstm_head3x3_bwd_ordered_rows(n, HW, HW))
+part = torch.empty(rows * (16 * 9 + 1), device=dev)
+report("head3x3_bwd_ordered", f"[{n},{HW},{HW},16] {rows} rows", nb(ah, dy, da),
+       lambda: L.check(K.uclstm_head3x3_bwd_ordered(ah.data_ptr(), w.data_ptr(), dy.data_ptr(), da.data_ptr(), part.data_ptr(), dw.data_ptr(),
+                                                    db.data_ptr(), 0, *geom, L.ACT_TYPE_BF16, S), "head_bwd_ordered"))
+if a.out:
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")

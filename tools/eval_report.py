@@ -4,9 +4,9 @@ statistics computed on the device (unet_convlstm_amd.evaluate_report) and every 
     python tools/eval_report.py --checkpoint model.pt --npz data.npz [--batch 8] [--use-mask] [--out report.npz] [--plots DIR]
     python tools/eval_report.py --bench            # kernel timing against uclstm_metric_sums, see profiles/eval_report.txt
 
-The checkpoint is what the reference's training writes: {"config": {...}, "model_state": state_dict}; only the 'custom' model
-type (TemporalUNetDualView) is supported.  --plots draws the reference's five figures from the report when matplotlib can be
-imported, after everything that is timed.
+The checkpoint is what the reference's training writes: {"config": {...}, "model_state": state_dict}, of model type 'custom'
+(TemporalUNetDualView) or 'resnet18' (PretrainedTemporalUNet: lstm_layers from the config or counted in the keys).  --plots
+draws the reference's five figures from the report when matplotlib can be imported, after everything that is timed.
 """
 from __future__ import annotations
 
@@ -39,11 +39,22 @@ def load_model(U, checkpoint_path, device):
     cfg = checkpoint.get("config", {})
     model_type = cfg.get("type", "custom")
     print(f"[INFO] Detected Model Type: {model_type}")
+    state = checkpoint["model_state"]
+    if model_type == "resnet18":
+        # train/get_metrics.py:75-79 rebuilds PretrainedTemporalUNet(lstm_layers=2); the layer count is in the config of newer
+        # checkpoints and in the keys of every one (lstm.layers.<l>.conv.weight)
+        layers = cfg.get("lstm_layers")
+        if layers is None:
+            layers = 1 + max(int(k.split(".")[2]) for k in state if k.startswith("lstm.layers."))
+        model = U.PretrainedTemporalUNet(out_channels=state["head.0.weight"].shape[0], lstm_layers=int(layers),
+                                         freeze_encoder=cfg.get("freeze_encoder", True))
+        model.load_state_dict(state, strict=True)
+        return model.to(device).eval()
     if model_type != "custom":
-        raise SystemExit(f"model type {model_type!r} is not supported (only 'custom': TemporalUNetDualView)")
+        raise SystemExit(f"model type {model_type!r} is not supported ('custom': TemporalUNetDualView, 'resnet18': PretrainedTemporalUNet)")
     model = U.TemporalUNetDualView(in_channels_per_sat=1, out_channels=1, base_ch=cfg.get("base_ch", 64), lstm_layers=1,
                                    use_skip_lstm=cfg.get("use_skip_lstm", True), use_attention=cfg.get("use_attention", False))
-    model.load_state_dict(checkpoint["model_state"])
+    model.load_state_dict(state)
     return model.to(device).eval()
 
 

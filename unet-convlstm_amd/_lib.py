@@ -161,6 +161,15 @@ _PROTOS = {
     "uclstm_outconv_bwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
     "uclstm_outconv_bwd_ordered_rows": [_L, _I],
     "uclstm_outconv_bwd_ordered": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P],
+    "uclstm_im2col7x7s2_first": [_P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _P],
+    "uclstm_maxpool3s2_fwd": [_P, _P, _I, _I, _I, _I, _P],
+    "uclstm_bn_add_relu": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P],
+    "uclstm_upsample2_fwd": [_P, _P, _I, _I, _I, _I, _P],
+    "uclstm_upsample2_bwd": [_P, _P, _I, _I, _I, _I, _P],
+    "uclstm_head3x3_fwd": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
+    "uclstm_head3x3_bwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
+    "uclstm_head3x3_bwd_ordered_rows": [_L, _I, _I],
+    "uclstm_head3x3_bwd_ordered": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _I, _P],
     "uclstm_colsum": [_P, _P, _L, _I, _P],
     "uclstm_colsum_ordered_rows": [_L, _I],
     "uclstm_colsum_ordered": [_P, _P, _P, _L, _I, _I, _I, _P],
@@ -197,12 +206,18 @@ _PROTOS = {
     "uclstm_last_error_string": [],
 }
 _RESTYPES = {"uclstm_build_arch": C.c_char_p, "uclstm_source_hash": C.c_char_p, "uclstm_last_error_string": C.c_char_p, "uclstm_bn_bwd_reduce_rows": C.c_int64, "uclstm_bn_pool_bwd_rows": C.c_int64,
-             "uclstm_eval_stats_rows": C.c_int64, "uclstm_colsum_ordered_rows": C.c_int64, "uclstm_outconv_bwd_ordered_rows": C.c_int64,
+             "uclstm_eval_stats_rows": C.c_int64, "uclstm_colsum_ordered_rows": C.c_int64, "uclstm_outconv_bwd_ordered_rows": C.c_int64, "uclstm_head3x3_bwd_ordered_rows": C.c_int64,
              "uclstm_loss_fwd_ordered_rows": C.c_int64, "uclstm_sumsq_ordered_rows": C.c_int64, "uclstm_metric_sums_ordered_rows": C.c_int64}
 
 
 # entry points that exist twice: name (bfloat16) and name_f16 (IEEE binary16), identical signatures (include/uclstm.h)
 F16_TWINS = ['uclstm_igemm_fwd', 'uclstm_igemm_fwd_group', 'uclstm_igemm_wgrad', 'uclstm_pack_weights', 'uclstm_pack_weights_batched', 'uclstm_bn_apply_relu', 'uclstm_bn_bwd_reduce', 'uclstm_bn_bwd_apply', 'uclstm_bn_apply_relu_pool', 'uclstm_bn_pool_bwd_reduce', 'uclstm_bn_pool_bwd_apply', 'uclstm_bn_head_fwd', 'uclstm_bn_head_bwd_reduce', 'uclstm_bn_head_bwd_apply', 'uclstm_maxpool2_fwd', 'uclstm_maxpool2_bwd', 'uclstm_lstm_bwd_pointwise', 'uclstm_lstm_fwd_pointwise', 'uclstm_lstm_fwd_pointwise_group', 'uclstm_splitk_finish', 'uclstm_nchw_to_nhwc', 'uclstm_nhwc_to_nchw', 'uclstm_nchw_grad_to_nhwc', 'uclstm_im2col3x3_first', 'uclstm_outconv_fwd', 'uclstm_outconv_bwd', 'uclstm_colsum', 'uclstm_attention_fwd', 'uclstm_attention_bwd']
+# the twins of csrc/resnet.hip (the ResNet18-encoder model), declared in the header as one list (UCLSTM_RESNET_F16_TWINS) and kept
+# as a list of their own here (tests/test_cabi_and_host.py and three more pin the list above at its 29 entries): bound, resolved
+# and exported exactly like the ones above
+RESNET_F16_TWINS = ['uclstm_im2col7x7s2_first', 'uclstm_maxpool3s2_fwd', 'uclstm_bn_add_relu', 'uclstm_upsample2_fwd', 'uclstm_upsample2_bwd',
+                    'uclstm_head3x3_fwd', 'uclstm_head3x3_bwd']
+_ALL_F16_TWINS = frozenset(F16_TWINS) | frozenset(RESNET_F16_TWINS)
 
 
 def header_symbols() -> list[str]:
@@ -221,7 +236,7 @@ def _load() -> C.CDLL:
             "(hipcc --offload-arch=gfx950). There is no CPU or PyTorch fallback for this package.")
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in list(_PROTOS.items()):
-        for sym in ([name, name + "_f16"] if name in F16_TWINS else [name]):
+        for sym in ([name, name + "_f16"] if name in _ALL_F16_TWINS else [name]):
             try:
                 fn = getattr(lib, sym)
             except AttributeError as e:
@@ -247,7 +262,7 @@ class _F16Kernels:
     """The same entry points for IEEE binary16 activations: twins resolve to ``name_f16``, shared ones to ``name``."""
 
     def __getattr__(self, name):
-        fn = getattr(lib, name + "_f16" if name in F16_TWINS else name)
+        fn = getattr(lib, name + "_f16" if name in _ALL_F16_TWINS else name)
         setattr(self, name, fn)
         return fn
 

@@ -38,6 +38,13 @@
 #define uclstm_colsum uclstm_colsum_f16
 #define uclstm_attention_fwd uclstm_attention_fwd_f16
 #define uclstm_attention_bwd uclstm_attention_bwd_f16
+#define uclstm_im2col7x7s2_first uclstm_im2col7x7s2_first_f16
+#define uclstm_maxpool3s2_fwd uclstm_maxpool3s2_fwd_f16
+#define uclstm_bn_add_relu uclstm_bn_add_relu_f16
+#define uclstm_upsample2_fwd uclstm_upsample2_fwd_f16
+#define uclstm_upsample2_bwd uclstm_upsample2_bwd_f16
+#define uclstm_head3x3_fwd uclstm_head3x3_fwd_f16
+#define uclstm_head3x3_bwd uclstm_head3x3_bwd_f16
 // a body that reads 16-bit data behind an entry point that exists ONCE (explicit activation-type argument, no _f16 twin):
 // internal name, not in the public header; the bfloat16 pass defines the dispatcher
 #define UCLSTM_ACT_IMPL(fn) fn##_impl_f16

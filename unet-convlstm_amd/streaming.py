@@ -19,6 +19,10 @@ from .modules import TemporalUNetDualView
 
 class StreamingPredictor:
     def __init__(self, model: TemporalUNetDualView, use_graph: bool = True, warmup: int = 2):
+        if not isinstance(model, TemporalUNetDualView):
+            # the step it captures is TemporalUNetDualView.step_nhwc with its three recurrent states; other models have none
+            raise TypeError(f"StreamingPredictor drives a TemporalUNetDualView, got {type(model).__name__} "
+                            "(PretrainedTemporalUNet has no frame-by-frame step)")
         self.model = model.eval()
         self.use_graph = use_graph
         self.warmup = warmup
