@@ -41,21 +41,30 @@ def _case(Co, H, W, dtype, seed=0):
             "Co": Co}
 
 
-def _run(c, *, attach=False, frozen=(), training=True, groups=2, variant="plain", skip_grad=True, count=None):
+def _run(c, *, attach=False, frozen=(), training=True, groups=2, variant="plain", skip_grad=True, count=None, c_valid=(CI,), off=(0, 0),
+         im2col=False):
     """One forward + backward of the stage.  ``variant``: "plain", "pool" (the stage's own pooling), "pool_sep" (the stage, then
     MaxPool2Skip) or "head".  ``attach``: every parameter gets a contiguous f32 ``.grad`` before the run -- zeros for a trainable
-    one (the backward kernels then add straight into it), MARK for a frozen one.  Returns outputs, dx, the running statistics,
-    every parameter's ``.grad`` and the LAUNCH_LOG of the run; ``count`` (a list) receives one entry per
+    one (the backward kernels then add straight into it), MARK for a frozen one; a dict {name: start value} attaches a copy of the
+    start value to the trainable parameters it names instead (tests/test_gpu_grad_routes.py).  ``c["x1"]`` with ``c_valid`` /
+    ``off``: a second source; ``im2col``: ``c["x"]`` is the pre-gathered first-layer tensor.  Returns outputs, dx, the running
+    statistics, every parameter's ``.grad`` and the LAUNCH_LOG of the run; ``count`` (a list) receives one entry per
     uclstm_bn_bwd_param_grads launch."""
     L = U._lib
     names = PARAMS + (("head_w", "head_b") if variant == "head" else ())
     x = c["x"].to(DEV).requires_grad_(True)
+    x1 = c["x1"].to(DEV).requires_grad_(True) if c.get("x1") is not None else None
     P = {k: c[k].to(DEV).requires_grad_(k not in frozen) for k in names}
     if attach:
         for k, p in P.items():
-            p.grad = torch.full_like(p, MARK if k in frozen else 0.0)
+            if k in frozen:
+                p.grad = torch.full_like(p, MARK)
+            elif not isinstance(attach, dict):
+                p.grad = torch.zeros_like(p)
+            elif k in attach:
+                p.grad = attach[k].to(DEV).clone()
     rm, rv = torch.zeros(c["Co"], device=DEV), torch.ones(c["Co"], device=DEV)
-    args = (x, None, P["weight"], P["bias"], P["gamma"], P["beta"], rm, rv, (CI,), (0, 0), groups, training, 0.1, 1e-5, False)
+    args = (x, x1, P["weight"], P["bias"], P["gamma"], P["beta"], rm, rv, tuple(c_valid), tuple(off), groups, training, 0.1, 1e-5, im2col)
     real = L.lib.uclstm_bn_bwd_param_grads
 
     def counted(*a):
