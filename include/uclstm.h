@@ -711,6 +711,36 @@ int32_t uclstm_head3x3_bwd_ordered(const void* a, const float* w, const float* d
                                    int32_t accumulate, int64_t n_img, int32_t H, int32_t W, int32_t Cp, int32_t C, int32_t Co,
                                    int32_t act_type, void* stream);
 
+/* Backward of the two point-wise stages of the encoder (csrc/resnet_bwd.hip).  No atomics: both are pure functions of their
+ * inputs, so deterministic mode needs no second form.
+ *
+ * Gradient of uclstm_maxpool3s2_fwd, gather form: every INPUT pixel looks at the (at most four) clipped 3x3 windows that contain
+ * it, recomputes each window's arg-max from `a` (first maximum in scan order, strict '>': ATen's rule; post-ReLU inputs are full of
+ * exact ties) and adds the dp of the windows it wins, window rows first, then columns:
+ *   da[y][x] = bf16((dskip ? dskip[y][x] : 0) + sum dp[yo][xo]),   one f32 sum, rounded once.
+ * a, dskip (may be NULL), da: bf16 [n_img][H][W][Cp]; dp: bf16 [n_img][Ho][Wo][Cp].  Every element of da is written. */
+int32_t uclstm_maxpool3s2_bwd(const void* a, const void* dp, const void* dskip, void* da, int32_t n_img, int32_t H, int32_t W,
+                              int32_t Cp, void* stream);
+/* Gradient of uclstm_bn_add_relu with both operands through a BatchNorm of the whole batch (one group, n = pixels):
+ *   u = (z*scale + shift) + (r*rscale + rshift) in f32 exactly as the forward kernel forms it,  g = da * [u > 0].
+ * Pass 1 writes sums[c] = (sum g, sum g*xhat_z) and, when r has a BatchNorm, rsums[c] = (sum g, sum g*xhat_r), both f32 [Cp][2] in
+ * the layout of uclstm_bn_bwd_reduce (uclstm_bn_bwd_param_grads reads them with groups = 1), xhat = (x - mean)*rstd.  Block b
+ * stores row b of `partials` (f32 [rows][Cp][3], rows = uclstm_bn_add_relu_bwd_rows, caller-owned, need not be initialised); a second kernel
+ * adds the rows in a fixed order.
+ * Pass 2: dz = bf16(scale*(g - s1/n - xhat_z*s2/n)), dr likewise with r's constants and rsums.  All-zero sums give the
+ * evaluation-statistics form scale*g, for either operand on its own.
+ * (rscale, rshift, rmean, rrstd, rsums) all NULL: r is the plain residual, dr = bf16(g).  dz or dr NULL: that output is not
+ * written (both NULL is UCLSTM_E_BADARG).  Cp / 8 <= 256. */
+int64_t uclstm_bn_add_relu_bwd_rows(int64_t pixels);
+int32_t uclstm_bn_add_relu_bwd_reduce(const void* z, const float* scale, const float* shift, const float* mean, const float* rstd,
+                                      const void* r, const float* rscale, const float* rshift, const float* rmean,
+                                      const float* rrstd, const void* da, float* partials, float* sums, float* rsums,
+                                      int64_t pixels, int32_t Cp, void* stream);
+int32_t uclstm_bn_add_relu_bwd_apply(const void* z, const float* scale, const float* shift, const float* mean, const float* rstd,
+                                     const float* sums, const void* r, const float* rscale, const float* rshift,
+                                     const float* rmean, const float* rrstd, const float* rsums, const void* da, void* dz,
+                                     void* dr, int64_t pixels, int32_t Cp, void* stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* fp16 twins (BASELINE.json configs[3]: "fp16 MFMA")                                    */
 /* ------------------------------------------------------------------------------------ */
@@ -756,6 +786,10 @@ UCLSTM_F16_TWIN(uclstm_attention_bwd)
     TWIN(uclstm_im2col7x7s2_first) TWIN(uclstm_maxpool3s2_fwd) TWIN(uclstm_bn_add_relu) TWIN(uclstm_upsample2_fwd) \
     TWIN(uclstm_upsample2_bwd) TWIN(uclstm_head3x3_fwd) TWIN(uclstm_head3x3_bwd)
 UCLSTM_RESNET_F16_TWINS(UCLSTM_F16_TWIN)
+/* the twins of csrc/resnet_bwd.hip (the host mirror: _lib.RESNET_BWD_F16_TWINS) */
+#define UCLSTM_RESNET_BWD_F16_TWINS(TWIN) \
+    TWIN(uclstm_maxpool3s2_bwd) TWIN(uclstm_bn_add_relu_bwd_reduce) TWIN(uclstm_bn_add_relu_bwd_apply)
+UCLSTM_RESNET_BWD_F16_TWINS(UCLSTM_F16_TWIN)
 
 /* Library self-description (used by the loader to check the build). */
 int32_t uclstm_abi_version(void);

@@ -9,7 +9,12 @@
 
 There is nothing to compare with: the parent cannot run this model and the eager smp path cannot run here.
 
-    python tools/bench_resnet.py [--steps 10] [--warmup 3] [--batch 32] [--frames 20] [--out FILE]
+``--unfreeze all`` (or ``layer3,layer4`` ...; profiles/resnet_unfrozen_step.txt): after the frozen step, the same step with that part of
+the encoder trainable (``model.unfreeze_encoder``, two optimiser groups, the encoder at lr / 10), the peak memory of both, the share
+of the step that the backward kernels of csrc/resnet_bwd.hip take (HIP events around each of their launches in a few further steps), and
+those kernels alone at the step's shapes like the ones above.
+
+    python tools/bench_resnet.py [--steps 10] [--warmup 3] [--batch 32] [--frames 20] [--unfreeze STAGES] [--out FILE]
 """
 import argparse
 import os
@@ -29,6 +34,7 @@ ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--frames", type=int, default=20)
 ap.add_argument("--size", type=int, default=64)
 ap.add_argument("--iters", type=int, default=7)
+ap.add_argument("--unfreeze", default=None, help="all, or a comma-separated list of stem, layer1 .. layer4")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 if not torch.cuda.is_available():
@@ -53,21 +59,31 @@ g = torch.Generator().manual_seed(1)
 x = torch.randn(B, T, 2, HW, HW, generator=g).to(dev)
 y = (torch.randn(B, T, 1, HW, HW, generator=g) * 0.5).to(dev)
 mask = (torch.rand(B, T, 1, HW, HW, generator=g) > 0.2).float().to(dev)
-losses = []
-for _ in range(a.warmup):
-    losses.append(U.train_step(model, opt, x, y, mask, True)[0])
-torch.cuda.synchronize()
-ev = []
-for _ in range(a.steps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    losses.append(U.train_step(model, opt, x, y, mask, True)[0])
-    e1.record()
-    ev.append((e0, e1))
-torch.cuda.synchronize()
-ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
-say(f"train_step: median {ms[len(ms) // 2]:.2f} ms, min {ms[0]:.2f}, max {ms[-1]:.2f} over {a.steps} steps after {a.warmup} warm-up steps "
-    f"({B * T / ms[len(ms) // 2] * 1e3:.0f} frames/s); loss {float(losses[0]):.4f} -> {float(losses[-1]):.4f}")
+
+
+def time_steps(model, opt, label):
+    """Median / min / max of --steps train_steps after --warmup, and the peak allocated memory of those steps."""
+    losses = []
+    for _ in range(a.warmup):
+        losses.append(U.train_step(model, opt, x, y, mask, True)[0])
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    ev = []
+    for _ in range(a.steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        losses.append(U.train_step(model, opt, x, y, mask, True)[0])
+        e1.record()
+        ev.append((e0, e1))
+    torch.cuda.synchronize()
+    ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+    say(f"{label}: median {ms[len(ms) // 2]:.2f} ms, min {ms[0]:.2f}, max {ms[-1]:.2f} over {a.steps} steps after {a.warmup} warm-up steps "
+        f"({B * T / ms[len(ms) // 2] * 1e3:.0f} frames/s); loss {float(losses[0]):.4f} -> {float(losses[-1]):.4f}; "
+        f"peak memory {torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB")
+    return ms[len(ms) // 2]
+
+
+time_steps(model, opt, "train_step")
 with torch.no_grad():
     model.eval()
     for _ in range(2):
@@ -85,6 +101,43 @@ ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
 say(f"eval forward (no_grad): median {ms[len(ms) // 2]:.2f} ms, min {ms[0]:.2f}, max {ms[-1]:.2f}")
 del model, opt
 torch.cuda.empty_cache()
+
+# ---- the same step with a trainable encoder ---------------------------------------------------
+BWD_KINDS = ("maxpool3s2_bwd", "bn_add_relu_bwd_reduce", "bn_add_relu_bwd_apply")
+if a.unfreeze:
+    stages = "all" if a.unfreeze == "all" else tuple(a.unfreeze.split(","))
+    say()
+    say(f"# the same step after model.unfreeze_encoder({stages!r}); two optimiser groups, the encoder at lr / 10")
+    torch.manual_seed(0)
+    model = U.PretrainedTemporalUNet(out_channels=1, lstm_layers=2).to(dev)
+    model.unfreeze_encoder(stages).train()
+    enc = [p for p in model.encoder.parameters() if p.requires_grad]
+    rest = [p for k, p in model.named_parameters() if p.requires_grad and ".encoder." not in k and not k.startswith("encoder.")]
+    say(f"# trainable parameters: {sum(p.numel() for p in enc)} of the encoder + {sum(p.numel() for p in rest)}")
+    opt = U.FusedAdamW([{"params": enc, "lr": 1e-4}, {"params": rest}], lr=1e-3, weight_decay=1e-4, max_grad_norm=1.0, order=model.parameters())
+    step_ms = time_steps(model, opt, "train_step (unfrozen)")
+    # the share of the new backward kernels: events around each of their launches (and of every other HBM-bound kernel) in three
+    # further steps; the step itself is slower with the events in it, so the sum is set against the median above
+    ops.PROFILE_HBM = prof = []
+    for _ in range(3):
+        U.train_step(model, opt, x, y, mask, True)
+    torch.cuda.synchronize()
+    ops.PROFILE_HBM = None
+    tot = {}
+    for kind, nbytes, e0, e1, _ in prof:
+        t = tot.setdefault(kind, [0.0, 0.0, 0])
+        t[0] += e0.elapsed_time(e1) / 3
+        t[1] += nbytes / 3
+        t[2] += 1
+    new_ms = 0.0
+    for kind in BWD_KINDS:
+        if kind in tot:
+            ms_, by, cnt = tot[kind]
+            new_ms += ms_
+            say(f"in the step: {kind:24s} {cnt // 3:3d} launches {ms_:7.3f} ms per step {by / ms_ / 1e9:6.2f} TB/s (algorithmic bytes, event-timed)")
+    say(f"in the step: the kernels of csrc/resnet_bwd.hip take {new_ms:.3f} ms of {step_ms:.2f} ms ({100 * new_ms / step_ms:.1f} %)")
+    del model, opt
+    torch.cuda.empty_cache()
 
 # ---- the kernels of csrc/resnet.hip alone -----------------------------------------------------
 flush = torch.empty(1 << 28, dtype=torch.float32, device=dev)
@@ -152,6 +205,33 @@ part = torch.empty(rows * (16 * 9 + 1), device=dev)
 report("head3x3_bwd_ordered", f"[{n},{HW},{HW},16] {rows} rows", nb(ah, dy, da),
        lambda: L.check(K.uclstm_head3x3_bwd_ordered(ah.data_ptr(), w.data_ptr(), dy.data_ptr(), da.data_ptr(), part.data_ptr(), dw.data_ptr(),
                                                     db.data_ptr(), 0, *geom, L.ACT_TYPE_BF16, S), "head_bwd_ordered"))
+if a.unfreeze:
+    say()
+    say(f"# backward kernels of csrc/resnet_bwd.hip alone, cold caches, median of {a.iters}")
+    dp = act(n, h2 // 2, h2 // 2, 64)
+    dsk, da1 = act(n, h2, h2, 64), torch.empty_like(f1)
+    f1.clamp_(min=0)                                    # post-ReLU, as in the model: exact ties at zero
+    for name, skip in (("maxpool3s2_bwd + dskip", dsk), ("maxpool3s2_bwd", None)):
+        report(name, f"[{n},{h2},{h2},64]", nb(f1, dp, da1) + (nb(dsk) if skip is not None else 0),
+               lambda: L.check(K.uclstm_maxpool3s2_bwd(f1.data_ptr(), dp.data_ptr(), None if skip is None else skip.data_ptr(), da1.data_ptr(),
+                                                       n, h2, h2, 64, S), "maxpool3s2_bwd"))
+    for C_, hh, raff in ((64, HW // 4, False), (128, HW // 8, True), (128, HW // 8, False), (512, HW // 32, True)):
+        px = n * hh * hh
+        z, r, g_ = act(px, C_), act(px, C_), act(px, C_)
+        dz, dr = torch.empty_like(z), torch.empty_like(z)
+        par = [torch.rand(C_, device=dev) + 0.5 for _ in range(8)]
+        pz = [t.data_ptr() for t in par[:4]]
+        pr = [t.data_ptr() for t in par[4:]] if raff else [None] * 4
+        sums, rsums = torch.empty((C_, 2), device=dev), torch.empty((C_, 2), device=dev) if raff else None
+        prt = torch.empty((int(K.uclstm_bn_add_relu_bwd_rows(px)), C_, 3), device=dev)
+        rp = None if rsums is None else rsums.data_ptr()
+        what = f"[{n},{hh},{hh},{C_}] {'bn_r' if raff else 'identity'}"
+        report("bn_add_relu_bwd_reduce", what, nb(z, r, g_),
+               lambda: L.check(K.uclstm_bn_add_relu_bwd_reduce(z.data_ptr(), *pz, r.data_ptr(), *pr, g_.data_ptr(), prt.data_ptr(), sums.data_ptr(), rp,
+                                                               px, C_, S), "bn_add_relu_bwd_reduce"))
+        report("bn_add_relu_bwd_apply", what, nb(z, r, g_, dz, dr),
+               lambda: L.check(K.uclstm_bn_add_relu_bwd_apply(z.data_ptr(), *pz, sums.data_ptr(), r.data_ptr(), *pr, rp, g_.data_ptr(), dz.data_ptr(),
+                                                              dr.data_ptr(), px, C_, S), "bn_add_relu_bwd_apply"))
 if a.out:
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")

@@ -170,6 +170,10 @@ _PROTOS = {
     "uclstm_head3x3_bwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     "uclstm_head3x3_bwd_ordered_rows": [_L, _I, _I],
     "uclstm_head3x3_bwd_ordered": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _I, _P],
+    "uclstm_maxpool3s2_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "uclstm_bn_add_relu_bwd_rows": [_L],
+    "uclstm_bn_add_relu_bwd_reduce": [_P] * 14 + [_L, _I, _P],
+    "uclstm_bn_add_relu_bwd_apply": [_P] * 15 + [_L, _I, _P],
     "uclstm_colsum": [_P, _P, _L, _I, _P],
     "uclstm_colsum_ordered_rows": [_L, _I],
     "uclstm_colsum_ordered": [_P, _P, _P, _L, _I, _I, _I, _P],
@@ -207,7 +211,8 @@ _PROTOS = {
 }
 _RESTYPES = {"uclstm_build_arch": C.c_char_p, "uclstm_source_hash": C.c_char_p, "uclstm_last_error_string": C.c_char_p, "uclstm_bn_bwd_reduce_rows": C.c_int64, "uclstm_bn_pool_bwd_rows": C.c_int64,
              "uclstm_eval_stats_rows": C.c_int64, "uclstm_colsum_ordered_rows": C.c_int64, "uclstm_outconv_bwd_ordered_rows": C.c_int64, "uclstm_head3x3_bwd_ordered_rows": C.c_int64,
-             "uclstm_loss_fwd_ordered_rows": C.c_int64, "uclstm_sumsq_ordered_rows": C.c_int64, "uclstm_metric_sums_ordered_rows": C.c_int64}
+             "uclstm_loss_fwd_ordered_rows": C.c_int64, "uclstm_sumsq_ordered_rows": C.c_int64, "uclstm_metric_sums_ordered_rows": C.c_int64,
+             "uclstm_bn_add_relu_bwd_rows": C.c_int64}
 
 
 # entry points that exist twice: name (bfloat16) and name_f16 (IEEE binary16), identical signatures (include/uclstm.h)
@@ -217,7 +222,9 @@ F16_TWINS = ['uclstm_igemm_fwd', 'uclstm_igemm_fwd_group', 'uclstm_igemm_wgrad',
 # and exported exactly like the ones above
 RESNET_F16_TWINS = ['uclstm_im2col7x7s2_first', 'uclstm_maxpool3s2_fwd', 'uclstm_bn_add_relu', 'uclstm_upsample2_fwd', 'uclstm_upsample2_bwd',
                     'uclstm_head3x3_fwd', 'uclstm_head3x3_bwd']
-_ALL_F16_TWINS = frozenset(F16_TWINS) | frozenset(RESNET_F16_TWINS)
+# the twins of csrc/resnet_bwd.hip (training the encoder), the header's UCLSTM_RESNET_BWD_F16_TWINS: a list of their own for the same reason
+RESNET_BWD_F16_TWINS = ['uclstm_maxpool3s2_bwd', 'uclstm_bn_add_relu_bwd_reduce', 'uclstm_bn_add_relu_bwd_apply']
+_ALL_F16_TWINS = frozenset(F16_TWINS) | frozenset(RESNET_F16_TWINS) | frozenset(RESNET_BWD_F16_TWINS)
 
 
 def header_symbols() -> list[str]:

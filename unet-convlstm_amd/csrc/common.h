@@ -45,6 +45,9 @@
 #define uclstm_upsample2_bwd uclstm_upsample2_bwd_f16
 #define uclstm_head3x3_fwd uclstm_head3x3_fwd_f16
 #define uclstm_head3x3_bwd uclstm_head3x3_bwd_f16
+#define uclstm_maxpool3s2_bwd uclstm_maxpool3s2_bwd_f16
+#define uclstm_bn_add_relu_bwd_reduce uclstm_bn_add_relu_bwd_reduce_f16
+#define uclstm_bn_add_relu_bwd_apply uclstm_bn_add_relu_bwd_apply_f16
 // a body that reads 16-bit data behind an entry point that exists ONCE (explicit activation-type argument, no _f16 twin):
 // internal name, not in the public header; the bfloat16 pass defines the dispatcher
 #define UCLSTM_ACT_IMPL(fn) fn##_impl_f16

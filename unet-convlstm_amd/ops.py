@@ -649,11 +649,13 @@ def prepack_end() -> None:
     _PACK_RECORDING = False
 
 
-def pack_weights(desc: L.PackDesc, w: torch.Tensor, elem_offset: int = 0, dtype=BF16) -> torch.Tensor:
-    """f32 reference-layout weight -> 16-bit panel of ``dtype`` (the dtype of the activations it will multiply)."""
+def pack_weights(desc: L.PackDesc, w: torch.Tensor, elem_offset: int = 0, dtype=BF16, lookahead: bool = True) -> torch.Tensor:
+    """f32 reference-layout weight -> 16-bit panel of ``dtype`` (the dtype of the activations it will multiply).
+    ``lookahead=False``: ``w`` is a temporary derived from a parameter inside the step (resnet.s2_dgrad_weight), not a parameter: the
+    look-ahead plan, which replays from the tensors it recorded at the start of the NEXT step, must not know it."""
     _dev(w, F32, "weight")
     key = None
-    if _PACK_RECORDING:
+    if _PACK_RECORDING and lookahead:
         key = (w.data_ptr(), elem_offset, bytes(desc), dtype)
         d2 = L.PackDesc()
         C.memmove(C.byref(d2), C.byref(desc), C.sizeof(L.PackDesc))

@@ -8,8 +8,12 @@
 implicit-GEMM family for the convolutions (stride 2 is a descriptor with ``scale = 2``), ``ops.ConvBNReLU`` for the decoder
 stages, this package's ``ConvLSTM`` for the recurrences and the kernels of ``csrc/resnet.hip`` around them.
 
-Not part of this module: training an unfrozen encoder (there is no strided input-gradient or weight-gradient GEMM),
-``GraphedTrainStep``, ``StreamingPredictor`` and ``sync_batchnorm`` with this model, and a fused upsample.
+The encoder trains after ``model.unfreeze_encoder(stages)``: the stages from the lowest trainable one up run through the autograd
+Functions below (``EncConv``, ``BnRelu``, ``BnAddRelu``, ``MaxPool3s2``) -- the kernels of ``csrc/resnet_bwd.hip``, the stride-2
+weight gradients as descriptors of the weight-gradient family over the OUTPUT grid, and the stride-2 input gradient as one launch of
+the forward family over the four parities of the input pixel (``conv_s2_dgrad``).
+
+Not part of this module: ``GraphedTrainStep``, ``StreamingPredictor`` and ``sync_batchnorm`` with this model, and a fused upsample.
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ Tensor = torch.Tensor
 ENCODER_CHANNELS = (2, 64, 64, 128, 256, 512)          # smp's resnet18 encoder.out_channels with in_channels = 2
 DECODER_CHANNELS = (256, 128, 64, 32, 16)              # train/resnet18.py:32
 HEAD_MAX_OUT = 4                                       # uclstm_head3x3_*: output channels are register accumulators
+ENCODER_STAGES = ("stem", "layer1", "layer2", "layer3", "layer4")          # what unfreeze_encoder() names
 
 # LAUNCH_LOG kinds of the head's parameter-gradient reduction, next to ops.ATOMIC_KINDS / ops.ORDERED_KINDS
 ATOMIC_KINDS = ops.ATOMIC_KINDS + ("head3x3_bwd",)
@@ -248,6 +253,292 @@ class Head3x3(ops._GradAwareFunction):
         return da, (dw if need_w else None), (db if need_b else None)
 
 
+# ---------------------------------------------------------------------------------------------
+# backward of the encoder (csrc/resnet_bwd.hip and the strided descriptors of the GEMM families)
+# ---------------------------------------------------------------------------------------------
+def maxpool3s2_bwd(a: Tensor, dp: Tensor, dskip: Optional[Tensor]) -> Tensor:
+    """Gradient of ``a`` from the gradient ``dp`` of ``maxpool3s2(a)`` plus ``dskip`` (or None), the gradient of its other use."""
+    N, H, W, Cp = a.shape
+    da = torch.empty_like(a)
+    dp = dp.contiguous()
+    dskip = None if dskip is None else dskip.contiguous()
+    ops._timed_hbm("maxpool3s2_bwd", 2.0 * (a.numel() * (3 if dskip is not None else 2) + dp.numel()),
+                   lambda: L.check(ops._k(a).uclstm_maxpool3s2_bwd(_p(a), _p(dp), _p(dskip), _p(da), N, H, W, Cp, _stream()), "maxpool3s2_bwd"))
+    return da
+
+
+class MaxPool3s2(torch.autograd.Function):
+    """MaxPool2d(3, 2, 1) of ``a`` plus ``a`` itself as a second output (the skip ConvLSTM's input): the two gradients of the
+    stem's activation are added inside the pooling backward kernel (ops.MaxPool2Skip does the same for the UNet)."""
+
+    @staticmethod
+    def forward(ctx, a):
+        ctx.save_for_backward(a)
+        return maxpool3s2(a), a.view_as(a)
+
+    @staticmethod
+    def backward(ctx, dp, dskip):
+        return dskip if dp is None else maxpool3s2_bwd(ctx.saved_tensors[0], dp, dskip)
+
+
+# taps of conv3x3 / stride 2 / pad 1 that reach input parity p from the output row j + t: input row 2j + p = 2(j + t) + k - 1
+_S2_TAP = ((1, None), (2, 0))          # [p][t] -> k (None: no such tap)
+_S2_INDEX: dict = {}                   # device -> the 16 (py, px, ty, tx) -> tap indices (9 = the zero tap), uploaded once
+
+
+def s2_dgrad_weight(w: Tensor, w_ds: Optional[Tensor] = None) -> Tensor:
+    """Weight of the input gradient of conv3x3 / stride 2 / pad 1 as four stride-1 problems, f32 ``[Co, Ci, py, px, ty, tx]``: the
+    input pixel (2j + py, 2i + px) reads ``dz`` at (j + ty, i + tx) through ``w[co, ci, ky, kx]`` with ky = 1 for py = 0 (ty = 0 only)
+    and ky = 2, 0 for py = 1 (ty = 0, 1); unused taps are zero.  ``w_ds`` (the block's conv1x1 / stride 2, ``[Co, Ci, 1, 1]``) is
+    appended along dim 0 as a second source that reaches parity (0, 0) through tap (0, 0) only.  9 tap products per 4 pixels."""
+    Co, Ci = w.shape[0], w.shape[1]
+    idx = _S2_INDEX.get(w.device)
+    if idx is None:
+        idx = _S2_INDEX[w.device] = torch.tensor(
+            [9 if (_S2_TAP[py][ty] is None or _S2_TAP[px][tx] is None) else _S2_TAP[py][ty] * 3 + _S2_TAP[px][tx]
+             for py in (0, 1) for px in (0, 1) for ty in (0, 1) for tx in (0, 1)], device=w.device)
+    wz = torch.nn.functional.pad(w.reshape(Co, Ci, 9), (0, 1))                    # column 9: the zero tap
+    out = wz[:, :, idx]
+    if w_ds is not None:
+        ds = torch.nn.functional.pad(w_ds.reshape(w_ds.shape[0], Ci, 1), (0, 15))          # (py, px, ty, tx) = 0 only
+        out = torch.cat([out, ds], 0)
+    return out.reshape(-1, Ci, 2, 2, 2, 2).contiguous()
+
+
+def s2_dgrad_pack_desc(Ci: int, Co: int, nsrc: int) -> L.PackDesc:
+    """Panel of ``s2_dgrad_weight``: rows (parity, ci) -- four segments of cpad(Ci) rows -- and K = (tap (ty, tx), source, co)."""
+    d = L.PackDesc()
+    d.N, d.taps, d.nsrc = 4 * cpad(Ci), 4, nsrc
+    d.kseg[0], d.kseg[1] = kseg(cpad(Co)), (kseg(cpad(Co)) if nsrc > 1 else 0)
+    d.cvalid[0], d.cvalid[1] = Co, (Co if nsrc > 1 else 0)
+    d.choff[0], d.choff[1] = 0, Co
+    d.Ktot = 4 * (d.kseg[0] + d.kseg[1])
+    d.n_mode, d.n_valid, d.n_cp = L.NMODE_TAPMAJOR, Ci, cpad(Ci)
+    d.k_mode, d.k_hdp, d.k_hd, d.tap_flip = L.KMODE_IDENTITY, 0, 0, 0
+    d.stride_n, d.stride_k, d.stride_tap, d.stride_ntap = 16, Ci * 16, 1, 4
+    return d
+
+
+def conv_s2_dgrad(dz: Tensor, weight: Tensor, dz_ds: Optional[Tensor] = None, w_ds: Optional[Tensor] = None) -> Tensor:
+    """Input gradient of conv3x3 / stride 2 / pad 1 (plus, folded in as a second source of the same launch, that of the conv1x1 /
+    stride 2 of the same input): ONE forward-family launch with ktap 2 on the Ho x Wo grid of ``dz`` and four output segments with
+    scale 2, oy = py, ox = px (the layout ConvT2x2 writes forward).  The input is (2 Ho, 2 Wo): even sizes only."""
+    n, Ho, Wo, _ = dz.shape
+    Co, Ci = weight.shape[0], weight.shape[1]
+    nsrc = 1 if dz_ds is None else 2
+    dd = s2_dgrad_pack_desc(Ci, Co, nsrc)
+    # the rearranged weight is a temporary: packed in line, never by the look-ahead plan
+    wd = ops.pack_weights(dd, s2_dgrad_weight(weight, w_ds if nsrc > 1 else None), 0, dz.dtype, lookahead=False)
+    Cip = cpad(Ci)
+    dx = torch.empty((n, 2 * Ho, 2 * Wo, Cip), dtype=dz.dtype, device=dz.device)
+    segs = [(dx, t * Cip, (t + 1) * Cip, 0, 2, t // 2, t % 2) for t in range(4)]
+    srcs = [SrcView(dz)] + ([SrcView(dz_ds)] if nsrc > 1 else [])
+    ops.igemm_store(srcs, wd, (Ho, Wo), n, segs, ktap=2, pad=0)
+    return dx
+
+
+def _bn_args(bn: nn.BatchNorm2d, pending: list):
+    """What EncConv needs of a BatchNorm to form its constants (no gradient flows through these; BnRelu / BnAddRelu own gamma, beta)."""
+    training, mom = _bn_mode(bn)
+    if training and bn.num_batches_tracked is not None:
+        pending.append((bn.num_batches_tracked, 1))
+    return bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, training, mom, bn.eps
+
+
+def _conv_stats(x: Tensor, weight: Tensor, pd: L.PackDesc, bn, k: int, s: int, pad: int, Ho: int, Wo: int):
+    """(z, par): the convolution's pre-BatchNorm output and (scale, shift, mean, rstd) [4, 1, Cop] -- of the batch, with the running
+    statistics updated, or (evaluation statistics with a backward pass) of the running statistics."""
+    gamma, beta, rm, rv, training, mom, eps = bn
+    n, Co, dev = x.shape[0], weight.shape[0], x.device
+    Cop = cpad(Co)
+    wp = ops.pack_weights(pd, weight, 0, x.dtype)
+    z = torch.empty((n, Ho, Wo, Cop), dtype=x.dtype, device=dev)
+    stats = None
+    if training:
+        stats = torch.empty((1, L.lib.uclstm_igemm_tiles_per_group(n, Ho, Wo, 1, Cop), Cop, 2), dtype=F32, device=dev)
+    else:
+        ops.join_forward_side(dev)
+    ops.igemm_store([SrcView(x)], wp, (Ho, Wo), n, [(z, 0, Cop, 0, 1, 0, 0)], ktap=k, scale=s, pad=pad, groups=1, stats=stats)
+    par, _ = ops._bn_forward_stats(stats, n, Ho, Wo, 1, Co, gamma, beta, rm, rv, mom, eps, "plain")
+    return z, par
+
+
+class EncConv(ops._GradAwareFunction):
+    """A bias-free convolution of the trainable encoder and its BatchNorm constants: ``(z, par, z_ds, par_ds)``, ``z`` the
+    pre-BatchNorm output.  ``w_ds``: the conv1x1 / stride 2 of the same input (a strided BasicBlock), so that the block's input
+    gradient is ONE launch (conv_s2_dgrad).  ``im2col``: ``x`` is the pre-gathered 7x7 stem matrix, which gets no gradient.
+    Backward: weight gradients over the OUTPUT grid (ktap k, scale = stride), through ops.wgrad_into_param."""
+
+    @staticmethod
+    def forward(ctx, x, weight, w_ds, bn, bn_ds, stride, im2col):
+        ops._dev(x, ops.ACT, "activation")
+        n, Hs, Ws, Cxp = x.shape
+        Co, Ci = weight.shape[0], weight.shape[1]
+        if im2col:
+            k, s, pad, Ho, Wo = 1, 1, 0, Hs, Ws
+        else:
+            k, s = weight.shape[2], stride
+            pad, Ho, Wo = k // 2, (Hs - 1) // s + 1, (Ws - 1) // s + 1
+            if s == 2 and (Hs % 2 or Ws % 2):
+                raise UclstmError("EncConv: a stride-2 convolution with a backward pass needs even input sizes")
+        z, par = _conv_stats(x, weight, EncConv._desc(weight, Cxp, im2col), bn, k, s, pad, Ho, Wo)
+        z_ds = par_ds = None
+        if w_ds is not None:
+            z_ds, par_ds = _conv_stats(x, w_ds, conv_desc(Co, Ci, 1, Cxp), bn_ds, 1, s, 0, Ho, Wo)
+        ctx.mark_non_differentiable(*[t for t in (par, par_ds) if t is not None])
+        ctx.save_for_backward(x, weight, w_ds)
+        ctx.geom = (k, s, pad, Ho, Wo, im2col)
+        if ops._will_backward(ctx):
+            ops.note_use(weight, w_ds)
+        return z, par, z_ds, par_ds
+
+    @staticmethod
+    def _desc(weight, Cxp, im2col):
+        Co, Ci = weight.shape[0], weight.shape[1]
+        return im2col7_pack_desc(Co, Ci, Cxp) if im2col else conv_desc(Co, Ci, weight.shape[2], Cxp)
+
+    @staticmethod
+    def _wgrad(x, weight, dz, pd, k, s, pad, Ho, Wo):
+        n, Cop = x.shape[0], dz.shape[3]
+        return ops.wgrad_into_param(weight, pd, [x, dz], lambda: ops.igemm_wgrad([SrcView(x)], [(dz, 0, Cop, 0, 1, 0, 0)], pd.N, pd.Ktot,
+                                                                                 (Ho, Wo), n, ktap=k, scale=s, pad=pad))
+
+    @staticmethod
+    def backward(ctx, dz, _dpar, dz_ds, _dpar_ds):
+        x, weight, w_ds = ctx.saved_tensors
+        k, s, pad, Ho, Wo, im2col = ctx.geom
+        n, Cxp = x.shape[0], x.shape[3]
+        Co, Ci = weight.shape[0], weight.shape[1]
+        dz = dz.contiguous()
+        dz_ds = None if (dz_ds is None or w_ds is None) else dz_ds.contiguous()
+        dweight = dw_ds = dx = None
+        if ctx.needs_input_grad[1]:
+            dweight = EncConv._wgrad(x, weight, dz, EncConv._desc(weight, Cxp, im2col), k, s, pad, Ho, Wo)
+        if dz_ds is not None and ctx.needs_input_grad[2]:
+            dw_ds = EncConv._wgrad(x, w_ds, dz_ds, conv_desc(Co, Ci, 1, Cxp), 1, s, 0, Ho, Wo)
+        if ctx.needs_input_grad[0] and not im2col:
+            if s == 2:
+                dx = conv_s2_dgrad(dz, weight, dz_ds, w_ds)
+            else:
+                dd = ops.conv_dgrad_pack_desc(Co, Ci, Ci)
+                wd = ops.pack_weights(dd, weight, 0, dz.dtype)
+                dx = torch.empty_like(x)
+                ops.igemm_store([SrcView(dz)], wd, (Ho, Wo), n, [(dx, 0, dd.N, 0, 1, 0, 0)], ktap=3, pad=1)
+        return dx, dweight, dw_ds, None, None, None, None
+
+
+def _bn_param_grads(need_gamma: bool, need_beta: bool, gamma: Tensor, beta: Tensor, sums: Tensor, Co: int):
+    """(dgamma, dbeta) for autograd from the sums (sum g, sum g*xhat) [1, Cop, 2]; (None, None) after the attached gradient buffers
+    were written directly (the route of ops.ConvBNReLU._param_grads); nothing is launched for a frozen pair."""
+    g_gamma, g_beta = ops.direct_grad(gamma), ops.direct_grad(beta)
+    if need_gamma and need_beta and g_gamma is not None and g_beta is not None:
+        def launch():
+            L.check(L.lib.uclstm_bn_bwd_param_grads(_p(sums), 1, sums.shape[1], Co, _p(g_gamma), _p(g_beta), 1, _stream()), "bn_bwd_param_grads")
+            ops.grad_written(gamma)
+            ops.grad_written(beta)
+
+        if ops.ASYNC_WGRAD and ops.PARAM_GRADS_ON_SIDE:
+            ops._on_side(sums.device, launch, (sums,))
+            ops._schedule_join(sums.device)
+        else:
+            launch()
+        return None, None
+    return (sums[0, :Co, 1].contiguous() if need_gamma else None), (sums[0, :Co, 0].contiguous() if need_beta else None)
+
+
+class BnRelu(ops._GradAwareFunction):
+    """``relu(z*scale + shift)`` with the constants ``par`` of EncConv; backward with uclstm_bn_bwd_reduce / _apply as one group.
+    ``training`` False: evaluation statistics with a backward pass (zero sums in the apply pass: dz = scale*g)."""
+
+    @staticmethod
+    def forward(ctx, z, par, gamma, beta, training):
+        a = torch.empty_like(z)
+        pixels, Cp = z.numel() // z.shape[-1], z.shape[-1]
+        ops._timed_hbm("bn_apply_relu", 4.0 * z.numel(),
+                       lambda: L.check(ops._k(z).uclstm_bn_apply_relu(_p(z), _p(a), _p(par[0]), _p(par[1]), pixels, pixels, Cp, _stream()),
+                                       "bn_apply_relu"))
+        ctx.save_for_backward(z, par, gamma, beta)
+        ctx.training = training
+        if ops._will_backward(ctx):
+            ops.note_use(gamma, beta)
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        z, par, gamma, beta = ctx.saved_tensors
+        need_z, _, need_gamma, need_beta, _ = ctx.needs_input_grad
+        pixels, Cp, dev = z.numel() // z.shape[-1], z.shape[-1], z.device
+        K, da = ops._k(z), da.contiguous()
+        pq = (_p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]))
+        sums = None
+        if ctx.training or need_gamma or need_beta:
+            sums = torch.empty((1, Cp, 2), dtype=F32, device=dev)
+            partials = torch.empty((int(L.lib.uclstm_bn_bwd_reduce_rows(pixels, pixels)), Cp, 2), dtype=F32, device=dev)
+            ops._timed_hbm("bn_bwd_reduce", 4.0 * z.numel(),
+                           lambda: L.check(K.uclstm_bn_bwd_reduce(_p(z), _p(da), *pq, _p(partials), _p(sums), pixels, pixels, Cp, _stream()),
+                                           "bn_bwd_reduce"))
+        dgamma, dbeta = _bn_param_grads(need_gamma, need_beta, gamma, beta, sums, gamma.shape[0]) if (need_gamma or need_beta) else (None, None)
+        dz = None
+        if need_z:
+            dz = torch.empty_like(z)
+            sums_dz = sums if ctx.training else torch.zeros((1, Cp, 2), dtype=F32, device=dev)
+            ops._timed_hbm("bn_bwd_apply", 6.0 * z.numel(),
+                           lambda: L.check(K.uclstm_bn_bwd_apply(_p(z), _p(da), *pq, _p(sums_dz), _p(dz), pixels, pixels, Cp, _stream()),
+                                           "bn_bwd_apply"))
+        return dz, None, dgamma, dbeta, None
+
+
+class BnAddRelu(ops._GradAwareFunction):
+    """Tail of a BasicBlock, ``relu(bn(z) + bn_r(r))`` (``rpar`` None: ``r`` is the block's input as it is).  Backward with
+    uclstm_bn_add_relu_bwd_reduce / _apply: the sums of both BatchNorms from one pass over (z, r, da), then dz and dr from a
+    second; a branch nobody needs is not written.  ``training`` / ``rtraining`` False: evaluation statistics, per branch."""
+
+    @staticmethod
+    def forward(ctx, z, par, gamma, beta, r, rpar, rgamma, rbeta, training, rtraining):
+        a = bn_add_relu(z, par, r, rpar)
+        ctx.save_for_backward(z, par, gamma, beta, r, rpar, rgamma, rbeta)
+        ctx.training, ctx.rtraining = training, rtraining
+        if ops._will_backward(ctx):
+            ops.note_use(gamma, beta, rgamma, rbeta)
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        z, par, gamma, beta, r, rpar, rgamma, rbeta = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        pixels, Cp, dev = z.numel() // z.shape[-1], z.shape[-1], z.device
+        K, da = ops._k(z), da.contiguous()
+        raff = rpar is not None
+        pq = (_p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]))
+        rq = (_p(rpar[0]), _p(rpar[1]), _p(rpar[2]), _p(rpar[3])) if raff else (None, None, None, None)
+        zero = None
+        sums = torch.empty((1, Cp, 2), dtype=F32, device=dev)
+        rsums = torch.empty((1, Cp, 2), dtype=F32, device=dev) if raff else None
+        need_reduce = (ctx.training and need[0]) or need[2] or need[3] or (raff and ((ctx.rtraining and need[4]) or need[6] or need[7]))
+        if need_reduce:
+            partials = torch.empty((int(L.lib.uclstm_bn_add_relu_bwd_rows(pixels)), Cp, 3), dtype=F32, device=dev)
+            ops._timed_hbm("bn_add_relu_bwd_reduce", 6.0 * z.numel(),
+                           lambda: L.check(K.uclstm_bn_add_relu_bwd_reduce(_p(z), *pq, _p(r), *rq, _p(da), _p(partials), _p(sums), _p(rsums),
+                                                                           pixels, Cp, _stream()), "bn_add_relu_bwd_reduce"))
+        dgamma, dbeta = _bn_param_grads(need[2], need[3], gamma, beta, sums, gamma.shape[0]) if (need[2] or need[3]) else (None, None)
+        drgamma = drbeta = None
+        if raff and (need[6] or need[7]):
+            drgamma, drbeta = _bn_param_grads(need[6], need[7], rgamma, rbeta, rsums, rgamma.shape[0])
+        dz = dr = None
+        if need[0] or need[4]:
+            if not (ctx.training and need_reduce) or (raff and not ctx.rtraining):
+                zero = torch.zeros((1, Cp, 2), dtype=F32, device=dev)
+            s_z = sums if (ctx.training and need_reduce) else zero
+            s_r = None if not raff else (rsums if (ctx.rtraining and need_reduce) else zero)
+            dz = torch.empty_like(z) if need[0] else None
+            dr = torch.empty_like(r) if need[4] else None
+            nb = 2.0 * z.numel() * (3 + (dz is not None) + (dr is not None))
+            ops._timed_hbm("bn_add_relu_bwd_apply", nb,
+                           lambda: L.check(K.uclstm_bn_add_relu_bwd_apply(_p(z), *pq, _p(s_z), _p(r), *rq, _p(s_r), _p(da), _p(dz), _p(dr),
+                                                                          pixels, Cp, _stream()), "bn_add_relu_bwd_apply"))
+        return dz, None, dgamma, dbeta, dr, None, drgamma, drbeta, None, None
+
+
 def _bn_mode(bn: nn.BatchNorm2d):
     """(uses batch statistics, momentum argument of the BatchNorm kernels) -- the rule of modules.DoubleConv._stage."""
     training = bn.training or not bn.track_running_stats
@@ -281,8 +572,9 @@ class PretrainedTemporalUNet(nn.Module):
     * A frozen encoder runs without autograd: no backward kernel is launched for it, and none for the input half of the skip
       ConvLSTMs' gate convolutions.  ``freeze_encoder`` only sets ``requires_grad=False``: after ``model.train()`` the frozen
       encoder still normalises with batch statistics and updates its running statistics, as the reference does.
-    * ``freeze_encoder=False`` constructs, loads and runs under ``torch.no_grad()``; a forward in grad mode while an encoder
-      parameter requires grad raises ``UclstmError`` (there is no strided input-gradient / weight-gradient GEMM).
+    * Training the encoder is opt-in: ``model.unfreeze_encoder(stages)`` (see there).  Without it, ``freeze_encoder=False``
+      constructs, loads and runs under ``torch.no_grad()``, and a forward in grad mode while an encoder parameter requires grad
+      raises ``UclstmError`` naming that method.
     * BatchNorm statistics are those of the whole ``B*T`` batch (one group), in the encoder and in the decoder.
     """
 
@@ -310,6 +602,7 @@ class PretrainedTemporalUNet(nn.Module):
         self.lstm_skips = nn.ModuleList(ConvLSTM(ch, ch, num_layers=lstm_layers, kernel_size=3) for ch in self.skip_channels)
         self.lstm_skips[0].requires_grad_(False)          # never computed: see the class docstring
         self.out_channels = out_channels
+        self._encoder_opt_in = False                       # unfreeze_encoder(): see there
 
     def load_encoder_weights(self, weights) -> None:
         """``weights``: a torchvision-layout ResNet18 state_dict or a path to one."""
@@ -318,6 +611,70 @@ class PretrainedTemporalUNet(nn.Module):
         sd = {k: v for k, v in weights.items() if not k.startswith("fc.")}
         sd["conv1.weight"] = adapt_first_conv(sd["conv1.weight"])
         self.encoder.load_state_dict(sd, strict=True)
+
+    def encoder_stage(self, name: str) -> list:
+        """The modules of one encoder stage: ``"stem"`` (conv1, bn1), ``"layer1"`` .. ``"layer4"``."""
+        if name not in ENCODER_STAGES:
+            raise UclstmError(f"PretrainedTemporalUNet: unknown encoder stage {name!r} (stages: {', '.join(ENCODER_STAGES)})")
+        enc = self.encoder
+        return [enc.conv1, enc.bn1] if name == "stem" else [getattr(enc, name)]
+
+    def unfreeze_encoder(self, stages="all") -> "PretrainedTemporalUNet":
+        """Opt in to training the encoder: ``requires_grad=True`` on the parameters of the named stages (``"all"``, one name or a
+        sequence of ``"stem"``, ``"layer1"`` .. ``"layer4"``), ``False`` on every other encoder parameter; ``()`` freezes the
+        whole encoder again.  From then on each parameter's own ``requires_grad`` decides what is computed (weight, gamma and
+        beta independently, so single parameters may be toggled afterwards): stages below the lowest one with a trainable
+        parameter run without autograd exactly as in the frozen model, the others keep their activations and run the backward
+        kernels of csrc/resnet_bwd.hip and the strided input- / weight-gradient descriptors.  BatchNorm mode stays per module:
+        after ``model.train(); model.encoder.eval()`` the weights train against frozen statistics."""
+        names = ENCODER_STAGES if stages == "all" else ((stages,) if isinstance(stages, str) else tuple(stages))
+        chosen = {id(p) for n in names for m in self.encoder_stage(n) for p in m.parameters()}
+        for p in self.encoder.parameters():
+            p.requires_grad = id(p) in chosen
+        self._encoder_opt_in = True
+        return self
+
+    def _first_trainable_stage(self) -> Optional[int]:
+        """Index into ENCODER_STAGES of the lowest stage with a parameter that requires grad (None: the encoder is frozen)."""
+        for i, name in enumerate(ENCODER_STAGES):
+            if any(p.requires_grad for m in self.encoder_stage(name) for p in m.parameters()):
+                return i
+        return None
+
+    # -- encoder: trainable stages (autograd Functions; everything below the lowest trainable stage stays forward-only) -----
+    def _t_block(self, x: Tensor, blk: BasicBlock, pending: list) -> Tensor:
+        ds = blk.downsample
+        z1, par1, zr, rpar = EncConv.apply(x, blk.conv1.weight, None if ds is None else ds[0].weight, _bn_args(blk.bn1, pending),
+                                           None if ds is None else _bn_args(ds[1], pending), blk.conv1.stride[0], False)
+        a1 = BnRelu.apply(z1, par1, blk.bn1.weight, blk.bn1.bias, _bn_mode(blk.bn1)[0])
+        z2, par2, _, _ = EncConv.apply(a1, blk.conv2.weight, None, _bn_args(blk.bn2, pending), None, 1, False)
+        if ds is None:
+            return BnAddRelu.apply(z2, par2, blk.bn2.weight, blk.bn2.bias, x, None, None, None, _bn_mode(blk.bn2)[0], False)
+        return BnAddRelu.apply(z2, par2, blk.bn2.weight, blk.bn2.bias, zr, rpar, ds[1].weight, ds[1].bias, _bn_mode(blk.bn2)[0],
+                               _bn_mode(ds[1])[0])
+
+    def _encode_trainable(self, x_seq: Tensor, pending: list, first: int):
+        """``_encode`` with the stages from ``first`` on under autograd.  The stem never computes an input gradient."""
+        enc = self.encoder
+        col = im2col7x7s2_first(x_seq)
+        if first == 0:
+            z, par, _, _ = EncConv.apply(col, enc.conv1.weight, None, _bn_args(enc.bn1, pending), None, 2, True)
+            f1 = BnRelu.apply(z, par, enc.bn1.weight, enc.bn1.bias, _bn_mode(enc.bn1)[0])
+            a, f1 = MaxPool3s2.apply(f1)
+        else:
+            with torch.no_grad():
+                f1 = self._conv_bn_relu(col, enc.conv1, enc.bn1, pending, im2col=True)
+                a = maxpool3s2(f1)
+        feats = [f1]
+        for li, layer in enumerate((enc.layer1, enc.layer2, enc.layer3, enc.layer4), start=1):
+            for blk in layer:
+                if li >= first:
+                    a = self._t_block(a, blk, pending)
+                else:
+                    with torch.no_grad():
+                        a = self._block(a, blk, pending)
+            feats.append(a)
+        return feats
 
     # -- encoder: forward-only stages -----------------------------------------------------------
     def _conv_bn(self, x: Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool, pending: list, im2col: bool = False):
@@ -398,9 +755,10 @@ class PretrainedTemporalUNet(nn.Module):
         B, T, _, H, W = x_seq.shape
         if H % 32 or W % 32:
             raise UclstmError(f"PretrainedTemporalUNet: H and W must be multiples of 32 (five stride-2 stages), got {H} x {W}")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.encoder.parameters()):
-            raise UclstmError("PretrainedTemporalUNet: training an unfrozen encoder is not supported (no strided input-gradient or "
-                              "weight-gradient GEMM): construct with freeze_encoder=True, or run under torch.no_grad()")
+        if torch.is_grad_enabled() and not self._encoder_opt_in and any(p.requires_grad for p in self.encoder.parameters()):
+            raise UclstmError("PretrainedTemporalUNet: training an unfrozen encoder is opt-in: call model.unfreeze_encoder() (all "
+                              "stages, or e.g. (\"layer3\", \"layer4\")) first, construct with freeze_encoder=True, or run under "
+                              "torch.no_grad()")
         pending: list = []
         try:
             return self._forward(x_seq.contiguous().float(), pending), None
@@ -411,8 +769,12 @@ class PretrainedTemporalUNet(nn.Module):
 
     def _forward(self, x_seq: Tensor, pending: list) -> Tensor:
         B, T, _, H, W = x_seq.shape
-        with torch.no_grad():
-            feats = self._encode(x_seq, pending)
+        first = self._first_trainable_stage() if (torch.is_grad_enabled() and self._encoder_opt_in) else None
+        if first is None:
+            with torch.no_grad():
+                feats = self._encode(x_seq, pending)
+        else:
+            feats = self._encode_trainable(x_seq, pending, first)
 
         def run(lstm: ConvLSTM, f: Tensor) -> Tensor:          # [T*B,h,w,C] -> the last layer's h for all steps, same shape
             out, _ = lstm.seq_nhwc(f.view(T, B, *f.shape[1:]), None)
