@@ -141,6 +141,20 @@ int32_t uclstm_igemm_fwd_group(const uclstm_igemm_desc* descs, int32_t n, void* 
 /* Validation only: the block count of the launch uclstm_igemm_fwd_group would make (>= 1), or UCLSTM_E_*. */
 int32_t uclstm_igemm_fwd_group_blocks(const uclstm_igemm_desc* descs, int32_t n);
 
+/* The same for the 128 x 128 per-tap shape: n (1..4) INDEPENDENT descriptors as ONE launch, for the cell steps the patch shape
+ * cannot take (it needs 256 | pixels) -- the small images of a frame-by-frame rollout, whose grids of a few tiles or a few
+ * dozen split-K blocks would otherwise each pay a launch, a fill and a drain of their own.  Every member must be a descriptor
+ * uclstm_igemm_fwd would run on shape 0 (uclstm_igemm_fwd_shape == 0) with ktap == 3 and UCLSTM_EPI_LSTM or UCLSTM_EPI_ATOMIC
+ * in slab mode (acc_slab > 0), all with the same nsrc.  Anything else -- a patch-shape or 64 x 256 member, a 5x5 / 7x7 cell,
+ * atomic accumulation, mixed nsrc, n outside 1..4 -- is UCLSTM_E_BADARG and nothing is launched.  Members are ordered longest
+ * block first (K-steps per block; ties keep the caller's order) and every member's first block id is a multiple of 8, so a
+ * member's tile order is that of a launch of its own.  Results are bit-identical to n separate uclstm_igemm_fwd launches: the
+ * blocks run the same kernel body and slab mode stores, it does not add. */
+int32_t uclstm_igemm_fwd_group_tap(const uclstm_igemm_desc* descs, int32_t n, void* stream);
+/* Validation only: the block count of the launch uclstm_igemm_fwd_group_tap would make -- the sum of the members' own grids,
+ * each rounded up to a multiple of 8 -- or UCLSTM_E_*. */
+int32_t uclstm_igemm_fwd_group_tap_blocks(const uclstm_igemm_desc* descs, int32_t n);
+
 /* Weight gradient  dWp[n][k] (+)= sum_pixels dY[pixel][n] * A[pixel][k]  (f32 [N][Ktot], same
  * K order as the forward panel).  dY is read through seg[] (nseg >= 1); `splits` pixel ranges
  * (0 = chosen by the library for its tile shape and the 256 CUs) accumulate with f32 atomics, so dWp
@@ -790,6 +804,9 @@ UCLSTM_RESNET_F16_TWINS(UCLSTM_F16_TWIN)
 #define UCLSTM_RESNET_BWD_F16_TWINS(TWIN) \
     TWIN(uclstm_maxpool3s2_bwd) TWIN(uclstm_bn_add_relu_bwd_reduce) TWIN(uclstm_bn_add_relu_bwd_apply)
 UCLSTM_RESNET_BWD_F16_TWINS(UCLSTM_F16_TWIN)
+/* the twin of the per-tap group launch (the host mirror: _lib.TAP_GROUP_F16_TWINS) */
+#define UCLSTM_TAP_GROUP_F16_TWINS(TWIN) TWIN(uclstm_igemm_fwd_group_tap)
+UCLSTM_TAP_GROUP_F16_TWINS(UCLSTM_F16_TWIN)
 
 /* Library self-description (used by the loader to check the build). */
 int32_t uclstm_abi_version(void);

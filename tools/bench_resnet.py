@@ -14,7 +14,15 @@ the encoder trainable (``model.unfreeze_encoder``, two optimiser groups, the enc
 of the step that the backward kernels of csrc/resnet_bwd.hip take (HIP events around each of their launches in a few further steps), and
 those kernels alone at the step's shapes like the ones above.
 
+``--rollout`` (profiles/resnet_rollout.txt) measures frame-by-frame inference instead and does nothing else: the shipped
+configuration (lstm_layers = 2) at B = 1, T = --frames, for each of --rollout-sizes (64 and 256), frames/s of one T-frame sequence
+between HIP events -- median, min and max of --iters sequences after two untimed ones --
+  (a) the reference's method on this code (test.py:305-310): ``model(x[:, :t])`` for t = 1 .. T under no_grad, T (T + 1) / 2 frames of work;
+  (b) ``PretrainedStreamingPredictor`` eager;  (c) with HIP graphs;  (d) as (c) with ``ops.GROUP_LSTM = False``: every cell step a
+  launch of its own, what the group launches of ``ops.convlstm_tick`` replace.  (c) and (d) are timed alternately.
+
     python tools/bench_resnet.py [--steps 10] [--warmup 3] [--batch 32] [--frames 20] [--unfreeze STAGES] [--out FILE]
+    python tools/bench_resnet.py --rollout [--frames 20] [--rollout-sizes 64,256] [--iters 7] [--out profiles/resnet_rollout.txt]
 """
 import argparse
 import os
@@ -35,6 +43,8 @@ ap.add_argument("--frames", type=int, default=20)
 ap.add_argument("--size", type=int, default=64)
 ap.add_argument("--iters", type=int, default=7)
 ap.add_argument("--unfreeze", default=None, help="all, or a comma-separated list of stem, layer1 .. layer4")
+ap.add_argument("--rollout", action="store_true", help="measure frame-by-frame inference (B = 1) and nothing else")
+ap.add_argument("--rollout-sizes", default="64,256")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 if not torch.cuda.is_available():
@@ -47,6 +57,82 @@ def say(s=""):
     print(s, flush=True)
     lines.append(s)
 
+
+def rollout_record():
+    T = a.frames
+    say(f"# PretrainedTemporalUNet(lstm_layers=2), evaluation mode, bf16, B=1 T={T}, {torch.cuda.get_device_name(0)}")
+    say(f"# frames/s of one {T}-frame sequence between HIP events: median (min .. max) of {a.iters} sequences after 2 untimed ones")
+    torch.manual_seed(0)
+    model = U.PretrainedTemporalUNet(out_channels=1, lstm_layers=2).to(dev).eval()
+
+    def timed_once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return T / e0.elapsed_time(e1) * 1e3, out
+
+    def line(tag, what, fps):
+        fps = sorted(fps)
+        say(f"{tag} {what:58s} {fps[len(fps) // 2]:9.1f} frames/s ({fps[0]:.1f} .. {fps[-1]:.1f})   {1e3 / fps[len(fps) // 2]:7.3f} ms/frame")
+        return fps[len(fps) // 2]
+
+    for size in (int(v) for v in a.rollout_sizes.split(",")):
+        x = torch.randn(1, T, 2, size, size, generator=torch.Generator().manual_seed(size)).to(dev)
+        say()
+        say(f"## {size} x {size}")
+
+        def prefixes():
+            with torch.no_grad():
+                return torch.cat([model(x[:, :t])[0][:, -1:] for t in range(1, T + 1)], dim=1)
+
+        def rolled(pred, group):
+            def fn():
+                ops.GROUP_LSTM = group
+                try:
+                    pred.new_sequence()
+                    return pred.rollout(x)
+                finally:
+                    ops.GROUP_LSTM = True
+            return fn
+
+        eager = rolled(U.PretrainedStreamingPredictor(model, use_graph=False), True)
+        graph = rolled(U.PretrainedStreamingPredictor(model, use_graph=True), True)
+        single = rolled(U.PretrainedStreamingPredictor(model, use_graph=True), False)
+        runs = {"a": prefixes, "b": eager, "c": graph, "d": single}
+        outs = {}
+        for k, fn in runs.items():
+            for _ in range(2):
+                outs[k] = fn()
+        torch.cuda.synchronize()
+        fps = {k: [] for k in runs}
+        for _ in range(a.iters):
+            for k in ("a", "b", "c", "d", ):          # (c) and (d) alternate: neighbours in time see the same machine
+                fps[k].append(timed_once(runs[k])[0])
+        med = {}
+        med["a"] = line("(a)", f"prefix loop model(x[:, :t]), {T * (T + 1) // 2} frames of work", fps["a"])
+        med["b"] = line("(b)", "PretrainedStreamingPredictor, eager", fps["b"])
+        med["c"] = line("(c)", "PretrainedStreamingPredictor, HIP graphs", fps["c"])
+        med["d"] = line("(d)", "as (c) with ops.GROUP_LSTM = False (every cell step alone)", fps["d"])
+        rel = lambda k: float((outs["c"] - outs[k]).norm() / outs[k].norm())
+        say(f"(c) / (d) = {med['c'] / med['d']:.3f}, (c) / (a) = {med['c'] / med['a']:.1f}; rel-L2 of the {T} predictions of (c) against those of "
+            f"(a) {rel('a'):.2e}, (b) {rel('b'):.2e}, (d) {rel('d'):.2e}")
+        ops.LAUNCH_LOG = log = []
+        eager()
+        ops.LAUNCH_LOG = None
+        ticks = [e for e in log if e[0] == "tick"]
+        per_frame = len(ticks) // T
+        say(f"launches of ops.convlstm_tick per frame (two layers): {ticks[-per_frame:]}")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if a.rollout:
+    rollout_record()
+    raise SystemExit(0)
 
 B, T, HW = a.batch, a.frames, a.size
 say(f"# PretrainedTemporalUNet(lstm_layers=2, freeze_encoder=True), bf16, B={B} T={T} {HW}x{HW}, {torch.cuda.get_device_name(0)}")

@@ -29,7 +29,9 @@ int main() {
     const int chans[] = {8, 16, 24, 40, 64, 72, 128, 136, 256, 512, 1024, 2048, -8, 0, 4};
     const int imgs[] = {1, 2, 3, 4, 8, 20, 32, 48, 640, 0, -1};
     const int taps[] = {1, 2, 3, 5, 7, 0, 9};
-    long n_ok = 0, n_bad = 0, n_wg = 0, n_pk = 0;
+    long n_ok = 0, n_bad = 0, n_wg = 0, n_pk = 0, n_tg = 0;
+    uclstm_igemm_desc recent[5];                          // the last descriptors of the sweep: members of unrelated shapes
+    memset(recent, 0, sizeof recent);
     for (int it = 0; it < 20000; ++it) {
         uclstm_igemm_desc d;
         memset(&d, 0, sizeof d);
@@ -88,6 +90,35 @@ int main() {
         }
         (shp >= 0 ? n_ok : n_bad)++;
         if (d.Ktot > 0) (void)uclstm_igemm_ksplit_used(d.Ktot, d.ktap, d.ksplit);
+        // the per-tap group planner: n = 0 .. 5 members (1 .. 4 are valid), once over the last descriptors of the sweep (mixed
+        // shapes, epilogues and source counts: mostly refused) and once over variations of this one (mostly accepted when it is
+        // a 3x3 shape-0 cell or slab step).  A plan is a positive multiple of 8 blocks; a lone member is accepted exactly when
+        // uclstm_igemm_fwd_shape says 0 and the member rules hold.
+        recent[it % 5] = d;
+        const int n_mem = (int)(rnd() % 6);
+        const int tg_mixed = uclstm_igemm_fwd_group_tap_blocks(recent, n_mem);
+        uclstm_igemm_desc var[5];
+        for (int k = 0; k < 5; ++k) {
+            var[k] = d;
+            var[k].ksplit = 1 + (int)(rnd() % 17);
+            if (k && rnd() % 4 == 0) var[k].n_img = pick(imgs, 9);
+            if (k && rnd() % 16 == 0) var[k].nsrc = 3 - d.nsrc;
+        }
+        const int tg_var = uclstm_igemm_fwd_group_tap_blocks(var, n_mem);
+        const int tg_one = uclstm_igemm_fwd_group_tap_blocks(&d, 1);
+        const bool one_ok = shp == 0 && d.ktap == 3 && (d.epi == UCLSTM_EPI_LSTM || (d.epi == UCLSTM_EPI_ATOMIC && d.acc_slab > 0));
+        const int tgs[3] = {tg_mixed, tg_var, tg_one};
+        for (int k = 0; k < 3; ++k) {
+            if (tgs[k] < UCLSTM_E_NODEVICE || tgs[k] == 0 || (tgs[k] > 0 && tgs[k] % 8) || (k < 2 && tgs[k] > 0 && (n_mem < 1 || n_mem > 4))) {
+                fprintf(stderr, "igemm_fwd_group_tap_blocks returned %d (case %d, n %d)\n", tgs[k], k, n_mem);
+                return 1;
+            }
+            n_tg += tgs[k] > 0;
+        }
+        if ((tg_one > 0) != one_ok || uclstm_igemm_fwd_group_tap_blocks(nullptr, 1) != UCLSTM_E_BADARG) {
+            fprintf(stderr, "igemm_fwd_group_tap_blocks: lone member returned %d, shape %d\n", tg_one, shp);
+            return 1;
+        }
         if (d.n_img > 0 && d.groups > 0) (void)uclstm_igemm_tiles_per_group(d.n_img, d.H, d.W, d.groups, d.N);
 
         uclstm_wgrad_desc w;
@@ -150,7 +181,7 @@ int main() {
             (void)uclstm_bn_bwd_reduce_rows(pixels, pixels / (d.groups > 0 && d.n_img % d.groups == 0 ? d.groups : 1));
         }
     }
-    printf("host sanitizer sweep: 20000 descriptors, %ld forward plans, %ld refused, %ld weight-gradient plans, %ld pack jobs, no sanitizer report\n",
-           n_ok, n_bad, n_wg, n_pk);
+    printf("host sanitizer sweep: 20000 descriptors, %ld forward plans, %ld refused, %ld per-tap group plans, %ld weight-gradient plans, "
+           "%ld pack jobs, no sanitizer report\n", n_ok, n_bad, n_tg, n_wg, n_pk);
     return 0;
 }

@@ -115,6 +115,8 @@ _PROTOS = {
     "uclstm_igemm_ksplit_used": [_I, _I, _I],
     "uclstm_igemm_fwd_group": [C.POINTER(IgemmDesc), _I, _P],
     "uclstm_igemm_fwd_group_blocks": [C.POINTER(IgemmDesc), _I],
+    "uclstm_igemm_fwd_group_tap": [C.POINTER(IgemmDesc), _I, _P],
+    "uclstm_igemm_fwd_group_tap_blocks": [C.POINTER(IgemmDesc), _I],
     "uclstm_igemm_wgrad": [C.POINTER(WgradDesc), _P],
     "uclstm_igemm_wgrad_splits": [C.POINTER(WgradDesc)],
     "uclstm_igemm_wgrad_shape": [C.POINTER(WgradDesc)],
@@ -224,7 +226,9 @@ RESNET_F16_TWINS = ['uclstm_im2col7x7s2_first', 'uclstm_maxpool3s2_fwd', 'uclstm
                     'uclstm_head3x3_fwd', 'uclstm_head3x3_bwd']
 # the twins of csrc/resnet_bwd.hip (training the encoder), the header's UCLSTM_RESNET_BWD_F16_TWINS: a list of their own for the same reason
 RESNET_BWD_F16_TWINS = ['uclstm_maxpool3s2_bwd', 'uclstm_bn_add_relu_bwd_reduce', 'uclstm_bn_add_relu_bwd_apply']
-_ALL_F16_TWINS = frozenset(F16_TWINS) | frozenset(RESNET_F16_TWINS) | frozenset(RESNET_BWD_F16_TWINS)
+# the twin of the per-tap group launch (csrc/igemm_fwd.hip), the header's UCLSTM_TAP_GROUP_F16_TWINS: a list of its own for the same reason
+TAP_GROUP_F16_TWINS = ['uclstm_igemm_fwd_group_tap']
+_ALL_F16_TWINS = frozenset(F16_TWINS) | frozenset(RESNET_F16_TWINS) | frozenset(RESNET_BWD_F16_TWINS) | frozenset(TAP_GROUP_F16_TWINS)
 
 
 def header_symbols() -> list[str]:

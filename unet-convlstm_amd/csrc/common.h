@@ -11,6 +11,7 @@
 #if defined(UCLSTM_ACT_F16)
 #define uclstm_igemm_fwd uclstm_igemm_fwd_f16
 #define uclstm_igemm_fwd_group uclstm_igemm_fwd_group_f16
+#define uclstm_igemm_fwd_group_tap uclstm_igemm_fwd_group_tap_f16
 #define uclstm_igemm_wgrad uclstm_igemm_wgrad_f16
 #define uclstm_pack_weights uclstm_pack_weights_f16
 #define uclstm_pack_weights_batched uclstm_pack_weights_batched_f16

@@ -96,7 +96,9 @@ __device__ __forceinline__ float row16_sum(float v) {
 // The kernel body as a device function of (descriptor, derived constants, block id within this launch plan): the plain
 // kernel below passes blockIdx.x, the grouped kernel (several independent GEMMs in ONE launch) the block's index inside its
 // member's sub-grid.
-template <int EPI, int SHP, int NSRC, int KT = 3>
+// GRP: the body is inlined into a group kernel, where d and dv are members of the by-value group argument: every access must
+// use a constant index (see igemm_fwd_group_kernel).
+template <int EPI, int SHP, int NSRC, int KT = 3, bool GRP = false>
 __device__ __forceinline__ void igemm_fwd_body(const uclstm_igemm_desc& d, const Derived& dv, const int bid) {
 #if defined(__HIP_DEVICE_COMPILE__)      // the buffer-resource type does not exist in the host pass (the stub needs no body)
     using SH = Shape<SHP>;
@@ -398,7 +400,15 @@ __device__ __forceinline__ void igemm_fwd_body(const uclstm_igemm_desc& d, const
         // NSRC == 2: the source of this K-step is wave-uniform (`s`), the per-row values are picked with scalar-condition
         // selects (never by pointing a shared body at one of two register arrays: that sends the arrays to scratch)
         const bool s1 = NSRC > 1 && s != 0;
-        const uclstm_src S = d.src[s1 ? 1 : 0];
+        struct { int Ws, C; } S;
+        if constexpr (GRP) {      // field by field, a constant index each: d.src[s] is a runtime index into the kernel argument
+            S.Ws = s1 ? d.src[1].Ws : d.src[0].Ws;
+            S.C = s1 ? d.src[1].C : d.src[0].C;
+        } else {
+            const uclstm_src S_ = d.src[s1 ? 1 : 0];
+            S.Ws = S_.Ws;
+            S.C = S_.C;
+        }
         const __amdgpu_buffer_rsrc_t rs = s1 ? rsx1 : rsx0;
         const int tdy = tap / d.ktap;
         const uint32_t tapoff = (uint32_t)(2 * ((tdy * S.Ws + (tap - tdy * d.ktap)) * S.C + c0));      // wave-uniform -> soffset
@@ -737,25 +747,38 @@ struct FwdGroup {
     Derived dv[GROUP_MAX];
 };
 
-template <int NSRC>
-__global__ __launch_bounds__(Shape<2>::NT, 1) void igemm_fwd_group_kernel(const FwdGroup g) {
-    const int b = (int)blockIdx.x;
-    // constant member index in every access: all fields are read straight from the kernel-argument segment (a runtime index
-    // into the by-value struct would send the whole 2-KiB argument to scratch memory)
-#define UCLSTM_GROUP_MEMBER(j_)                                                                            \
+// constant member index in every access: all fields are read straight from the kernel-argument segment (a runtime index
+// into the by-value struct would send the whole 2-KiB argument to scratch memory)
+#define UCLSTM_GROUP_MEMBER(j_, SHP_)                                                                      \
     if (j_ < g.n && b >= g.first[j_] && b < g.first[j_ + 1]) {                                             \
         const int bid = b - g.first[j_];                                                                   \
         if (bid >= g.nblk[j_]) return;                                                                     \
-        if (g.d[j_].epi == UCLSTM_EPI_LSTM) igemm_fwd_body<UCLSTM_EPI_LSTM, 2, NSRC>(g.d[j_], g.dv[j_], bid);   \
-        else igemm_fwd_body<UCLSTM_EPI_ATOMIC, 2, NSRC>(g.d[j_], g.dv[j_], bid);                           \
+        if (g.d[j_].epi == UCLSTM_EPI_LSTM) igemm_fwd_body<UCLSTM_EPI_LSTM, SHP_, NSRC, 3, true>(g.d[j_], g.dv[j_], bid);   \
+        else igemm_fwd_body<UCLSTM_EPI_ATOMIC, SHP_, NSRC, 3, true>(g.d[j_], g.dv[j_], bid);               \
         return;                                                                                            \
     }
-    UCLSTM_GROUP_MEMBER(0)
-    UCLSTM_GROUP_MEMBER(1)
-    UCLSTM_GROUP_MEMBER(2)
-    UCLSTM_GROUP_MEMBER(3)
-#undef UCLSTM_GROUP_MEMBER
+
+template <int NSRC>
+__global__ __launch_bounds__(Shape<2>::NT, 1) void igemm_fwd_group_kernel(const FwdGroup g) {
+    const int b = (int)blockIdx.x;
+    UCLSTM_GROUP_MEMBER(0, 2)
+    UCLSTM_GROUP_MEMBER(1, 2)
+    UCLSTM_GROUP_MEMBER(2, 2)
+    UCLSTM_GROUP_MEMBER(3, 2)
 }
+
+// The same for the 128 x 128 per-tap shape (3x3 cells): the cell steps of the small images of a frame-by-frame rollout -- a
+// few tiles each, or a few dozen split-K blocks -- which the patch shape cannot take (it needs 256 | pixels).  Launch bounds
+// and dynamic LDS are those of igemm_fwd_kernel<., 0, .>, so two blocks share a CU as they do there.
+template <int NSRC>
+__global__ __launch_bounds__(Shape<0>::NT, Shape<0>::MINB) void igemm_fwd_tap_group_kernel(const FwdGroup g) {
+    const int b = (int)blockIdx.x;
+    UCLSTM_GROUP_MEMBER(0, 0)
+    UCLSTM_GROUP_MEMBER(1, 0)
+    UCLSTM_GROUP_MEMBER(2, 0)
+    UCLSTM_GROUP_MEMBER(3, 0)
+}
+#undef UCLSTM_GROUP_MEMBER
 
 // ------------------------------------------------------------------------------------------------------------------
 // 3x3 / pad 1 convolution with C_in = C_out = 64 on images whose width is a multiple of 64 (the full-resolution level of
@@ -1284,9 +1307,12 @@ extern "C" int32_t uclstm_igemm_fwd(const uclstm_igemm_desc* dp, void* stream) {
     return launch<UCLSTM_EPI_STORE, 0>(d, dv, nblk, st);
 }
 
-// Several independent GEMMs in one launch (igemm_fwd_group_kernel).  Every member must be a descriptor that uclstm_igemm_fwd
-// would run on the patch shape (uclstm_igemm_fwd_shape == 2) with the fused-cell or the split-K epilogue, and all members must
-// have the same number of sources.  query != 0: validate only and return the block count of the launch.
+// Several independent GEMMs in one launch (igemm_fwd_group_kernel / igemm_fwd_tap_group_kernel).  Every member must be a
+// descriptor that uclstm_igemm_fwd would run on the group's shape -- SHP 2: the patch shape (uclstm_igemm_fwd_shape == 2);
+// SHP 0: the 128 x 128 per-tap shape with a 3x3 kernel (uclstm_igemm_fwd_shape == 0, ktap == 3) -- with the fused-cell epilogue
+// or split-K slabs, and all members must have the same number of sources.  query != 0: validate only and return the block
+// count of the launch.
+template <int SHP>
 static int32_t fwd_group_run(const uclstm_igemm_desc* descs, int32_t n, void* stream, int query) {
     if (!descs || n < 1 || n > GROUP_MAX) return UCLSTM_E_BADARG;
     FwdGroup g{};
@@ -1300,8 +1326,9 @@ static int32_t fwd_group_run(const uclstm_igemm_desc* descs, int32_t n, void* st
         int64_t mg = 0;
         const int32_t rc = plan_fwd(d, dvs[i], shp, nblks[i], mg);
         if (rc != UCLSTM_OK) return rc;
-        if (shp != 2 || (c64_ok(d) && mg % 256 == 0)) return UCLSTM_E_BADARG;
+        if (shp != SHP || (c64_ok(d) && mg % 256 == 0)) return UCLSTM_E_BADARG;
         if (d.epi != UCLSTM_EPI_LSTM && d.epi != UCLSTM_EPI_ATOMIC) return UCLSTM_E_BADARG;
+        if (SHP == 0 && (d.ktap != 3 || (d.epi == UCLSTM_EPI_ATOMIC && d.acc_slab <= 0))) return UCLSTM_E_BADARG;
         if (d.nsrc != descs[0].nsrc) return UCLSTM_E_BADARG;
         work[i] = dvs[i].kper;              // K-steps per block: longest blocks get the lowest block ids
         order[i] = i;
@@ -1322,18 +1349,32 @@ static int32_t fwd_group_run(const uclstm_igemm_desc* descs, int32_t n, void* st
     for (int k = n; k <= GROUP_MAX; ++k) g.first[k] = (int)at;
     if (query) return (int32_t)at;
     hipStream_t st = (hipStream_t)stream;
-    if (descs[0].nsrc == 1) {
-        static bool a1 = false;
-        if (!a1) { (void)hipFuncSetAttribute((const void*)igemm_fwd_group_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, Shape<2>::SMEM); a1 = true; }
-        UCLSTM_LAUNCH((igemm_fwd_group_kernel<1>), dim3((unsigned)at), dim3(Shape<2>::NT), Shape<2>::SMEM, st, g);
+    if constexpr (SHP == 2) {
+        if (descs[0].nsrc == 1) {
+            static bool a1 = false;
+            if (!a1) { (void)hipFuncSetAttribute((const void*)igemm_fwd_group_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, Shape<2>::SMEM); a1 = true; }
+            UCLSTM_LAUNCH((igemm_fwd_group_kernel<1>), dim3((unsigned)at), dim3(Shape<2>::NT), Shape<2>::SMEM, st, g);
+        } else {
+            static bool a2 = false;
+            if (!a2) { (void)hipFuncSetAttribute((const void*)igemm_fwd_group_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, Shape<2>::SMEM); a2 = true; }
+            UCLSTM_LAUNCH((igemm_fwd_group_kernel<2>), dim3((unsigned)at), dim3(Shape<2>::NT), Shape<2>::SMEM, st, g);
+        }
     } else {
-        static bool a2 = false;
-        if (!a2) { (void)hipFuncSetAttribute((const void*)igemm_fwd_group_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, Shape<2>::SMEM); a2 = true; }
-        UCLSTM_LAUNCH((igemm_fwd_group_kernel<2>), dim3((unsigned)at), dim3(Shape<2>::NT), Shape<2>::SMEM, st, g);
+        if (descs[0].nsrc == 1) {
+            static bool t1 = false;
+            if (!t1) { (void)hipFuncSetAttribute((const void*)igemm_fwd_tap_group_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, Shape<0>::SMEM); t1 = true; }
+            UCLSTM_LAUNCH((igemm_fwd_tap_group_kernel<1>), dim3((unsigned)at), dim3(Shape<0>::NT), Shape<0>::SMEM, st, g);
+        } else {
+            static bool t2 = false;
+            if (!t2) { (void)hipFuncSetAttribute((const void*)igemm_fwd_tap_group_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, Shape<0>::SMEM); t2 = true; }
+            UCLSTM_LAUNCH((igemm_fwd_tap_group_kernel<2>), dim3((unsigned)at), dim3(Shape<0>::NT), Shape<0>::SMEM, st, g);
+        }
     }
     return UCLSTM_OK;
 }
-extern "C" int32_t uclstm_igemm_fwd_group(const uclstm_igemm_desc* descs, int32_t n, void* stream) { return fwd_group_run(descs, n, stream, 0); }
+extern "C" int32_t uclstm_igemm_fwd_group(const uclstm_igemm_desc* descs, int32_t n, void* stream) { return fwd_group_run<2>(descs, n, stream, 0); }
+extern "C" int32_t uclstm_igemm_fwd_group_tap(const uclstm_igemm_desc* descs, int32_t n, void* stream) { return fwd_group_run<0>(descs, n, stream, 0); }
 #ifndef UCLSTM_ACT_F16
-extern "C" int32_t uclstm_igemm_fwd_group_blocks(const uclstm_igemm_desc* descs, int32_t n) { return fwd_group_run(descs, n, nullptr, 1); }
+extern "C" int32_t uclstm_igemm_fwd_group_blocks(const uclstm_igemm_desc* descs, int32_t n) { return fwd_group_run<2>(descs, n, nullptr, 1); }
+extern "C" int32_t uclstm_igemm_fwd_group_tap_blocks(const uclstm_igemm_desc* descs, int32_t n) { return fwd_group_run<0>(descs, n, nullptr, 1); }
 #endif

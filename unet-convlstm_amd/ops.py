@@ -1129,13 +1129,16 @@ def igemm_lstm(x: Optional[torch.Tensor], h_prev: torch.Tensor, wp: torch.Tensor
     _igemm_launch(_lstm_desc(x, h_prev, wp, bias, c_prev, c_out, h_out, gates_out, ksize, pre_add), _k(wp), "igemm_fwd_lstm", "igemm_fwd(lstm)")
 
 
-def igemm_group(items, K, kind: str = "igemm_fwd_group") -> None:
-    """``items``: [(desc, flops, nbytes, note)] of INDEPENDENT launches -> one uclstm_igemm_fwd_group launch."""
+def igemm_group(items, K, kind: str = "igemm_fwd_group", tap: bool = False) -> None:
+    """``items``: [(desc, flops, nbytes, note)] of INDEPENDENT launches -> one uclstm_igemm_fwd_group launch (``tap``: one
+    uclstm_igemm_fwd_group_tap launch, the group of the 128 x 128 per-tap shape)."""
     arr = (L.IgemmDesc * len(items))(*[it[0] for it in items])
     for it in items:
         _log_shape(it[0])
-    _timed(kind + "[patch128x256]" if PROFILE is not None else kind, sum(it[1] for it in items),
-           lambda: L.check(K.uclstm_igemm_fwd_group(arr, len(items), _stream()), "igemm_fwd_group"),
+    entry, what, shape = (K.uclstm_igemm_fwd_group_tap, "igemm_fwd_group_tap", "[pertap128x128]") if tap else \
+                         (K.uclstm_igemm_fwd_group, "igemm_fwd_group", "[patch128x256]")
+    _timed(kind + shape if PROFILE is not None else kind, sum(it[1] for it in items),
+           lambda: L.check(entry(arr, len(items), _stream()), what),
            " | ".join(it[3] for it in items), nbytes=sum(it[2] for it in items))
 
 
@@ -2192,6 +2195,75 @@ def convlstm_group_step(members) -> bool:
         return False
     _lstm_launch_group(_k(ms[0].x_all), steps)
     return True
+
+
+_TICK_MAX = 4          # members per group launch (GROUP_MAX of csrc/igemm_fwd.hip) and per point-wise group launch
+
+
+def _tick_kind(desc) -> str:
+    """Which launch of convlstm_tick a step descriptor takes -- the library's own answer: "patch" (uclstm_igemm_fwd_group takes
+    it), "tap" (uclstm_igemm_fwd_group_tap does) or "single" (neither: a launch of its own)."""
+    one = (L.IgemmDesc * 1)(desc)
+    if int(L.lib.uclstm_igemm_fwd_group_blocks(one, 1)) > 0:
+        return "patch"
+    if int(L.lib.uclstm_igemm_fwd_group_tap_blocks(one, 1)) > 0:
+        return "tap"
+    return "single"
+
+
+def convlstm_tick(members) -> None:
+    """ONE inference step of n independent single-layer ConvLSTMs with carried state, whatever their sizes: the five recurrences
+    of resnet.PretrainedTemporalUNet, whose step GEMMs run on B*h*w = 1024 ... 4 pixels at 64 x 64.  ``members``: what
+    convlstm_group_step takes, (x_t [B,H,W,Cxp], h_prev, c_prev, h_out, c_out, weight, bias, Hd, Cx); the new state is written
+    into h_out / c_out (h_out must not alias h_prev; c_out may be c_prev).  Every member is launched:
+
+      patch-shape steps     uclstm_igemm_fwd_group, up to four per launch; two or more in a launch take their K ranges from
+                            plan_group_ksplit, as in convlstm_group_step
+      128 x 128 3x3 steps   uclstm_igemm_fwd_group_tap, up to four per launch, each with the K split it has alone
+                            (split_k_factor), so its result is bit-identical to stepping it alone
+      anything else         (a 5x5 cell, a 64 x 256 split-K step) one by one
+
+    and the split members of both group kinds share uclstm_lstm_fwd_pointwise_group launches of up to four.  ``GROUP_LSTM =
+    False``: every member one by one (the A/B baseline).  LAUNCH_LOG gets ("tick", kind, members) per launch, kind = "patch" /
+    "tap" / "single" / "pointwise"."""
+    if not members:
+        return
+    for x_t, h_prev, c_prev, h_out, c_out, *_ in members:
+        if h_prev is None or c_prev is None or h_out is None or c_out is None:
+            raise L.UclstmError("convlstm_tick: every member carries its state (h_prev, c_prev) and names its output buffers")
+        if h_out.data_ptr() == h_prev.data_ptr():
+            raise L.UclstmError("convlstm_tick: h_out aliases h_prev")
+    _same_act_dtype([mem[0] for mem in members], "convlstm_tick")
+    ms = [_LstmLayerFwd(x_t.unsqueeze(0), h_prev, c_prev, weight, bias, Hd, Cx, False, (h_out, c_out))
+          for x_t, h_prev, c_prev, h_out, c_out, weight, bias, Hd, Cx in members]
+    K = _k(ms[0].x_all)
+    buckets = {"patch": [], "tap": [], "single": []}
+    for m in ms:
+        m.split(split_k_factor(m.pixels, m.N, m.Ktot // 64))
+        step = m.step(0)
+        buckets[_tick_kind(step[0][0]) if GROUP_LSTM else "single"].append((m, step))
+
+    def log(kind: str, n: int) -> None:
+        if LAUNCH_LOG is not None:
+            LAUNCH_LOG.append(("tick", kind, n))
+
+    pws = []
+    for kind in ("patch", "tap"):
+        for i in range(0, len(buckets[kind]), _TICK_MAX):
+            chunk = buckets[kind][i:i + _TICK_MAX]
+            if kind == "patch" and len(chunk) > 1:          # K ranges planned for the launch; the point-wise struct is per layer
+                _group_split([m for m, _ in chunk])
+                chunk = [(m, m.step(0)) for m, _ in chunk]
+            igemm_group([step[0] for _, step in chunk], K, tap=kind == "tap")
+            log(kind, len(chunk))
+            pws += [step[1] for _, step in chunk if step[1] is not None]
+    for i in range(0, len(pws), _TICK_MAX):
+        chunk = pws[i:i + _TICK_MAX]
+        L.check(K.uclstm_lstm_fwd_pointwise_group((L.LstmFwdPwArgs * len(chunk))(*chunk), len(chunk), _stream()), "lstm_fwd_pointwise_group")
+        log("pointwise", len(chunk))
+    for _, step in buckets["single"]:
+        _lstm_launch_one(K, *step)
+        log("single", 1)
 
 
 class ConvLSTMSeqPre(torch.autograd.Function):

@@ -13,7 +13,10 @@ Functions below (``EncConv``, ``BnRelu``, ``BnAddRelu``, ``MaxPool3s2``) -- the 
 weight gradients as descriptors of the weight-gradient family over the OUTPUT grid, and the stride-2 input gradient as one launch of
 the forward family over the four parities of the input pixel (``conv_s2_dgrad``).
 
-Not part of this module: ``GraphedTrainStep``, ``StreamingPredictor`` and ``sync_batchnorm`` with this model, and a fused upsample.
+Frame-by-frame inference is ``step_nhwc`` (driven by ``streaming.PretrainedStreamingPredictor``): the five recurrences advance
+layer by layer, each layer of all five as one ``ops.convlstm_tick``.
+
+Not part of this module: ``GraphedTrainStep`` and ``sync_batchnorm`` with this model, and a fused upsample.
 """
 from __future__ import annotations
 
@@ -766,6 +769,76 @@ class PretrainedTemporalUNet(nn.Module):
             if pending:
                 modules._flush_counters(pending)
             ops.join_forward_side(x_seq.device)          # BatchNorm running statistics were updated on the second stream
+
+    # -- streaming: one frame in, one frame out, all five recurrent states carried ------------------
+    STATE_KEYS = ("lstm", "skip1", "skip2", "skip3", "skip4")
+
+    def _recurrences(self):
+        """(state key, ConvLSTM, index of its encoder feature) of the five computed recurrences, ``lstm`` first."""
+        return [("lstm", self.lstm, 4)] + [(f"skip{j}", self.lstm_skips[j], j - 1) for j in (1, 2, 3, 4)]
+
+    def state_spec(self, B: int, H: int, W: int) -> dict:
+        """``{key: (layers, (B, h, w, padded channels))}``: the shapes of the recurrent state ``step_nhwc`` carries."""
+        return {key: (len(lstm.layers), (B, H >> (fi + 1), W >> (fi + 1), cpad(lstm.layers[0].hidden_dim)))
+                for key, lstm, fi in self._recurrences()}
+
+    def step_nhwc(self, x_t: Tensor, full_state: Optional[dict] = None, out_state: Optional[dict] = None):
+        """``x_t`` f32 ``[B, 2, H, W]`` -> ``(y_t f32 [B, out_channels, H, W], new_state)``: one frame of ``forward()``.
+
+        ``full_state`` maps ``'lstm'`` and ``'skip1'`` .. ``'skip4'`` (``lstm_skips[1..4]``; ``lstm_skips[0]`` is never computed)
+        to per-layer lists of ``(h 16-bit NHWC, c f32 NHWC)``; ``None`` is the zero state.  Feeding frames one by one reproduces
+        ``forward()`` on the whole sequence in evaluation mode.  ``out_state`` (same structure): the buffers the new state is
+        written into -- no copies; h buffers must differ from the input state's, c buffers may be the same tensors.
+
+        One step: the encoder on the frame, layer l of all five ConvLSTMs as ONE ``ops.convlstm_tick`` (l = 0, 1, ...), the
+        decoder, the head.  Inference only: it raises in grad mode, and while any BatchNorm is in training mode (a one-frame
+        batch statistic is not what ``forward`` computes, and it would move the running statistics)."""
+        if not isinstance(x_t, torch.Tensor) or not x_t.is_cuda:
+            raise UclstmError("PretrainedTemporalUNet.step_nhwc: a HIP device tensor is required (this package has no CPU path)")
+        if x_t.dim() != 4 or x_t.shape[1] != ENCODER_CHANNELS[0]:
+            raise UclstmError(f"PretrainedTemporalUNet.step_nhwc: expected [B, {ENCODER_CHANNELS[0]}, H, W], got {tuple(x_t.shape)}")
+        B, _, H, W = x_t.shape
+        if H % 32 or W % 32:
+            raise UclstmError(f"PretrainedTemporalUNet.step_nhwc: H and W must be multiples of 32 (five stride-2 stages), got {H} x {W}")
+        if torch.is_grad_enabled():
+            raise UclstmError("PretrainedTemporalUNet.step_nhwc is inference only: call it under torch.no_grad()")
+        if any(isinstance(m, nn.BatchNorm2d) and _bn_mode(m)[0] for m in self.modules()):
+            raise UclstmError("PretrainedTemporalUNet.step_nhwc: a BatchNorm is in training mode (batch statistics of one frame are "
+                              "not what forward() computes): call model.eval() first")
+        adt, dev = ops.get_compute_dtype(), x_t.device
+        spec = self.state_spec(B, H, W)
+        st = {} if full_state is None else full_state
+        ost = {} if out_state is None else out_state
+        cur, new_state = {}, {}
+        for key, (n_layers, shape) in spec.items():
+            cur[key] = st.get(key) or [(torch.zeros(shape, dtype=adt, device=dev), torch.zeros(shape, dtype=F32, device=dev))
+                                       for _ in range(n_layers)]
+            new_state[key] = ost.get(key) or [(torch.empty(shape, dtype=adt, device=dev), torch.empty(shape, dtype=F32, device=dev))
+                                              for _ in range(n_layers)]
+            if len(cur[key]) != n_layers or len(new_state[key]) != n_layers:
+                raise UclstmError(f"PretrainedTemporalUNet.step_nhwc: state {key!r} must hold one (h, c) per layer ({n_layers})")
+        pending: list = []
+        feats = self._encode(x_t.contiguous().float().unsqueeze(1), pending)
+        recs = self._recurrences()
+        xs = {key: feats[fi] for key, _, fi in recs}
+        for li in range(len(self.lstm.layers)):
+            members = []
+            for key, lstm, _ in recs:
+                cell = lstm.layers[li]
+                (h_prev, c_prev), (h_out, c_out) = cur[key][li], new_state[key][li]
+                members.append((xs[key], h_prev, c_prev, h_out, c_out, cell.conv.weight, cell.conv.bias, cell.hidden_dim, cell.input_dim))
+                xs[key] = h_out
+            ops.convlstm_tick(members)
+        x = xs["lstm"]
+        skips = [xs[f"skip{j}"] for j in (4, 3, 2, 1)] + [None]
+        for blk, skip in zip(self.decoder.blocks, skips):
+            cin, cskip, cout = blk.channels
+            up = Upsample2.apply(x)
+            x = self._stage(blk.conv1, up, skip, (cin, cskip) if skip is not None else (cin,), pending)
+            x = self._stage(blk.conv2, x, None, (cout,), pending)
+        ops.join_forward_side(dev)
+        conv = self.head[0]
+        return Head3x3.apply(x, conv.weight, conv.bias), new_state
 
     def _forward(self, x_seq: Tensor, pending: list) -> Tensor:
         B, T, _, H, W = x_seq.shape
