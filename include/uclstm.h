@@ -124,8 +124,11 @@ int32_t uclstm_igemm_fwd(const uclstm_igemm_desc* d, void* stream);
 /* Which kernel uclstm_igemm_fwd would run for this descriptor (same validation, nothing is launched): 0 = per-tap loop,
  * 128 x 128 tile; 1 = per-tap loop, 64 rows x 256 pixels (C_out <= 64); 2 = patch loop, 128 rows x 256 pixels (3x3 / pad 1 /
  * stride 1, every source on the output grid with C % 64 == 0, >= 2 channel chunks, 256 | pixels per group, patch <= 448
- * rows); 3 = the 64 -> 64-channel ring kernel.  Negative: UCLSTM_E_*.  Tests use it to assert that a parity case really
- * exercised the kernel it is meant for. */
+ * rows); 3 = the 64 -> 64-channel ring kernel; 4 = the flat kernel, persistent 128 rows x 256 pixels with a three-stage ring
+ * over all its tiles (UCLSTM_EPI_STORE, one source with C % 64 == 0 or C < 64 and zero offsets, pad 0, Ktot <= 512, 256 | pixels per group,
+ * and either ktap 1 / scale 1 / source on the output grid or ktap 2 / scale 2 / source twice the output grid: ConvTranspose2d
+ * forward and input gradient, the pre-gathered first layer; its statistics rows are those of shapes 0 / 1 for the same N).  Negative: UCLSTM_E_*.  Tests use it to assert that a parity case really exercised the kernel it
+ * is meant for. */
 int32_t uclstm_igemm_fwd_shape(const uclstm_igemm_desc* desc);
 /* Number of non-empty K ranges uclstm_igemm_fwd will use for (Ktot, kernel width, requested ksplit): the slab count of acc_slab
  * mode.  K ranges are whole (source, 64-channel) chunks of ktap*ktap K-steps: steps per range = ktap^2 * ceil(chunks / ksplit). */

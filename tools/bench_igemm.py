@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Per-shape timing of the MFMA kernels at the benchmark configuration (developer tool, GPU only).
 
-    python tools/bench_igemm.py [--iters 5] [--only fwd|lstm|wgrad]
+    python tools/bench_igemm.py [--iters 5] [--only fwd|lstm|wgrad|flat]
 
 Shapes are the convolutions of TemporalUNetDualView(base_ch=64, skip LSTMs) at 64x64 with T*B = 640 images
-(main.py:215-228).  Prints ms and algorithmic TFLOP/s per launch.
+(main.py:215-228).  Prints ms and algorithmic TFLOP/s per launch.  `--only flat` (not part of the default run) times the nine
+plain-gather launches of the step -- the four ConvTranspose2d forwards (ktap 1, four scattered segments), their input gradients
+(ktap 2 / scale 2) and the pre-gathered first layer (24 gathered channels in a K of 64, N = 64, statistics, 20 groups) -- and adds the algorithmic GB/s (every
+operand counted once).
 """
 import argparse
 import os
@@ -29,6 +32,29 @@ CONVS = [  # name, H, C0, C1, Co
     ("up1.c0", 32, 128, 128, 128), ("up0.c0", 64, 64, 64, 64),
 ]
 LSTMS = [("temporal", 4, 1024), ("skip3", 8, 512), ("skip2", 16, 256)]
+CONVTS = [("up0", 32, 128, 64), ("up1", 16, 256, 128), ("up2", 8, 512, 256), ("up3", 4, 1024, 512)]   # name, input H, Ci, Co
+
+
+def flat_launches():
+    """(name, M, N, K, gathered values per pixel, launch) of the nine plain-gather launches; panels are random (their layout does not
+    matter to the clock)."""
+    for name, h, Ci, Co in CONVTS:
+        x, wp = rnd(NIMG, h, h, Ci), rnd(4 * Co, Ci)
+        u = torch.empty(NIMG, 2 * h, 2 * h, Co, dtype=torch.bfloat16, device=DEV)
+        segs = [(u, t * Co, (t + 1) * Co, 0, 2, t // 2, t % 2) for t in range(4)]
+        yield (name + ".fwd", NIMG * h * h, 4 * Co, Ci, Ci,
+               lambda x=x, wp=wp, segs=segs, h=h: ops.igemm_store([ops.SrcView(x)], wp, (h, h), NIMG, segs, ktap=1, pad=0))
+    for name, h, Ci, Co in CONVTS:
+        du, wd = rnd(NIMG, 2 * h, 2 * h, Co), rnd(Ci, 4 * Co)
+        dx = torch.empty(NIMG, h, h, Ci, dtype=torch.bfloat16, device=DEV)
+        yield (name + ".dgrad", NIMG * h * h, Ci, 4 * Co, 4 * Co,
+               lambda du=du, wd=wd, dx=dx, h=h, Ci=Ci: ops.igemm_store([ops.SrcView(du)], wd, (h, h), NIMG, [(dx, 0, Ci, 0, 1, 0, 0)], ktap=2,
+                                                                     scale=2, pad=0))
+    x, wp = rnd(NIMG, 64, 64, 24), rnd(64, 64)      # 9 taps x 2 channels, padded to 24; the panel's K is 64
+    out = torch.empty(NIMG, 64, 64, 64, dtype=torch.bfloat16, device=DEV)
+    stats = torch.empty(20, U._lib.lib.uclstm_igemm_tiles_per_group(NIMG, 64, 64, 20, 64), 64, 2, device=DEV)
+    yield ("inc.0", NIMG * 64 * 64, 64, 64, 24,
+           lambda: ops.igemm_store([ops.SrcView(x)], wp, (64, 64), NIMG, [(out, 0, 64, 0, 1, 0, 0)], ktap=1, pad=0, groups=20, stats=stats))
 
 
 def timeit(fn, iters):
@@ -58,6 +84,15 @@ def main():
         CONVS = [c for c in CONVS if c[0] == a.shape]
         LSTMS = [l for l in LSTMS if l[0] == a.shape]
     tot_ms = tot_fl = 0.0
+    if a.only == "flat":
+        for name, M, N, K, Kin, fn in flat_launches():
+            if a.shape and name != a.shape:
+                continue
+            ms = timeit(fn, a.iters)
+            fl, by = 2.0 * M * N * K, 2.0 * (M * Kin + N * K + M * N)
+            tot_ms += ms
+            tot_fl += fl
+            print(f"flat  {name:10s} M={M:8d} N={N:5d} K={K:6d}  {ms:8.4f} ms  {fl / ms / 1e9:8.1f} TFLOP/s  {by / ms / 1e6:8.1f} GB/s", flush=True)
     if a.only in ("", "fwd"):
         for name, H, C0, C1, Co in CONVS:
             Ci = C0 + C1

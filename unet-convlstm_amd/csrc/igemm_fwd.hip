@@ -1079,6 +1079,358 @@ __global__ __launch_bounds__(256, 1) void igemm_fwd_c64_kernel(const uclstm_igem
 
 #undef C64_ISSUE_NEXT_ROW
 
+// ------------------------------------------------------------------------------------------------------------------
+// "Flat" GEMMs: STORE descriptors whose A operand is a plain row gather -- ktap 1 (ConvTranspose2d forward: every pixel times
+// a [4*Co][C] panel, scattered by the segments) and ktap 2 / scale 2 (its input gradient: the four taps of source pixel
+// (2y, 2x)).  No halo, no border, one source, C % 64 == 0 or C < 64.  K is short (2 .. 32 steps), so a block of the per-tap loop
+// spends most of its life in the load latency and the epilogue with nothing in flight.  Here:
+//   * persistent blocks, one per CU, 8 waves (2 x 4, each a 64 x 64 sub-tile: the arithmetic and the K order -- 64-channel
+//     chunk major, tap minor, two 32-deep halves, a outer / b inner -- are the per-tap loop's, so results are bit-identical);
+//     tile = 128 panel rows x 256 pixels; a block keeps ONE panel-row tile for all its pixel tiles, so the epilogue constants
+//     are loaded once, before the first DMA (an ordinary load used inside the loop would make the compiler drain vmcnt);
+//   * the K-steps of all the block's tiles form ONE sequence g = 0, 1, ... through a ring of three 48-KiB stages (256 pixel
+//     rows + 128 panel rows of 128 B); step g: `s_waitcnt vmcnt(6)` (a wave issues 6 DMA pieces per stage: stage g landed,
+//     g+1 may be in flight) -> raw `s_barrier` -> issue stage g+2 -> fragments + MFMAs of stage g.  The cursor of the loads runs
+//     across tile boundaries: while a tile's epilogue stores, the first two stages of the next tile are in flight.
+//     RAW: a wave reads slot g%3 only after its own vmcnt wait AND the barrier every issuing wave reached after ITS wait.
+//     WAR: stage g+2 goes to slot (g-1)%3, whose last reads (step g-1) every wave retired -- they fed its MFMAs -- before it
+//     arrived at barrier g.
+//   * past the last real step the cursor issues out-of-range pieces (zeros into a free slot), so the counted wait means
+//     the same thing on every step;
+//   * epilogue straight from registers (v_permlane16_swap -> 16-byte stores, as the ring kernel), no LDS staging: the ring
+//     slots belong to the prefetch.  Stores sit on the same counter as the DMA pieces and retire in order with them, so a
+//     counted wait issued while stores are outstanding would wait for the stores too: before the epilogue a wave waits for
+//     stage g+1 (issued two steps earlier), and the first step of the next tile then needs no wait of its own; by the second
+//     step the stores are a whole K-step old.
+//   * BatchNorm partial sums of the rounded values: N > 64: registers -> DPP row sums -> 4 KiB of LDS behind the ring -> the two
+//     128-pixel statistics rows the tile covers (the layout uclstm_igemm_tiles_per_group promises for N > 64; equal to the
+//     per-tap loop's up to the f32 summation order, as the patch loop's); N <= 64: the tile's one 256-pixel row, summed in
+//     the per-tap shape's own order from a staging of the rounded tile in the ring slot the last K-step freed (bit-identical).
+constexpr int FLAT_XBYTES = 256 * 128;
+constexpr int FLAT_WBYTES = 128 * 128;
+constexpr int FLAT_STAGE = FLAT_XBYTES + FLAT_WBYTES;          // 49152
+constexpr int FLAT_SLOTS = 3;
+constexpr int FLAT_RED = FLAT_SLOTS * FLAT_STAGE;               // 147456: [4 pixel waves][128 rows][2] floats
+constexpr int FLAT_SMEM = FLAT_RED + 4 * 128 * 2 * 4;           // 151552
+constexpr int FLAT_OT_PITCH = 64 * 2 + 16;                      // the 64 x 256 per-tap shape's staging pitch
+constexpr int FLAT_PIECES = 6;                                  // DMA instructions a wave issues per stage (4 pixel + 2 panel rounds)
+
+struct FlatPlan {
+    int n_mtiles, n_ntiles;      // 256-pixel tiles, 128-row panel tiles
+    int mstride;                 // blocks per panel-row tile: block (mi, nt) runs pixel tiles mi, mi + mstride, ...
+    int chunks;                  // C / 64
+    int taps;                    // 1 or 4
+    uint32_t xbytes, wbytes;
+    FastDiv dHW, dW;
+};
+
+__global__ __launch_bounds__(512, 1) void igemm_fwd_flat_kernel(const uclstm_igemm_desc d, const FlatPlan p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    typedef __attribute__((address_space(3))) void* lds_ptr;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wc = wave >> 2;                          // wave position along panel rows
+    const int wpx = wave & 3;                          // wave position along pixels
+    const int l15 = lane & 15;
+    const int lq = lane >> 4;
+
+    const int lid = xcd_remap((int)blockIdx.x, (int)gridDim.x);      // the blocks of one pixel tile share an XCD's L2
+    const int mi = lid / p.n_ntiles;
+    const int nt = lid - mi * p.n_ntiles;
+    const int n0 = nt * 128;
+    const int HW = d.H * d.W;
+    const int C = d.src[0].C, Hs = d.src[0].Hs, Ws = d.src[0].Ws;
+    const int ksteps = p.chunks * p.taps;
+
+    // epilogue constants of this lane's panel rows n0 + wc*64 + a*16 + lq*4 .. +3: loaded and waited for before any DMA
+    float bs[4][4], scl[4][4], sft[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const int n = n0 + wc * 64 + a * 16 + lq * 4;
+        const bool in = n < d.N;
+        const float4 t0 = (in && d.bias) ? *(const float4*)(d.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 t1 = (in && d.col_scale) ? *(const float4*)(d.col_scale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
+        const float4 t2 = (in && d.col_shift) ? *(const float4*)(d.col_shift + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+        bs[a][0] = t0.x; bs[a][1] = t0.y; bs[a][2] = t0.z; bs[a][3] = t0.w;
+        scl[a][0] = t1.x; scl[a][1] = t1.y; scl[a][2] = t1.z; scl[a][3] = t1.w;
+        sft[a][0] = t2.x; sft[a][1] = t2.y; sft[a][2] = t2.z; sft[a][3] = t2.w;
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(bs[a][r]), "+v"(scl[a][r]), "+v"(sft[a][r]));      // values are in registers HERE
+    // this lane's two 8-channel output runs (after the quad swap below): panel row, segment, and the run's offset in a pixel
+    const int nst0 = (lq & 1) ? 16 + (lq - 1) * 4 : lq * 4;
+    int o_scale[2], o_oy[2], o_ox[2], o_Hd[2], o_Wd[2], o_C[2], o_coff[2];
+    typedef __attribute__((address_space(1))) unsigned char gbyte;      // GLOBAL: a generic store may hit LDS, and the compiler would drain the DMA first
+    gbyte* o_ptr[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int n = n0 + wc * 64 + h * 32 + nst0;
+        o_ptr[h] = nullptr;
+        o_scale[h] = o_oy[h] = o_ox[h] = o_Hd[h] = o_Wd[h] = o_C[h] = o_coff[h] = 0;
+#pragma unroll
+        for (int si = 0; si < 4; ++si) {
+            if (si < d.nseg && n < d.N && n >= d.seg[si].n_begin && n < d.seg[si].n_end) {
+                const uclstm_seg sg = d.seg[si];
+                o_ptr[h] = (gbyte*)sg.ptr;
+                o_scale[h] = sg.scale; o_oy[h] = sg.oy; o_ox[h] = sg.ox; o_Hd[h] = sg.Hd; o_Wd[h] = sg.Wd; o_C[h] = sg.C;
+                o_coff[h] = sg.c_off + (n - sg.n_begin);
+            }
+        }
+    }
+
+    const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)d.src[0].ptr, 0, p.xbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)d.wp, 0, p.wbytes, 0x00020000);
+    // staging geometry of the per-tap loop: DMA round i of wave w fills rows 64*i + 8*w + (lane>>3); linear destination,
+    // XOR-swizzled source chunk
+    const int lrow0 = tid >> 3;
+    const int lchunk = (tid & 7) ^ (lrow0 & 7);
+    const int wrow_lds = wave * 8 * 128;
+    uint32_t wvoff[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int nrow = n0 + lrow0 + 64 * i;
+        wvoff[i] = nrow < d.N ? (uint32_t)(2 * (nrow * d.Ktot + lchunk * 8)) : OOB;
+    }
+
+    // cursor of the NEXT stage to load: pixel tile lmt (row offsets roff of its 4 rounds), chunk lch, tap ltap
+    int lmt = mi, lch = 0, ltap = 0;
+    uint32_t roff[4];
+#define FLAT_ROWS()                                                                                                       \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                                    \
+        const uint32_t m_ = (uint32_t)lmt * 256u + (uint32_t)(lrow0 + 64 * i_);                                           \
+        uint32_t pixel_ = m_;                                                                                             \
+        if (p.taps == 4) {                                                                                                \
+            const uint32_t img_ = fdiv(m_, p.dHW);                                                                        \
+            const uint32_t rem_ = m_ - img_ * (uint32_t)HW;                                                               \
+            const uint32_t y_ = fdiv(rem_, p.dW);                                                                         \
+            const uint32_t x_ = rem_ - y_ * (uint32_t)d.W;                                                                \
+            pixel_ = (img_ * (uint32_t)Hs + 2u * y_) * (uint32_t)Ws + 2u * x_;                                            \
+        }                                                                                                                 \
+        roff[i_] = (lmt < p.n_mtiles && lchunk * 8 < C) ? pixel_ * (uint32_t)(2 * C) + (uint32_t)(lchunk * 16) : OOB;     \
+    }
+#define FLAT_ISSUE(slot_)                                                                                                 \
+    {                                                                                                                     \
+        unsigned char* X_ = smem + (slot_) * FLAT_STAGE;                                                                  \
+        const int tdy_ = ltap >> 1;                                                                                       \
+        const uint32_t tapoff_ = (uint32_t)(2 * ((tdy_ * Ws + (ltap & 1)) * C + lch * BK));                               \
+        const uint32_t koff_ = (uint32_t)(ltap * p.chunks + lch) * (BK * 2);                                              \
+        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                                  \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsx, (lds_ptr)(X_ + i_ * 64 * 128 + wrow_lds), 16, roff[i_], tapoff_, 0, 0); \
+        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_)                                                                  \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr)(X_ + FLAT_XBYTES + i_ * 64 * 128 + wrow_lds), 16,     \
+                                                     lmt < p.n_mtiles ? wvoff[i_] : OOB, koff_, 0, 0);                    \
+        if (++ltap == p.taps) {                                                                                           \
+            ltap = 0;                                                                                                     \
+            if (++lch == p.chunks) {                                                                                      \
+                lch = 0;                                                                                                  \
+                if (lmt < p.n_mtiles) lmt += p.mstride;                                                                   \
+                FLAT_ROWS()                                                                                               \
+            }                                                                                                             \
+        }                                                                                                                 \
+    }
+    FLAT_ROWS()
+    FLAT_ISSUE(0)
+    FLAT_ISSUE(1)
+
+    const int choff0 = ((0 * 4 + lq) ^ (l15 & 7)) << 4;
+    const int choff1 = ((1 * 4 + lq) ^ (l15 & 7)) << 4;
+    float* Red = (float*)(smem + FLAT_RED);
+    const bool active = n0 + wc * 64 < d.N;
+    int slot = 0;
+    bool first = true;
+    for (int mt = mi; mt < p.n_mtiles; mt += p.mstride) {
+        f32x4 acc[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < ksteps; ++j) {
+            // stage g has landed; the 6 youngest pieces (stage g+1) may be in flight.  Step 0 of every tile but the first
+            // was waited for before the previous epilogue.
+            if (j > 0 || first) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            // every wave is past its reads of step g-1: that slot takes stage g+2
+            int s2 = slot + 2;
+            s2 = s2 >= FLAT_SLOTS ? s2 - FLAT_SLOTS : s2;
+            FLAT_ISSUE(s2)
+            if (active) {      // wave-uniform: a wave whose 64 panel rows all lie beyond N only stages and keeps the barriers
+                const unsigned char* X = smem + slot * FLAT_STAGE;
+                const unsigned char* Wt = X + FLAT_XBYTES;
+                act16x8 wf[4], xf[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) wf[a] = *(const act16x8*)(Wt + (wc * 64 + a * 16 + l15) * 128 + choff0);
+#pragma unroll
+                for (int b = 0; b < 4; ++b) xf[b] = *(const act16x8*)(X + (wpx * 64 + b * 16 + l15) * 128 + choff0);
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) acc[a][b] = UCLSTM_MFMA_16x16x32(wf[a], xf[b], acc[a][b], 0, 0, 0);
+#pragma unroll
+                for (int a = 0; a < 4; ++a) wf[a] = *(const act16x8*)(Wt + (wc * 64 + a * 16 + l15) * 128 + choff1);
+#pragma unroll
+                for (int b = 0; b < 4; ++b) xf[b] = *(const act16x8*)(X + (wpx * 64 + b * 16 + l15) * 128 + choff1);
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) acc[a][b] = UCLSTM_MFMA_16x16x32(wf[a], xf[b], acc[a][b], 0, 0, 0);
+            }
+            slot = slot + 1 >= FLAT_SLOTS ? 0 : slot + 1;
+        }
+        first = false;
+        // the next tile's first stage (or the zero filler) has landed: see the header comment on stores and counted waits
+        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+
+        // ---- epilogue from registers: lane = (pixel wpx*64 + b*16 + l15, panel rows wc*64 + a*16 + lq*4 .. +3) ----
+        // Nothing else runs on the CU during an epilogue, so its VALU count is tile time: one pair of row tiles at a time
+        // (convert, statistics, store: few live registers), ReLU by a block-uniform branch, 32-bit addresses up to the pixel.
+        // N <= 64: the statistics must come out in the 64 x 256 per-tap shape's own summation order (the step's BatchNorm reads
+        // them, and a different f32 order would change what the step computes): the rounded tile is staged as that shape stages
+        // it, in the ring slot of the stage just consumed -- free until the next K-step's barrier -- and summed exactly as there.
+        const bool stage_stats = d.stats && d.N <= 64;      // block-uniform
+        unsigned char* const Ot = smem + (slot == 0 ? FLAT_SLOTS - 1 : slot - 1) * FLAT_STAGE;      // [256 pixels][FLAT_OT_PITCH]
+        if (stage_stats) {      // every wave is past its fragment reads of that slot
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+        if (active) {
+            uint32_t dpix[4][2];      // destination pixel of (b, h), or ~0: outside its segment's image / no segment
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const uint32_t m = (uint32_t)mt * 256u + (uint32_t)(wpx * 64 + b * 16 + l15);
+                const int img = (int)fdiv(m, p.dHW);
+                const uint32_t rem = m - (uint32_t)img * (uint32_t)HW;
+                const int y = (int)fdiv(rem, p.dW);
+                const int x = (int)rem - y * d.W;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int yd = y * o_scale[h] + o_oy[h];
+                    const int xd = x * o_scale[h] + o_ox[h];
+                    const bool ok = o_ptr[h] && (unsigned)yd < (unsigned)o_Hd[h] && (unsigned)xd < (unsigned)o_Wd[h];
+                    dpix[b][h] = ok ? (uint32_t)((img * o_Hd[h] + yd) * o_Wd[h] + xd) : 0xffffffffu;      // < 2^31 (flat_ok)
+                }
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                Pack8 ov[2][4];
+#define FLAT_CONVERT(RELU_)                                                                                               \
+                _Pragma("unroll") for (int a2 = 0; a2 < 2; ++a2)                                                          \
+                    _Pragma("unroll") for (int b = 0; b < 4; ++b)                                                         \
+                        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                   \
+                            const int a = 2 * h + a2;                                                                     \
+                            float v = (acc[a][b][r] + bs[a][r]) * scl[a][r] + sft[a][r];                                  \
+                            if (RELU_) v = fmaxf(v, 0.f);                                                                 \
+                            ov[a2][b].e[r] = f32_to_act(v);                                                               \
+                        }
+                if (d.relu) { FLAT_CONVERT(true) } else { FLAT_CONVERT(false) }
+#undef FLAT_CONVERT
+                if (stage_stats) {
+#pragma unroll
+                    for (int a2 = 0; a2 < 2; ++a2)
+#pragma unroll
+                        for (int b = 0; b < 4; ++b)
+                            *(uint2*)(Ot + (wpx * 64 + b * 16 + l15) * FLAT_OT_PITCH + ((2 * h + a2) * 16 + lq * 4) * 2) = ov[a2][b].u;
+                } else if (d.stats) {      // of the ROUNDED values (what BatchNorm will read)
+#pragma unroll
+                    for (int a2 = 0; a2 < 2; ++a2)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+                            for (int b = 0; b < 4; ++b) {
+                                const float q = act_to_f32(ov[a2][b].e[r]);
+                                s1 += q;
+                                s2 += q * q;
+                            }
+                            const float t1 = row16_sum(s1), t2 = row16_sum(s2);
+                            if (l15 == 0) {
+                                const int col = wc * 64 + (2 * h + a2) * 16 + lq * 4 + r;
+                                Red[(wpx * 128 + col) * 2] = t1;
+                                Red[(wpx * 128 + col) * 2 + 1] = t2;
+                            }
+                        }
+                }
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    // v_permlane16_swap: the even 16-lane row ends up with 8 consecutive rows of tile 2h, the odd one of 2h+1
+                    const auto p0 = __builtin_amdgcn_permlane16_swap(ov[0][b].u.x, ov[1][b].u.x, false, false);
+                    const auto p1 = __builtin_amdgcn_permlane16_swap(ov[0][b].u.y, ov[1][b].u.y, false, false);
+                    if (dpix[b][h] != 0xffffffffu)
+                        *(__attribute__((address_space(1))) uint4*)(o_ptr[h] + ((uint64_t)dpix[b][h] * (uint32_t)o_C[h] + (uint32_t)o_coff[h]) * 2) =
+                            make_uint4(p0[0], p1[0], p0[1], p1[1]);
+                }
+            }
+        }
+        if (d.stats) {      // block-uniform
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            if (d.N > 64) {      // two rows of 128 pixels (pixel waves 0-1, 2-3): the layout of every shape with N > 64
+                if (tid < 256) {
+                    const int half = tid >> 7, col = tid & 127;
+                    const int n = n0 + col;
+                    if (n < d.N) {
+                        float* sp = d.stats + ((long)(mt * 2 + half) * d.N + n) * 2;
+                        sp[0] = Red[((2 * half) * 128 + col) * 2] + Red[((2 * half + 1) * 128 + col) * 2];
+                        sp[1] = Red[((2 * half) * 128 + col) * 2 + 1] + Red[((2 * half + 1) * 128 + col) * 2 + 1];
+                    }
+                }
+            } else {      // one row of 256 pixels: eight interleaved partial sums per column and their tree, as the per-tap epilogue
+                const int col = tid >> 3, j = tid & 7;
+                float s1 = 0.f, s2 = 0.f;
+                if (col < d.N) {
+                    for (int r = j; r < 256; r += 8) {
+                        const float v = act_to_f32(*(const act16*)(Ot + r * FLAT_OT_PITCH + col * 2));
+                        s1 += v;
+                        s2 += v * v;
+                    }
+                }
+                // ((p0 + p4) + (p1 + p5)) + ((p2 + p6) + (p3 + p7)) in every lane of the column's eight
+                s1 += __shfl_xor(s1, 4); s2 += __shfl_xor(s2, 4);
+                s1 += __shfl_xor(s1, 1); s2 += __shfl_xor(s2, 1);
+                s1 += __shfl_xor(s1, 2); s2 += __shfl_xor(s2, 2);
+                if (col < d.N && j == 0) {
+                    float* sp = d.stats + ((long)mt * d.N + col) * 2;
+                    sp[0] = s1;
+                    sp[1] = s2;
+                }
+            }
+            // (Red is rewritten after the next tile's K-step barriers, which every wave reaches with these reads retired)
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the filler stages
+#undef FLAT_ISSUE
+#undef FLAT_ROWS
+#endif
+}
+
+// The launch conditions of igemm_fwd_flat_kernel (everything else stays where it was).  N <= 64 (the pre-gathered first layer) runs
+// with the block's second row of waves idle: it is a streaming launch, and the statistics row is then the 256-pixel tile.
+inline bool flat_ok(const uclstm_igemm_desc& d, int64_t mg) {
+    static const bool off = [] { const char* e = getenv("UCLSTM_FWD_FLAT"); return e && e[0] == '0'; }();
+    if (off || d.epi != UCLSTM_EPI_STORE || d.nsrc != 1 || d.pad != 0 || (mg % 256)) return false;
+    for (int i = 0; i < d.nseg && i < 4; ++i)      // the epilogue indexes destination pixels with 32 bits
+        if ((int64_t)d.n_img * d.seg[i].Hd * d.seg[i].Wd >= ((int64_t)1 << 31)) return false;
+    const uclstm_src& S = d.src[0];
+    // C % 64 == 0, or ONE chunk narrower than 64 channels (the pre-gathered first layer: 24 of 64 K columns; a lane whose 8
+    // channels lie beyond C stages zeros, as in the per-tap loop)
+    if (((S.C % 64) && S.C > 64) || S.offY || S.offX) return false;
+    if (d.ktap == 1) {
+        if (d.scale != 1 || S.Hs != d.H || S.Ws != d.W) return false;
+    } else if (d.ktap == 2) {
+        if (d.scale != 2 || S.Hs != 2 * d.H || S.Ws != 2 * d.W) return false;
+    } else {
+        return false;
+    }
+    // What the kernel removes is per-TILE overhead (load latency, staged epilogue, nothing in flight between tiles); from 16
+    // K-steps per tile on the per-tap loop's main loop carries the launch and the two measured level (profiles/flat_gemm_notes.md:
+    // K = 1024 and 2048 within the parent's spread or behind it, K <= 512 ahead by 12 - 42 %).
+    if (d.Ktot > 512) return false;
+    return (d.N + 127) / 128 <= 256;
+}
+
 // The launch conditions of igemm_fwd_c64_kernel (everything else takes the generic kernel).
 inline bool c64_ok(const uclstm_igemm_desc& d) {
     static const bool off = [] { const char* e = getenv("UCLSTM_FWD_C64"); return e && e[0] == '0'; }();
@@ -1105,7 +1457,7 @@ inline int pick_shape(int N, int64_t /*mg*/, int /*groups*/, int epi) {
     if (epi == UCLSTM_EPI_LSTM) return 0;
     return N <= 64 ? 1 : 0;
 }
-inline int shape_pixels(int shp) { return shp == 0 ? 128 : 256; }
+inline int shape_pixels(int shp) { return shp == 0 ? 128 : 256; }      // (4, the flat kernel: 128 x 256 like the patch shape)
 inline int shape_rows(int shp) { return shp == 1 ? 64 : 128; }
 
 // Rows a 256-pixel tile's patch can span in the shared-zero padded index space (see the patch K loop): 255 steps between
@@ -1221,6 +1573,7 @@ static int32_t plan_fwd(const uclstm_igemm_desc& d, Derived& dv, int& shp, int64
     int patch = patch_ok(d, mg);
     if (d.epi == UCLSTM_EPI_ATOMIC && d.ksplit < 1) return UCLSTM_E_BADARG;      // (K ranges are whole chunks: ksplit_kper)
     if (patch) shp = 2;
+    else if (flat_ok(d, mg)) shp = 4;
     dv.strip = patch == 2;
     dv.strips = d.W / 64;
     dv.tiles_per_img = (d.H / 4) * (d.W / 64);
@@ -1296,6 +1649,26 @@ extern "C" int32_t uclstm_igemm_fwd(const uclstm_igemm_desc* dp, void* stream) {
         const int grid = (tiles_total + per - 1) / per;
         UCLSTM_LAUNCH(igemm_fwd_c64_kernel, dim3(grid), dim3(256), C64_SMEM, st, d, tiles_total, per,
                       (uint32_t)((int64_t)d.n_img * d.H * d.W * 64 * 2), dv.tpg);
+        return UCLSTM_OK;
+    }
+    if (shp == 4) {
+        static bool attr_flat = false;
+        if (!attr_flat) {
+            (void)hipFuncSetAttribute((const void*)igemm_fwd_flat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FLAT_SMEM);
+            attr_flat = true;
+        }
+        FlatPlan p;
+        p.n_mtiles = dv.n_mtiles;
+        p.n_ntiles = dv.n_ntiles;
+        const int per_nt = 256 / p.n_ntiles > 0 ? 256 / p.n_ntiles : 1;      // one block per CU, every block one panel-row tile
+        p.mstride = p.n_mtiles < per_nt ? p.n_mtiles : per_nt;
+        p.chunks = dv.kseg0 / BK;
+        p.taps = d.ktap * d.ktap;
+        p.xbytes = dv.xbytes[0] - dv.xbias[0];
+        p.wbytes = dv.wbytes;
+        p.dHW = dv.dHW;
+        p.dW = dv.dW;
+        UCLSTM_LAUNCH(igemm_fwd_flat_kernel, dim3((unsigned)(p.mstride * p.n_ntiles)), dim3(512), FLAT_SMEM, st, d, p);
         return UCLSTM_OK;
     }
     if (d.epi == UCLSTM_EPI_LSTM) return shp == 2 ? launch<UCLSTM_EPI_LSTM, 2>(d, dv, nblk, st) : launch<UCLSTM_EPI_LSTM, 0>(d, dv, nblk, st);

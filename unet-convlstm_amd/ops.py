@@ -213,7 +213,7 @@ PROFILE: Optional[list] = None
 
 
 # Optional record of which forward-family kernel each launch takes (uclstm_igemm_fwd_shape: 0 / 1 per-tap shapes, 2 patch loop,
-# 3 ring kernel): tests set it to a list to assert that a parity case exercised the kernel it is meant for.
+# 3 ring kernel, 4 flat kernel): tests set it to a list to assert that a parity case exercised the kernel it is meant for.
 SHAPE_LOG: Optional[list] = None
 # Same, as (epilogue, shape) pairs -- epilogue 0 store, 1 fused ConvLSTM cell, 2 split-K partial tiles: the BASELINE-shape
 # parity tests assert that the fused-cell, split-K and patch kernels the benchmark runs were the ones compared.
@@ -271,7 +271,7 @@ def _timed_hbm(kind: str, nbytes: float, launch) -> None:
     PROFILE_HBM.append((kind, nbytes, e0, e1, ""))
 
 
-_SHAPE_NAMES = {0: "pertap128x128", 1: "pertap64x256", 2: "patch128x256", 3: "ring64"}
+_SHAPE_NAMES = {0: "pertap128x128", 1: "pertap64x256", 2: "patch128x256", 3: "ring64", 4: "flat128x256"}
 
 
 def _kernel_kind(kind: str, d) -> str:
