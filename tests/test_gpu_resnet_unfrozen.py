@@ -299,7 +299,7 @@ def test_one_basic_block_against_f64(block):
     m.unfreeze_encoder(name).train()
     blk = getattr(m.encoder, name)[idx]
     xd = RC.nhwc(x).to(torch.bfloat16).to(DEV).requires_grad_(True)
-    a = m._t_block(xd, blk, [])
+    a = m._block(xd, blk, [], True)
     (a.float() * RC.nhwc(gout).to(DEV)).sum().backward()
     ops.join_forward_side(xd.device)
     torch.cuda.synchronize()
@@ -326,7 +326,7 @@ def test_stem_pool_and_first_layer_against_f64():
     m.load_state_dict(sd, strict=True)
     m.unfreeze_encoder(("stem", "layer1")).train()
     pending = []
-    feats = m._encode_trainable(x.to(DEV), pending, 0)
+    feats = m._encode(x.to(DEV), pending, 0)
     (feats[0].float() * RC.nhwc(g1).to(DEV)).sum().add((feats[1].float() * RC.nhwc(g2).to(DEV)).sum()).backward()
     ops.join_forward_side(torch.device(DEV))
     torch.cuda.synchronize()

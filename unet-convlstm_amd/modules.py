@@ -125,6 +125,20 @@ def _flush_counters(pending: list) -> None:
             torch._foreach_add_(ts, inc)
 
 
+def bn_mode(bn: nn.BatchNorm2d, training: bool):
+    """(uses batch statistics, momentum argument of the BatchNorm kernels) of ``bn`` in a module whose training flag is ``training``."""
+    training = training or not bn.track_running_stats
+    if bn.momentum is not None:
+        mom = bn.momentum
+    elif training and bn.num_batches_tracked is not None:
+        # momentum=None is PyTorch's cumulative moving average (factor 1/num_batches_tracked after the bump); the counter
+        # lives on the device, so this rare mode (no reference script uses it) costs one host read per stage
+        mom = -float(int(bn.num_batches_tracked) + 1)
+    else:
+        mom = 0.0
+    return training, mom
+
+
 class DoubleConv(nn.Module):
     """Reference train/unet.py:66-75: (conv3x3 + BN + ReLU) x 2, ``self.net`` indices 0,1,3,4 hold the parameters."""
 
@@ -138,15 +152,7 @@ class DoubleConv(nn.Module):
     def _stage(self, conv: nn.Conv2d, bn: nn.BatchNorm2d, x0, x1, c_valid, off, groups, im2col=False, head=None, pool=False):
         """``head``: an ``nn.Conv2d(C, 1, 1)`` fused behind this stage (training mode): returns its f32 NCHW output.
         ``pool``: returns ``(activation, MaxPool2d(2)(activation))``."""
-        training = self.training or not bn.track_running_stats
-        if bn.momentum is not None:
-            mom = bn.momentum
-        elif training and bn.num_batches_tracked is not None:
-            # momentum=None is PyTorch's cumulative moving average (factor 1/num_batches_tracked after the bump); the counter
-            # lives on the device, so this rare mode (no reference script uses it) costs one host read per stage
-            mom = -float(int(bn.num_batches_tracked) + 1)
-        else:
-            mom = 0.0
+        training, mom = bn_mode(bn, self.training)
         head_w, head_b = (None, None) if head is None else (head.weight, head.bias)
         a = ops.ConvBNReLU.apply(x0, x1, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                  tuple(c_valid), tuple(off), groups, training, mom, bn.eps, im2col, head_w, head_b, bool(pool) and head is None)

@@ -1445,6 +1445,33 @@ def _bn_forward_stats(stats, n_img, H, W, groups, Co, gamma, beta, running_mean,
     return par, sync
 
 
+def bn_param_grads(need_gamma: bool, need_beta: bool, gamma, beta, sums, Co: int):
+    """(dgamma, dbeta, direct) of one BatchNorm from ``sums`` (sum g, sum g*xhat) [groups, Cop, 2].  ``direct``: both are wanted and
+    both own an attached gradient buffer -- one kernel then adds the groups straight into the buffers (instead of sum + 2 copies +
+    2 accumulates) and nothing is returned to autograd.  Nothing in the backward pass waits for it: with the weight-gradient
+    stream in use it goes there (small dependent launches off the main stream; joined with the weight gradients at the end of
+    backward).  Otherwise the wanted ones are returned (one group: its row as it is, no sum launch); nothing is launched for a
+    frozen pair (requires_grad False: gamma and beta are independent of each other)."""
+    g_gamma, g_beta = direct_grad(gamma), direct_grad(beta)
+    if need_gamma and need_beta and g_gamma is not None and g_beta is not None:
+        def launch():
+            L.check(L.lib.uclstm_bn_bwd_param_grads(_p(sums), sums.shape[0], sums.shape[1], Co, _p(g_gamma), _p(g_beta), 1, _stream()),
+                    "bn_bwd_param_grads")
+            grad_written(gamma)
+            grad_written(beta)
+
+        if ASYNC_WGRAD and PARAM_GRADS_ON_SIDE:
+            _on_side(sums.device, launch, (sums,))
+            _schedule_join(sums.device)
+        else:
+            launch()
+        return None, None, True
+    if not (need_gamma or need_beta):
+        return None, None, False
+    tot = sums[0] if sums.shape[0] == 1 else sums.sum(dim=0)
+    return (tot[:Co, 1].contiguous() if need_gamma else None), (tot[:Co, 0].contiguous() if need_beta else None), False
+
+
 class ConvBNReLU(_GradAwareFunction):
     """One (conv3x3 pad 1 + bias -> BatchNorm2d -> ReLU) stage on NHWC bf16.
 
@@ -1601,30 +1628,10 @@ class ConvBNReLU(_GradAwareFunction):
     def _param_grads(ctx, dz, sums, gamma, beta, bias):
         """Part 2: (dbias, dgamma, dbeta) for autograd; None for a frozen parameter (requires_grad False: fine-tuning -- nothing
         is launched for it; bias, gamma and beta are independent of each other) and for one whose attached gradient was written."""
-        (_, _, groups, training, _, Co, _, has_bias), dev = ctx.cfg, dz.device
+        (_, _, _, training, _, Co, _, has_bias), dev = ctx.cfg, dz.device
         need_b, need_gamma, need_beta = ctx.needs_input_grad[3:6]
-        dbias = dgamma = dbeta = None
-        g_gamma, g_beta = direct_grad(gamma), direct_grad(beta)
-        direct = need_gamma and need_beta and g_gamma is not None and g_beta is not None
-        if direct:
-            # one kernel accumulates straight into the attached gradient buffers (instead of sum + 2 copies + 2 accumulates).
-            # Nothing in the backward pass waits for it: with the weight-gradient stream in use it goes there (18 small
-            # dependent launches off the main stream; joined with the weight gradients at the end of backward).
-            def launch():
-                L.check(L.lib.uclstm_bn_bwd_param_grads(_p(sums), groups, sums.shape[1], Co, _p(g_gamma), _p(g_beta), 1, _stream()),
-                        "bn_bwd_param_grads")
-                grad_written(gamma)
-                grad_written(beta)
-
-            if ASYNC_WGRAD and PARAM_GRADS_ON_SIDE:
-                _on_side(dev, launch, (sums,))
-                _schedule_join(dev)
-            else:
-                launch()
-        elif need_gamma or need_beta:
-            tot = sums.sum(dim=0)
-            dbeta = tot[:Co, 0].contiguous() if need_beta else None
-            dgamma = tot[:Co, 1].contiguous() if need_gamma else None
+        dgamma, dbeta, direct = bn_param_grads(need_gamma, need_beta, gamma, beta, sums, Co)
+        dbias = None
         if need_b and has_bias:
             # training: the conv bias feeds BatchNorm, which removes any per-channel constant -- its gradient is analytically 0.
             # With frozen statistics it is the column sum of dz.

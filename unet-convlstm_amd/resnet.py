@@ -8,10 +8,14 @@
 implicit-GEMM family for the convolutions (stride 2 is a descriptor with ``scale = 2``), ``ops.ConvBNReLU`` for the decoder
 stages, this package's ``ConvLSTM`` for the recurrences and the kernels of ``csrc/resnet.hip`` around them.
 
-The encoder trains after ``model.unfreeze_encoder(stages)``: the stages from the lowest trainable one up run through the autograd
-Functions below (``EncConv``, ``BnRelu``, ``BnAddRelu``, ``MaxPool3s2``) -- the kernels of ``csrc/resnet_bwd.hip``, the stride-2
-weight gradients as descriptors of the weight-gradient family over the OUTPUT grid, and the stride-2 input gradient as one launch of
-the forward family over the four parities of the input pixel (``conv_s2_dgrad``).
+The encoder has ONE route (``_encode`` / ``_block`` / ``_conv_bn``), and every forward body is a plain function without autograd:
+``_conv_stats`` (convolution + BatchNorm constants), ``conv_bn_fold`` (evaluation statistics in the GEMM's epilogue), ``bn_relu``,
+``bn_add_relu``, ``maxpool3s2``, all on the one ``conv_geometry``.  A frozen stage calls them directly.  After
+``model.unfreeze_encoder(stages)`` the stages from the lowest trainable one up call them through the autograd Functions ``EncConv``,
+``BnRelu``, ``BnAddRelu``, ``MaxPool3s2``, whose backward is the kernels of ``csrc/resnet_bwd.hip``, the stride-2 weight gradients as
+descriptors of the weight-gradient family over the OUTPUT grid, and the stride-2 input gradient as one launch of the forward family
+over the four parities of the input pixel (``conv_s2_dgrad``).  Each BatchNorm decides by its own mode; the fold is taken exactly when
+it uses its running statistics and its stage is not under autograd (with a backward pass ``z`` is kept and BatchNorm applied after it).
 
 Frame-by-frame inference is ``step_nhwc`` (driven by ``streaming.PretrainedStreamingPredictor``): the five recurrences advance
 layer by layer, each layer of all five as one ``ops.convlstm_tick``.
@@ -29,7 +33,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import modules, ops
 from ._lib import UclstmError
-from .modules import ConvLSTM
+from .modules import ConvLSTM, bn_mode
 from .ops import F32, SrcView, _p, _stream, cpad, kseg
 
 Tensor = torch.Tensor
@@ -341,16 +345,30 @@ def conv_s2_dgrad(dz: Tensor, weight: Tensor, dz_ds: Optional[Tensor] = None, w_
 
 
 def _bn_args(bn: nn.BatchNorm2d, pending: list):
-    """What EncConv needs of a BatchNorm to form its constants (no gradient flows through these; BnRelu / BnAddRelu own gamma, beta)."""
-    training, mom = _bn_mode(bn)
+    """``bn`` as the kernels take it, for one use in a forward pass: (gamma, beta, running mean, running variance, uses batch
+    statistics, momentum argument, eps).  In training mode its counter goes to ``pending`` (one multi-tensor add per forward).
+    Plain tuples here and in conv_geometry: the eager frame-by-frame path is host-bound."""
+    training, mom = bn_mode(bn, bn.training)
     if training and bn.num_batches_tracked is not None:
         pending.append((bn.num_batches_tracked, 1))
-    return bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, training, mom, bn.eps
+    return bn.weight, bn.bias, bn.running_mean, bn.running_var, training, mom, bn.eps
 
 
-def _conv_stats(x: Tensor, weight: Tensor, pd: L.PackDesc, bn, k: int, s: int, pad: int, Ho: int, Wo: int):
+def conv_geometry(x: Tensor, weight: Tensor, stride: int, im2col: bool):
+    """(pack descriptor, ktap, scale, pad, Ho, Wo) of a bias-free convolution of the encoder, for the forward GEMM and the weight
+    gradient alike.  ``im2col``: ``x`` is the pre-gathered 7x7 stem matrix, a plain GEMM per pixel; otherwise k x k taps with pad
+    k // 2 over the output grid, stride 2 as ``scale = 2`` (the 1x1 downsample convolution: k = 1, pad 0 on the same grid)."""
+    _, Hs, Ws, Cxp = x.shape
+    Co, Ci, k, s = weight.shape[0], weight.shape[1], weight.shape[2], stride
+    if im2col:
+        return im2col7_pack_desc(Co, Ci, Cxp), 1, 1, 0, Hs, Ws
+    return conv_desc(Co, Ci, k, Cxp), k, s, k // 2, (Hs - 1) // s + 1, (Ws - 1) // s + 1
+
+
+def _conv_stats(x: Tensor, weight: Tensor, geom, bn):
     """(z, par): the convolution's pre-BatchNorm output and (scale, shift, mean, rstd) [4, 1, Cop] -- of the batch, with the running
     statistics updated, or (evaluation statistics with a backward pass) of the running statistics."""
+    pd, k, s, pad, Ho, Wo = geom
     gamma, beta, rm, rv, training, mom, eps = bn
     n, Co, dev = x.shape[0], weight.shape[0], x.device
     Cop = cpad(Co)
@@ -366,6 +384,39 @@ def _conv_stats(x: Tensor, weight: Tensor, pd: L.PackDesc, bn, k: int, s: int, p
     return z, par
 
 
+def conv_bn_fold(x: Tensor, weight: Tensor, geom, bn, relu: bool) -> Tensor:
+    """Evaluation statistics without a backward pass: ``bn(conv(x))`` (and ReLU) with BatchNorm's scale and shift in the GEMM's
+    epilogue -- one rounding to 16 bits, where ``_conv_stats`` + ``bn_relu`` make two."""
+    pd, k, s, pad, Ho, Wo = geom
+    gamma, beta, rm, rv, _, mom, eps = bn
+    n, Co, dev = x.shape[0], weight.shape[0], x.device
+    Cop = cpad(Co)
+    wp = ops.pack_weights(pd, weight, 0, x.dtype)
+    out = torch.empty((n, Ho, Wo, Cop), dtype=x.dtype, device=dev)
+    ops.join_forward_side(dev)
+    par = ops._eval_bn_constants(gamma, beta, rm, rv, eps, mom, Co, Cop)
+    ops.igemm_store([SrcView(x)], wp, (Ho, Wo), n, [(out, 0, Cop, 0, 1, 0, 0)], ktap=k, scale=s, pad=pad, col_scale=par[0], col_shift=par[1],
+                    relu=relu)
+    return out
+
+
+def _conv_bn_forward(x: Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, stride: int, pending: list, relu: bool, im2col: bool):
+    """A convolution that is not under autograd: (z, par), or (the finished activation, None) where BatchNorm (and ReLU if ``relu``)
+    went into the GEMM's epilogue -- exactly when this BatchNorm uses its running statistics."""
+    args, geom = _bn_args(bn, pending), conv_geometry(x, conv.weight, stride, im2col)
+    return _conv_stats(x, conv.weight, geom, args) if args[4] else (conv_bn_fold(x, conv.weight, geom, args, relu), None)
+
+
+def bn_relu(z: Tensor, par: Tensor) -> Tensor:
+    """``relu(z*scale + shift)`` with the constants ``par`` of ``_conv_stats``."""
+    a = torch.empty_like(z)
+    pixels, Cp = z.numel() // z.shape[-1], z.shape[-1]
+    ops._timed_hbm("bn_apply_relu", 4.0 * z.numel(),
+                   lambda: L.check(ops._k(z).uclstm_bn_apply_relu(_p(z), _p(a), _p(par[0]), _p(par[1]), pixels, pixels, Cp, _stream()),
+                                   "bn_apply_relu"))
+    return a
+
+
 class EncConv(ops._GradAwareFunction):
     """A bias-free convolution of the trainable encoder and its BatchNorm constants: ``(z, par, z_ds, par_ds)``, ``z`` the
     pre-BatchNorm output.  ``w_ds``: the conv1x1 / stride 2 of the same input (a strided BasicBlock), so that the block's input
@@ -375,33 +426,24 @@ class EncConv(ops._GradAwareFunction):
     @staticmethod
     def forward(ctx, x, weight, w_ds, bn, bn_ds, stride, im2col):
         ops._dev(x, ops.ACT, "activation")
-        n, Hs, Ws, Cxp = x.shape
-        Co, Ci = weight.shape[0], weight.shape[1]
-        if im2col:
-            k, s, pad, Ho, Wo = 1, 1, 0, Hs, Ws
-        else:
-            k, s = weight.shape[2], stride
-            pad, Ho, Wo = k // 2, (Hs - 1) // s + 1, (Ws - 1) // s + 1
-            if s == 2 and (Hs % 2 or Ws % 2):
-                raise UclstmError("EncConv: a stride-2 convolution with a backward pass needs even input sizes")
-        z, par = _conv_stats(x, weight, EncConv._desc(weight, Cxp, im2col), bn, k, s, pad, Ho, Wo)
-        z_ds = par_ds = None
+        g = conv_geometry(x, weight, stride, im2col)
+        if g[2] == 2 and (x.shape[1] % 2 or x.shape[2] % 2):          # scale 2: conv_s2_dgrad writes a (2 Ho, 2 Wo) input
+            raise UclstmError("EncConv: a stride-2 convolution with a backward pass needs even input sizes")
+        z, par = _conv_stats(x, weight, g, bn)
+        g_ds = z_ds = par_ds = None
         if w_ds is not None:
-            z_ds, par_ds = _conv_stats(x, w_ds, conv_desc(Co, Ci, 1, Cxp), bn_ds, 1, s, 0, Ho, Wo)
+            g_ds = conv_geometry(x, w_ds, stride, False)
+            z_ds, par_ds = _conv_stats(x, w_ds, g_ds, bn_ds)
         ctx.mark_non_differentiable(*[t for t in (par, par_ds) if t is not None])
         ctx.save_for_backward(x, weight, w_ds)
-        ctx.geom = (k, s, pad, Ho, Wo, im2col)
+        ctx.geom = (g, g_ds, im2col)
         if ops._will_backward(ctx):
             ops.note_use(weight, w_ds)
         return z, par, z_ds, par_ds
 
     @staticmethod
-    def _desc(weight, Cxp, im2col):
-        Co, Ci = weight.shape[0], weight.shape[1]
-        return im2col7_pack_desc(Co, Ci, Cxp) if im2col else conv_desc(Co, Ci, weight.shape[2], Cxp)
-
-    @staticmethod
-    def _wgrad(x, weight, dz, pd, k, s, pad, Ho, Wo):
+    def _wgrad(x, weight, dz, geom):
+        pd, k, s, pad, Ho, Wo = geom
         n, Cop = x.shape[0], dz.shape[3]
         return ops.wgrad_into_param(weight, pd, [x, dz], lambda: ops.igemm_wgrad([SrcView(x)], [(dz, 0, Cop, 0, 1, 0, 0)], pd.N, pd.Ktot,
                                                                                  (Ho, Wo), n, ktap=k, scale=s, pad=pad))
@@ -409,44 +451,25 @@ class EncConv(ops._GradAwareFunction):
     @staticmethod
     def backward(ctx, dz, _dpar, dz_ds, _dpar_ds):
         x, weight, w_ds = ctx.saved_tensors
-        k, s, pad, Ho, Wo, im2col = ctx.geom
-        n, Cxp = x.shape[0], x.shape[3]
-        Co, Ci = weight.shape[0], weight.shape[1]
+        g, g_ds, im2col = ctx.geom
+        _, _, scale, _, Ho, Wo = g
         dz = dz.contiguous()
         dz_ds = None if (dz_ds is None or w_ds is None) else dz_ds.contiguous()
         dweight = dw_ds = dx = None
         if ctx.needs_input_grad[1]:
-            dweight = EncConv._wgrad(x, weight, dz, EncConv._desc(weight, Cxp, im2col), k, s, pad, Ho, Wo)
+            dweight = EncConv._wgrad(x, weight, dz, g)
         if dz_ds is not None and ctx.needs_input_grad[2]:
-            dw_ds = EncConv._wgrad(x, w_ds, dz_ds, conv_desc(Co, Ci, 1, Cxp), 1, s, 0, Ho, Wo)
+            dw_ds = EncConv._wgrad(x, w_ds, dz_ds, g_ds)
         if ctx.needs_input_grad[0] and not im2col:
-            if s == 2:
+            if scale == 2:
                 dx = conv_s2_dgrad(dz, weight, dz_ds, w_ds)
             else:
+                Co, Ci = weight.shape[0], weight.shape[1]
                 dd = ops.conv_dgrad_pack_desc(Co, Ci, Ci)
                 wd = ops.pack_weights(dd, weight, 0, dz.dtype)
                 dx = torch.empty_like(x)
-                ops.igemm_store([SrcView(dz)], wd, (Ho, Wo), n, [(dx, 0, dd.N, 0, 1, 0, 0)], ktap=3, pad=1)
+                ops.igemm_store([SrcView(dz)], wd, (Ho, Wo), x.shape[0], [(dx, 0, dd.N, 0, 1, 0, 0)], ktap=3, pad=1)
         return dx, dweight, dw_ds, None, None, None, None
-
-
-def _bn_param_grads(need_gamma: bool, need_beta: bool, gamma: Tensor, beta: Tensor, sums: Tensor, Co: int):
-    """(dgamma, dbeta) for autograd from the sums (sum g, sum g*xhat) [1, Cop, 2]; (None, None) after the attached gradient buffers
-    were written directly (the route of ops.ConvBNReLU._param_grads); nothing is launched for a frozen pair."""
-    g_gamma, g_beta = ops.direct_grad(gamma), ops.direct_grad(beta)
-    if need_gamma and need_beta and g_gamma is not None and g_beta is not None:
-        def launch():
-            L.check(L.lib.uclstm_bn_bwd_param_grads(_p(sums), 1, sums.shape[1], Co, _p(g_gamma), _p(g_beta), 1, _stream()), "bn_bwd_param_grads")
-            ops.grad_written(gamma)
-            ops.grad_written(beta)
-
-        if ops.ASYNC_WGRAD and ops.PARAM_GRADS_ON_SIDE:
-            ops._on_side(sums.device, launch, (sums,))
-            ops._schedule_join(sums.device)
-        else:
-            launch()
-        return None, None
-    return (sums[0, :Co, 1].contiguous() if need_gamma else None), (sums[0, :Co, 0].contiguous() if need_beta else None)
 
 
 class BnRelu(ops._GradAwareFunction):
@@ -455,11 +478,7 @@ class BnRelu(ops._GradAwareFunction):
 
     @staticmethod
     def forward(ctx, z, par, gamma, beta, training):
-        a = torch.empty_like(z)
-        pixels, Cp = z.numel() // z.shape[-1], z.shape[-1]
-        ops._timed_hbm("bn_apply_relu", 4.0 * z.numel(),
-                       lambda: L.check(ops._k(z).uclstm_bn_apply_relu(_p(z), _p(a), _p(par[0]), _p(par[1]), pixels, pixels, Cp, _stream()),
-                                       "bn_apply_relu"))
+        a = bn_relu(z, par)
         ctx.save_for_backward(z, par, gamma, beta)
         ctx.training = training
         if ops._will_backward(ctx):
@@ -480,7 +499,7 @@ class BnRelu(ops._GradAwareFunction):
             ops._timed_hbm("bn_bwd_reduce", 4.0 * z.numel(),
                            lambda: L.check(K.uclstm_bn_bwd_reduce(_p(z), _p(da), *pq, _p(partials), _p(sums), pixels, pixels, Cp, _stream()),
                                            "bn_bwd_reduce"))
-        dgamma, dbeta = _bn_param_grads(need_gamma, need_beta, gamma, beta, sums, gamma.shape[0]) if (need_gamma or need_beta) else (None, None)
+        dgamma, dbeta, _ = ops.bn_param_grads(need_gamma, need_beta, gamma, beta, sums, gamma.shape[0])
         dz = None
         if need_z:
             dz = torch.empty_like(z)
@@ -523,10 +542,10 @@ class BnAddRelu(ops._GradAwareFunction):
             ops._timed_hbm("bn_add_relu_bwd_reduce", 6.0 * z.numel(),
                            lambda: L.check(K.uclstm_bn_add_relu_bwd_reduce(_p(z), *pq, _p(r), *rq, _p(da), _p(partials), _p(sums), _p(rsums),
                                                                            pixels, Cp, _stream()), "bn_add_relu_bwd_reduce"))
-        dgamma, dbeta = _bn_param_grads(need[2], need[3], gamma, beta, sums, gamma.shape[0]) if (need[2] or need[3]) else (None, None)
+        dgamma, dbeta, _ = ops.bn_param_grads(need[2], need[3], gamma, beta, sums, gamma.shape[0])
         drgamma = drbeta = None
-        if raff and (need[6] or need[7]):
-            drgamma, drbeta = _bn_param_grads(need[6], need[7], rgamma, rbeta, rsums, rgamma.shape[0])
+        if raff:
+            drgamma, drbeta, _ = ops.bn_param_grads(need[6], need[7], rgamma, rbeta, rsums, rgamma.shape[0])
         dz = dr = None
         if need[0] or need[4]:
             if not (ctx.training and need_reduce) or (raff and not ctx.rtraining):
@@ -540,18 +559,6 @@ class BnAddRelu(ops._GradAwareFunction):
                            lambda: L.check(K.uclstm_bn_add_relu_bwd_apply(_p(z), *pq, _p(s_z), _p(r), *rq, _p(s_r), _p(da), _p(dz), _p(dr),
                                                                           pixels, Cp, _stream()), "bn_add_relu_bwd_apply"))
         return dz, None, dgamma, dbeta, dr, None, drgamma, drbeta, None, None
-
-
-def _bn_mode(bn: nn.BatchNorm2d):
-    """(uses batch statistics, momentum argument of the BatchNorm kernels) -- the rule of modules.DoubleConv._stage."""
-    training = bn.training or not bn.track_running_stats
-    if bn.momentum is not None:
-        mom = bn.momentum
-    elif training and bn.num_batches_tracked is not None:
-        mom = -float(int(bn.num_batches_tracked) + 1)
-    else:
-        mom = 0.0
-    return training, mom
 
 
 # ---------------------------------------------------------------------------------------------
@@ -644,120 +651,97 @@ class PretrainedTemporalUNet(nn.Module):
                 return i
         return None
 
-    # -- encoder: trainable stages (autograd Functions; everything below the lowest trainable stage stays forward-only) -----
-    def _t_block(self, x: Tensor, blk: BasicBlock, pending: list) -> Tensor:
-        ds = blk.downsample
-        z1, par1, zr, rpar = EncConv.apply(x, blk.conv1.weight, None if ds is None else ds[0].weight, _bn_args(blk.bn1, pending),
-                                           None if ds is None else _bn_args(ds[1], pending), blk.conv1.stride[0], False)
-        a1 = BnRelu.apply(z1, par1, blk.bn1.weight, blk.bn1.bias, _bn_mode(blk.bn1)[0])
-        z2, par2, _, _ = EncConv.apply(a1, blk.conv2.weight, None, _bn_args(blk.bn2, pending), None, 1, False)
-        if ds is None:
-            return BnAddRelu.apply(z2, par2, blk.bn2.weight, blk.bn2.bias, x, None, None, None, _bn_mode(blk.bn2)[0], False)
-        return BnAddRelu.apply(z2, par2, blk.bn2.weight, blk.bn2.bias, zr, rpar, ds[1].weight, ds[1].bias, _bn_mode(blk.bn2)[0],
-                               _bn_mode(ds[1])[0])
+    # -- encoder: ONE route.  ``grad``: the stage runs under autograd (EncConv, BnRelu, BnAddRelu, MaxPool3s2); without it the plain
+    #    functions those Functions call run directly, under no_grad -- the forward-only route pays for no Function.apply ----------
+    @staticmethod
+    def _conv_bn(x: Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, ds: Optional[nn.Sequential], pending: list, grad: bool,
+                 relu: bool = False, im2col: bool = False):
+        """``(z, par, z_ds, par_ds)`` of ``conv`` and (``ds``: the block's downsample pair) of the conv1x1 of the same input, launched
+        right behind it.  ``par`` None: ``z`` is finished (the fold: that BatchNorm uses its running statistics and the stage is
+        not under autograd)."""
+        stride = conv.stride[0]
+        if grad:
+            return EncConv.apply(x, conv.weight, None if ds is None else ds[0].weight, _bn_args(bn, pending),
+                                 None if ds is None else _bn_args(ds[1], pending), stride, im2col)
+        main = _conv_bn_forward(x, conv, bn, stride, pending, relu, im2col)
+        return main + ((None, None) if ds is None else _conv_bn_forward(x, ds[0], ds[1], stride, pending, False, False))
 
-    def _encode_trainable(self, x_seq: Tensor, pending: list, first: int):
-        """``_encode`` with the stages from ``first`` on under autograd.  The stem never computes an input gradient."""
-        enc = self.encoder
-        col = im2col7x7s2_first(x_seq)
-        if first == 0:
-            z, par, _, _ = EncConv.apply(col, enc.conv1.weight, None, _bn_args(enc.bn1, pending), None, 2, True)
-            f1 = BnRelu.apply(z, par, enc.bn1.weight, enc.bn1.bias, _bn_mode(enc.bn1)[0])
-            a, f1 = MaxPool3s2.apply(f1)
-        else:
-            with torch.no_grad():
-                f1 = self._conv_bn_relu(col, enc.conv1, enc.bn1, pending, im2col=True)
-                a = maxpool3s2(f1)
-        feats = [f1]
-        for li, layer in enumerate((enc.layer1, enc.layer2, enc.layer3, enc.layer4), start=1):
-            for blk in layer:
-                if li >= first:
-                    a = self._t_block(a, blk, pending)
-                else:
-                    with torch.no_grad():
-                        a = self._block(a, blk, pending)
-            feats.append(a)
-        return feats
-
-    # -- encoder: forward-only stages -----------------------------------------------------------
-    def _conv_bn(self, x: Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool, pending: list, im2col: bool = False):
-        """conv (+ BatchNorm statistics).  Training mode: (pre-BatchNorm z, par) -- the caller applies the affine; evaluation
-        mode: (BatchNorm folded into the epilogue, with ReLU if ``relu``, None)."""
-        n, Hs, Ws, Cxp = x.shape
-        Co, Ci = conv.weight.shape[0], conv.weight.shape[1]
-        Cop, dev = cpad(Co), x.device
-        if im2col:
-            k, s, pad, (Ho, Wo) = 1, 1, 0, (Hs, Ws)
-            pd = im2col7_pack_desc(Co, Ci, Cxp)
-        else:
-            k, s = conv.kernel_size[0], conv.stride[0]
-            pad, Ho, Wo = k // 2, (Hs - 1) // s + 1, (Ws - 1) // s + 1
-            pd = conv_desc(Co, Ci, k, Cxp)
-        wp = ops.pack_weights(pd, conv.weight, 0, x.dtype)
-        out = torch.empty((n, Ho, Wo, Cop), dtype=x.dtype, device=dev)
-        seg = [(out, 0, Cop, 0, 1, 0, 0)]
-        training, mom = _bn_mode(bn)
-        if not training:
-            ops.join_forward_side(dev)
-            par = ops._eval_bn_constants(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, mom, Co, Cop)
-            ops.igemm_store([SrcView(x)], wp, (Ho, Wo), n, seg, ktap=k, scale=s, pad=pad, col_scale=par[0], col_shift=par[1], relu=relu)
-            return out, None
-        stats = torch.empty((1, L.lib.uclstm_igemm_tiles_per_group(n, Ho, Wo, 1, Cop), Cop, 2), dtype=F32, device=dev)
-        ops.igemm_store([SrcView(x)], wp, (Ho, Wo), n, seg, ktap=k, scale=s, pad=pad, groups=1, stats=stats)
-        par, _ = ops._bn_forward_stats(stats, n, Ho, Wo, 1, Co, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, "plain")
-        if bn.num_batches_tracked is not None:
-            pending.append((bn.num_batches_tracked, 1))
-        return out, par
-
-    def _conv_bn_relu(self, x, conv, bn, pending, im2col=False) -> Tensor:
-        z, par = self._conv_bn(x, conv, bn, True, pending, im2col)
+    @staticmethod
+    def _bn_relu(z: Tensor, par: Optional[Tensor], bn: nn.BatchNorm2d, grad: bool) -> Tensor:
         if par is None:
             return z
-        a = torch.empty_like(z)
-        pixels = z.numel() // z.shape[-1]
-        ops._timed_hbm("bn_apply_relu", 4.0 * z.numel(),
-                       lambda: L.check(ops._k(z).uclstm_bn_apply_relu(_p(z), _p(a), _p(par[0]), _p(par[1]), pixels, pixels, z.shape[-1],
-                                                                      _stream()), "bn_apply_relu"))
-        return a
+        return BnRelu.apply(z, par, bn.weight, bn.bias, bn_mode(bn, bn.training)[0]) if grad else bn_relu(z, par)
 
-    def _block(self, x: Tensor, blk: BasicBlock, pending: list) -> Tensor:
-        a1 = self._conv_bn_relu(x, blk.conv1, blk.bn1, pending)
-        z2, par2 = self._conv_bn(a1, blk.conv2, blk.bn2, False, pending)
-        r, rpar = x, None
-        if blk.downsample is not None:
-            r, rpar = self._conv_bn(x, blk.downsample[0], blk.downsample[1], False, pending)
-        return bn_add_relu(z2, par2, r, rpar)
+    def _block(self, x: Tensor, blk: BasicBlock, pending: list, grad: bool) -> Tensor:
+        ds = blk.downsample
+        z1, par1, r, rpar = self._conv_bn(x, blk.conv1, blk.bn1, ds, pending, grad, relu=True)
+        a1 = self._bn_relu(z1, par1, blk.bn1, grad)
+        z2, par2, _, _ = self._conv_bn(a1, blk.conv2, blk.bn2, None, pending, grad)
+        if ds is None:
+            r = x
+        if not grad:
+            return bn_add_relu(z2, par2, r, rpar)
+        rbn = (None, None, False) if ds is None else (ds[1].weight, ds[1].bias, bn_mode(ds[1], ds[1].training)[0])
+        return BnAddRelu.apply(z2, par2, blk.bn2.weight, blk.bn2.bias, r, rpar, rbn[0], rbn[1], bn_mode(blk.bn2, blk.bn2.training)[0], rbn[2])
 
-    def _encode(self, x_seq: Tensor, pending: list):
-        """f32 [B,T,2,H,W] -> (f1 .. f5), 16-bit NHWC with image ``t*B + b``, at H/2 .. H/32."""
-        enc = self.encoder
-        f1 = self._conv_bn_relu(im2col7x7s2_first(x_seq), enc.conv1, enc.bn1, pending, im2col=True)
-        feats, a = [f1], maxpool3s2(f1)
-        for layer in (enc.layer1, enc.layer2, enc.layer3, enc.layer4):
-            for blk in layer:
-                a = self._block(a, blk, pending)
+    def _encode(self, x_seq: Tensor, pending: list, first: Optional[int] = None):
+        """f32 [B,T,2,H,W] -> (f1 .. f5), 16-bit NHWC with image ``t*B + b``, at H/2 .. H/32.  ``first``: index into ENCODER_STAGES
+        of the lowest stage under autograd; None: none, and the caller runs this under no_grad.  The stem never computes an input
+        gradient."""
+        enc, feats = self.encoder, []
+
+        def stage(i: int, a: Tensor) -> Tensor:
+            grad = first is not None and i >= first
+            if i == 0:
+                z, par, _, _ = self._conv_bn(a, enc.conv1, enc.bn1, None, pending, grad, relu=True, im2col=True)
+                f1 = self._bn_relu(z, par, enc.bn1, grad)
+                a, f1 = MaxPool3s2.apply(f1) if grad else (maxpool3s2(f1), f1)
+                feats.append(f1)
+                return a
+            for blk in getattr(enc, ENCODER_STAGES[i]):
+                a = self._block(a, blk, pending, grad)
             feats.append(a)
+            return a
+
+        a = im2col7x7s2_first(x_seq)
+        for i in range(len(ENCODER_STAGES)):
+            if first is None or i >= first:
+                a = stage(i, a)
+            else:
+                with torch.no_grad():          # below the lowest trainable stage: as in the frozen model
+                    a = stage(i, a)
         return feats
 
     # -- decoder --------------------------------------------------------------------------------
     @staticmethod
     def _stage(seq: nn.Sequential, x0: Tensor, x1: Optional[Tensor], c_valid, pending: list) -> Tensor:
-        conv, bn = seq[0], seq[1]
-        training, mom = _bn_mode(bn)
-        a = ops.ConvBNReLU.apply(x0, x1, conv.weight, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, tuple(c_valid), (0, 0), 1,
-                                 training, mom, bn.eps, False)
-        if training and bn.num_batches_tracked is not None:
-            pending.append((bn.num_batches_tracked, 1))
-        return a
+        gamma, beta, rm, rv, training, mom, eps = _bn_args(seq[1], pending)
+        return ops.ConvBNReLU.apply(x0, x1, seq[0].weight, None, gamma, beta, rm, rv, tuple(c_valid), (0, 0), 1, training, mom, eps, False)
+
+    def _decode(self, x: Tensor, skips, pending: list) -> Tensor:
+        """The five blocks of the decoder on ``x`` (the bottleneck, 16-bit NHWC) and ``skips`` (deepest first, None for the last block),
+        then the head: f32 ``[n, out_channels, H, W]``."""
+        for blk, skip in zip(self.decoder.blocks, skips):
+            cin, cskip, cout = blk.channels
+            up = Upsample2.apply(x)
+            x = self._stage(blk.conv1, up, skip, (cin, cskip) if skip is not None else (cin,), pending)
+            x = self._stage(blk.conv2, x, None, (cout,), pending)
+        conv = self.head[0]
+        return Head3x3.apply(x, conv.weight, conv.bias)
+
+    @staticmethod
+    def _check_input(x: Tensor, who: str, ndim: int) -> None:
+        """``ndim`` 5: a sequence [B, T, C, H, W]; 4: one frame [B, C, H, W]."""
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise UclstmError(f"{who}: a HIP device tensor is required (this package has no CPU path)")
+        if x.dim() != ndim or x.shape[-3] != ENCODER_CHANNELS[0]:
+            raise UclstmError(f"{who}: expected [B, {'T, ' if ndim == 5 else ''}{ENCODER_CHANNELS[0]}, H, W], got {tuple(x.shape)}")
+        H, W = x.shape[-2:]
+        if H % 32 or W % 32:
+            raise UclstmError(f"{who}: H and W must be multiples of 32 (five stride-2 stages), got {H} x {W}")
 
     def forward(self, x_seq: Tensor):
-        if not isinstance(x_seq, torch.Tensor) or not x_seq.is_cuda:
-            raise UclstmError("PretrainedTemporalUNet: a HIP device tensor is required (this package has no CPU path)")
-        if x_seq.dim() != 5 or x_seq.shape[2] != ENCODER_CHANNELS[0]:
-            raise UclstmError(f"PretrainedTemporalUNet: expected [B, T, {ENCODER_CHANNELS[0]}, H, W], got {tuple(x_seq.shape)}")
-        B, T, _, H, W = x_seq.shape
-        if H % 32 or W % 32:
-            raise UclstmError(f"PretrainedTemporalUNet: H and W must be multiples of 32 (five stride-2 stages), got {H} x {W}")
+        self._check_input(x_seq, "PretrainedTemporalUNet", 5)
         if torch.is_grad_enabled() and not self._encoder_opt_in and any(p.requires_grad for p in self.encoder.parameters()):
             raise UclstmError("PretrainedTemporalUNet: training an unfrozen encoder is opt-in: call model.unfreeze_encoder() (all "
                               "stages, or e.g. (\"layer3\", \"layer4\")) first, construct with freeze_encoder=True, or run under "
@@ -793,16 +777,11 @@ class PretrainedTemporalUNet(nn.Module):
         One step: the encoder on the frame, layer l of all five ConvLSTMs as ONE ``ops.convlstm_tick`` (l = 0, 1, ...), the
         decoder, the head.  Inference only: it raises in grad mode, and while any BatchNorm is in training mode (a one-frame
         batch statistic is not what ``forward`` computes, and it would move the running statistics)."""
-        if not isinstance(x_t, torch.Tensor) or not x_t.is_cuda:
-            raise UclstmError("PretrainedTemporalUNet.step_nhwc: a HIP device tensor is required (this package has no CPU path)")
-        if x_t.dim() != 4 or x_t.shape[1] != ENCODER_CHANNELS[0]:
-            raise UclstmError(f"PretrainedTemporalUNet.step_nhwc: expected [B, {ENCODER_CHANNELS[0]}, H, W], got {tuple(x_t.shape)}")
+        self._check_input(x_t, "PretrainedTemporalUNet.step_nhwc", 4)
         B, _, H, W = x_t.shape
-        if H % 32 or W % 32:
-            raise UclstmError(f"PretrainedTemporalUNet.step_nhwc: H and W must be multiples of 32 (five stride-2 stages), got {H} x {W}")
         if torch.is_grad_enabled():
             raise UclstmError("PretrainedTemporalUNet.step_nhwc is inference only: call it under torch.no_grad()")
-        if any(isinstance(m, nn.BatchNorm2d) and _bn_mode(m)[0] for m in self.modules()):
+        if any(isinstance(m, nn.BatchNorm2d) and bn_mode(m, m.training)[0] for m in self.modules()):
             raise UclstmError("PretrainedTemporalUNet.step_nhwc: a BatchNorm is in training mode (batch statistics of one frame are "
                               "not what forward() computes): call model.eval() first")
         adt, dev = ops.get_compute_dtype(), x_t.device
@@ -829,37 +808,19 @@ class PretrainedTemporalUNet(nn.Module):
                 members.append((xs[key], h_prev, c_prev, h_out, c_out, cell.conv.weight, cell.conv.bias, cell.hidden_dim, cell.input_dim))
                 xs[key] = h_out
             ops.convlstm_tick(members)
-        x = xs["lstm"]
-        skips = [xs[f"skip{j}"] for j in (4, 3, 2, 1)] + [None]
-        for blk, skip in zip(self.decoder.blocks, skips):
-            cin, cskip, cout = blk.channels
-            up = Upsample2.apply(x)
-            x = self._stage(blk.conv1, up, skip, (cin, cskip) if skip is not None else (cin,), pending)
-            x = self._stage(blk.conv2, x, None, (cout,), pending)
-        ops.join_forward_side(dev)
-        conv = self.head[0]
-        return Head3x3.apply(x, conv.weight, conv.bias), new_state
+        ops.join_forward_side(dev)          # (nothing is pending here: every evaluation-mode stage above has joined already)
+        return self._decode(xs["lstm"], [xs[f"skip{j}"] for j in (4, 3, 2, 1)] + [None], pending), new_state
 
     def _forward(self, x_seq: Tensor, pending: list) -> Tensor:
         B, T, _, H, W = x_seq.shape
         first = self._first_trainable_stage() if (torch.is_grad_enabled() and self._encoder_opt_in) else None
-        if first is None:
-            with torch.no_grad():
-                feats = self._encode(x_seq, pending)
-        else:
-            feats = self._encode_trainable(x_seq, pending, first)
+        with torch.set_grad_enabled(first is not None):
+            feats = self._encode(x_seq, pending, first)
 
         def run(lstm: ConvLSTM, f: Tensor) -> Tensor:          # [T*B,h,w,C] -> the last layer's h for all steps, same shape
             out, _ = lstm.seq_nhwc(f.view(T, B, *f.shape[1:]), None)
             return out.reshape(T * B, *out.shape[2:])
 
         x = run(self.lstm, feats[4])
-        skips = [run(self.lstm_skips[j], feats[j - 1]) for j in (4, 3, 2, 1)] + [None]
-        for blk, skip in zip(self.decoder.blocks, skips):
-            cin, cskip, cout = blk.channels
-            up = Upsample2.apply(x)
-            x = self._stage(blk.conv1, up, skip, (cin, cskip) if skip is not None else (cin,), pending)
-            x = self._stage(blk.conv2, x, None, (cout,), pending)
-        conv = self.head[0]
-        y = Head3x3.apply(x, conv.weight, conv.bias)
+        y = self._decode(x, [run(self.lstm_skips[j], feats[j - 1]) for j in (4, 3, 2, 1)] + [None], pending)
         return y.view(T, B, self.out_channels, H, W).transpose(0, 1)
