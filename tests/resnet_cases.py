@@ -1,7 +1,8 @@
 """Helpers of the PretrainedTemporalUNet tests that need no GPU (plain torch on the CPU): the state-dict key / shape table of the
 reference's ``resnet18_frozen_*`` checkpoints (train/resnet18.py:26-74 over smp.Unet("resnet18", in_channels=2,
-decoder_channels=(256,128,64,32,16))), a seeded state generator, a FUNCTIONAL RESTATEMENT of the model's forward pass, and f64
-references of the kernels of csrc/resnet.hip with their counted bounds.
+decoder_channels=(256,128,64,32,16))), a seeded state generator, a FUNCTIONAL RESTATEMENT of the model's forward pass, the
+single-stage gradient helpers (``stage_grads`` / ``report``) with the seeded decoder cases built on them, and f64 references of the
+kernels of csrc/resnet.hip with their counted bounds.
 
 The yardstick of the model tests is this restatement, written for the tests from the reference's forward (train/resnet18.py:76-139),
 torchvision's BasicBlock and smp's decoder block as the issue states them -- not a fixture produced by the reference: smp is not
@@ -9,9 +10,12 @@ available where the fixtures are made, so no golden file exists for the encoder 
 F.batch_norm / F.max_pool2d / F.interpolate(mode="nearest") and the ConvLSTM equations (train/unet.py:21-36).
 """
 import contextlib
+import functools
 
 import torch
 import torch.nn.functional as F
+
+from conftest import per_tensor_grad_report, rel_l2
 
 ENC = (2, 64, 64, 128, 256, 512)
 DEC_IN, DEC_SKIP, DEC_OUT = (512, 256, 128, 64, 32), (256, 128, 64, 64, 0), (256, 128, 64, 32, 16)
@@ -185,7 +189,6 @@ class _Ref:
         return out
 
     def forward(self, x):
-        p = self.p
         B, T = x.shape[:2]
         feats = self.encoder(x.reshape(B * T, *x.shape[2:]).to(self.dtype))
 
@@ -193,15 +196,26 @@ class _Ref:
             return self.convlstm(f.view(B, T, *f.shape[1:]), prefix).reshape(B * T, *f.shape[1:])
 
         a = temporal(feats[4], "lstm.")
-        skips = [temporal(feats[j - 1], f"lstm_skips.{j}.") for j in (4, 3, 2, 1)] + [None]
-        for i, skip in enumerate(skips):
-            a = F.interpolate(a, scale_factor=2, mode="nearest")
-            if skip is not None:
-                a = torch.cat([a, skip], 1)
-            for c in ("conv1", "conv2"):
-                a = F.relu(self.bn(F.conv2d(a, p[f"decoder.blocks.{i}.{c}.0.weight"], None, 1, 1), f"decoder.blocks.{i}.{c}.1."))
-        y = F.conv2d(a, p["head.0.weight"], p["head.0.bias"], 1, 1)
+        y = self.decoder(a, [temporal(feats[j - 1], f"lstm_skips.{j}.") for j in (4, 3, 2, 1)] + [None])
         return y.view(B, T, *y.shape[1:])
+
+    def concat(self, up, skip):
+        return torch.cat([up, skip], 1)
+
+    def decoder_block(self, x, skip, i):
+        """smp's DecoderBlock ``i``: nearest x2, cat([x, skip]) (``skip`` None: the last block), conv3x3 / BatchNorm / ReLU twice."""
+        a = F.interpolate(x, scale_factor=2, mode="nearest")
+        if skip is not None:
+            a = self.concat(a, skip)
+        for c in ("conv1", "conv2"):
+            a = F.relu(self.bn(F.conv2d(a, self.p[f"decoder.blocks.{i}.{c}.0.weight"], None, 1, 1), f"decoder.blocks.{i}.{c}.1."))
+        return a
+
+    def decoder(self, x, skips):
+        """The five blocks on the bottleneck ``x`` and ``skips`` (deepest first, None for the last block), then the head."""
+        for i, skip in enumerate(skips):
+            x = self.decoder_block(x, skip, i)
+        return F.conv2d(x, self.p["head.0.weight"], self.p["head.0.bias"], 1, 1)
 
 
 def forward_ref(sd, x, training, dtype=torch.float64, autocast=None):
@@ -242,6 +256,115 @@ def make_batch(seed, B, T, H, W, out_channels=1):
     y = torch.randn(B, T, out_channels, H, W, generator=g) * 0.5
     mask = (torch.rand(B, T, out_channels, H, W, generator=g) > 0.2).float()
     return x, y, mask
+
+
+# ---------------------------------------------------------------------------------------------
+# single stages against f64: gradients of sum(out * gout), and the restatement's own reduced-precision drift as the anchor
+# ---------------------------------------------------------------------------------------------
+def stage_grads(sd, prefix, x, gouts, run, dtype, autocast, training=True, ref_cls=None, keep=None):
+    """Gradients of sum(out_i * gout_i) with respect to x and every parameter under ``prefix`` (one prefix or a tuple of them);
+    ``run(ref, x)`` -> outputs.  ``x``: one tensor, whose gradient is returned as "x", or a dict name -> tensor (None entries stay
+    None and get no gradient): ``run`` then gets the dict of leaves.  ``training``: the BatchNorm mode of the restatement;
+    ``ref_cls``: a subclass of _Ref to run instead; ``keep`` (a dict) receives "outs" and "buffers"."""
+    names = [k for k in sd if k.startswith(prefix) and not is_buffer(k)]
+    leaves = {k: sd[k].detach().to(dtype).clone().requires_grad_(True) for k in names}
+    leaf = lambda t: None if t is None else t.detach().to(dtype).clone().requires_grad_(True)
+    xs = {k: leaf(v) for k, v in x.items()} if isinstance(x, dict) else {"x": leaf(x)}
+    ref = (ref_cls or _Ref)({**sd, **leaves}, training, dtype)
+    with (torch.autocast("cpu", dtype=autocast) if autocast is not None else contextlib.nullcontext()):
+        outs = run(ref, xs if isinstance(x, dict) else xs["x"])
+    loss = sum((o.to(dtype) * g.to(dtype)).sum() for o, g in zip(outs, gouts))
+    wrt = {**{k: v for k, v in xs.items() if v is not None}, **leaves}
+    grads = torch.autograd.grad(loss, list(wrt.values()), allow_unused=True)
+    if keep is not None:
+        keep.update(outs=[o.detach() for o in outs], buffers=dict(ref.buffers))
+    return dict(zip(wrt, grads))
+
+
+def report(what, got, want, anchor, label=lambda k: k.split(".", 3)[-1]):
+    """conftest.per_tensor_grad_report with its defaults over the tensors of ``want``: prints the ratios (``label``: how a key is
+    printed; by default without its stage prefix), raises on a failure."""
+    names = list(want)
+    bad, rows, med = per_tensor_grad_report(names, got, want, [float(want[k].norm()) for k in names], [anchor[k] for k in names])
+    print(f"[parity] {what}: median rel-L2 / anchor {med:.3f} (bound 1.25); (rel-L2 / bound): " +
+          "; ".join(f"{label(k)} {rel:.4f}/{bound:.4f}" for _, k, rel, bound, _, z in rows if not z))
+    assert not bad, " | ".join(bad[:8])
+
+
+# ---------------------------------------------------------------------------------------------
+# the decoder, one block at a time and as a chain: seeded inputs, the f64 reference and the autocast anchor of every case of
+# tests/test_gpu_resnet_decoder.py, computed on the CPU (tests/test_resnet_host.py checks the anchors without a GPU)
+# ---------------------------------------------------------------------------------------------
+DEC_STATE_SEED = 101
+DEC_DTYPES = (torch.bfloat16, torch.float16)
+DEC_MODES = ("train", "eval")                      # BatchNorm with batch statistics / with running statistics, both with a backward pass
+DEC_ANCHOR_CAP, DEC_CHAIN_ANCHOR_CAP = 0.12, 0.30   # conditions on the INPUTS: with them the per-tensor bound 2.5 x anchor stays <= 0.30 / 0.75
+DEC_CHAIN_N = 4
+# forward floor of one stage in bf16 (tests/test_gpu_ops.py::test_conv_bn_relu_train_fwd_bwd_two_groups); fp16 has three more mantissa bits
+DEC_OUT_FLOOR = {torch.bfloat16: 6e-3, torch.float16: 6e-3 / 8}
+
+
+def decoder_block_shapes(i):
+    """(n, h, w) of the input of block ``i`` (its skip and its output are 2h x 2w): the block's own shape in the model's smallest
+    test case (B2 T2, 64 x 64), and 3 x (3, 5) -> 180 output pixels: a partial tile in every direction, non-square, an odd image count."""
+    return [(4, 2 ** (i + 1), 2 ** (i + 1)), (3, 3, 5)]
+
+
+@functools.lru_cache(maxsize=None)
+def decoder_state():
+    """The decoder's and the head's entries of make_state(DEC_STATE_SEED): shared, never modified."""
+    return {k: v for k, v in make_state(DEC_STATE_SEED, 1, 1).items() if k.startswith(("decoder.", "head."))}
+
+
+def decoder_block_inputs(i, shape, dtype):
+    """(x [n,cin,h,w], skip [n,cskip,2h,2w] or None, gout [n,cout,2h,2w]): f32 values that ``dtype`` holds exactly, so that the
+    device and the reference start from the same numbers (gout too: autograd hands it to the stage in the activation's dtype)."""
+    n, h, w = shape
+    g = torch.Generator().manual_seed(4000 + 100 * i + 10 * n + h)
+    q = lambda t: t.to(dtype).float()
+    x = q(torch.randn(n, DEC_IN[i], h, w, generator=g))
+    skip = q(torch.randn(n, DEC_SKIP[i], 2 * h, 2 * w, generator=g)) if DEC_SKIP[i] else None
+    return x, skip, q(torch.randn(n, DEC_OUT[i], 2 * h, 2 * w, generator=g))
+
+
+def _anchored(sd, prefix, inputs, gouts, run, dtype, mode, ref_cls=None):
+    """The f64 result of one case and the drift of the same restatement in f32 under torch.autocast("cpu", dtype) against it."""
+    training, k64, k16 = mode == "train", {}, {}
+    grads = stage_grads(sd, prefix, inputs, gouts, run, torch.float64, None, training, ref_cls, k64)
+    drift = stage_grads(sd, prefix, inputs, gouts, run, torch.float32, dtype, training, ref_cls, k16)
+    fbuf = [k for k in k64["buffers"] if not k.endswith("num_batches_tracked")]
+    return dict(sd=sd, inputs=inputs, gouts=gouts, out=k64["outs"][0], grads=grads, buffers=k64["buffers"],
+                anchor_out=rel_l2(k16["outs"][0], k64["outs"][0]), anchor_grads={k: rel_l2(drift[k], grads[k]) for k in grads},
+                anchor_buffers={k: rel_l2(k16["buffers"][k], k64["buffers"][k]) for k in fbuf})
+
+
+def decoder_block_reference(i, shape, dtype, mode, ref_cls=None):
+    """Block ``i`` alone: gradients of sum(out * gout) for x, skip and the block's six parameters, the output, the updated buffers."""
+    x, skip, gout = decoder_block_inputs(i, shape, dtype)
+    run = lambda ref, xs: [ref.decoder_block(xs["x"], xs["skip"], i)]
+    return _anchored(decoder_state(), f"decoder.blocks.{i}.", {"x": x, "skip": skip}, [gout], run, dtype, mode, ref_cls)
+
+
+def decoder_chain_inputs(dtype):
+    """The model's own smallest decoder shapes: a bottleneck of 512 x 2 x 2, four skips, an f32 output gradient [n, 1, 64, 64]."""
+    n, g = DEC_CHAIN_N, torch.Generator().manual_seed(4900)
+    q = lambda t: t.to(dtype).float()
+    inputs = {"x": q(torch.randn(n, DEC_IN[0], 2, 2, generator=g))}
+    for i in range(4):
+        inputs[f"skip{i}"] = q(torch.randn(n, DEC_SKIP[i], 4 << i, 4 << i, generator=g))
+    return inputs, torch.randn(n, 1, 64, 64, generator=g)
+
+
+def decoder_chain_reference(dtype, mode):
+    """The five blocks and the head: gradients for x, the four skips, every decoder.* parameter and head.0.*."""
+    inputs, gout = decoder_chain_inputs(dtype)
+    run = lambda ref, xs: [ref.decoder(xs["x"], [xs[f"skip{i}"] for i in range(4)] + [None])]
+    return _anchored(decoder_state(), ("decoder.", "head."), inputs, [gout], run, dtype, mode)
+
+
+# shared by the tests of one process: computed once per case, never modified
+decoder_block_case = functools.lru_cache(maxsize=None)(decoder_block_reference)
+decoder_chain_case = functools.lru_cache(maxsize=None)(decoder_chain_reference)
 
 
 # ---------------------------------------------------------------------------------------------

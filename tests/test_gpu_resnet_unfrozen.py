@@ -259,25 +259,7 @@ def test_fp16_five_steps_with_loss_scaling():
 BLOCKS = [("layer1", 0), ("layer2", 0), ("layer3", 0), ("layer4", 1)]          # identity residual, strided with downsample (one and two chunks)
 
 
-def stage_grads(sd, prefix, x, gouts, run, dtype, autocast):
-    """Gradients of sum(out_i * gout_i) with respect to x and every parameter under ``prefix``; ``run(ref, x)`` -> outputs."""
-    names = [k for k in sd if k.startswith(prefix) and not RC.is_buffer(k)]
-    leaves = {k: sd[k].detach().to(dtype).clone().requires_grad_(True) for k in names}
-    xl = x.detach().to(dtype).clone().requires_grad_(True)
-    ref = RC._Ref({**sd, **leaves}, True, dtype)
-    with (torch.autocast("cpu", dtype=autocast) if autocast is not None else contextlib.nullcontext()):
-        outs = run(ref, xl)
-    loss = sum((o.to(dtype) * g.to(dtype)).sum() for o, g in zip(outs, gouts))
-    grads = torch.autograd.grad(loss, [xl] + [leaves[k] for k in names], allow_unused=True)
-    return dict(zip(["x"] + names, grads))
-
-
-def report(what, got, want, anchor):
-    names = list(want)
-    bad, rows, med = per_tensor_grad_report(names, got, want, [float(want[k].norm()) for k in names], [anchor[k] for k in names])
-    print(f"[parity] {what}: median rel-L2 / anchor {med:.3f} (bound 1.25); (rel-L2 / bound): " +
-          "; ".join(f"{k.split('.', 3)[-1]} {rel:.4f}/{bound:.4f}" for _, k, rel, bound, _, z in rows if not z))
-    assert not bad, " | ".join(bad[:8])
+stage_grads, report = RC.stage_grads, RC.report          # shared with tests/test_gpu_resnet_decoder.py
 
 
 @pytest.mark.parametrize("block", BLOCKS, ids=lambda b: f"{b[0]}.{b[1]}")

@@ -212,3 +212,59 @@ def test_restatement_agrees_with_the_module_containers_on_the_cpu():
     assert set(grads) == {k for k in sd if RC.is_trainable(k)} and all(float(g.abs().max()) > 0 for g in grads.values())
     assert set(buffers) == {k for k in sd if RC.is_buffer(k) and not k.startswith("base_model.")}
     assert int(buffers["encoder.bn1.num_batches_tracked"]) == 4
+
+
+# ---------------------------------------------------------------------------------------------
+# the decoder cases of tests/test_gpu_resnet_decoder.py: their references and anchors, checked where no GPU is needed
+# ---------------------------------------------------------------------------------------------
+DEC_NAME = {torch.bfloat16: "bf16", torch.float16: "fp16"}
+
+
+def check_decoder_case(a, b, dtype, cap):
+    """``a``, ``b``: the same case computed twice.  The f64 reference is reproducible to f64 rounding and the anchors to well within
+    the margins they are used with (2.5 x and 1.25 x); every input is a value the 16-bit type holds; every tensor has a gradient;
+    and no anchor is so large that its bound would let an O(1) error pass -- a condition on the seeds, not a measurement."""
+    assert all(v is None or torch.equal(v.to(dtype).float(), v) for v in a["inputs"].values())
+    assert set(a["grads"]) == set(b["grads"]) and all(g is not None and bool(torch.isfinite(g).all()) and float(g.norm()) > 0 for g in a["grads"].values())
+    assert a["out"].dtype == torch.float64 and RC.rel_l2(b["out"], a["out"]) <= 1e-12
+    assert all(RC.rel_l2(b["grads"][k], a["grads"][k]) <= 1e-12 for k in a["grads"])
+    anchors = lambda r: {"out": r["anchor_out"], **r["anchor_grads"], **r["anchor_buffers"]}
+    aa, ab = anchors(a), anchors(b)
+    assert set(aa) == set(ab) and all(abs(aa[k] - ab[k]) <= 1e-3 * aa[k] for k in aa), "the autocast anchor is not reproducible"
+    assert all(0 <= v < 1 for v in aa.values())          # 0: a sum of 16-bit values in f32 (the last beta's gradient) can be exact
+    worst = max(a["anchor_grads"], key=a["anchor_grads"].get)
+    print(f"[anchor] worst per-tensor gradient anchor {a['anchor_grads'][worst]:.4f} ({worst}; cap {cap}), output anchor {a['anchor_out']:.6f}")
+    assert a["anchor_grads"][worst] <= cap, f"{worst}: anchor {a['anchor_grads'][worst]:.4f} > {cap}: choose another seed"
+    assert a["anchor_out"] <= 2e-2
+
+
+@pytest.mark.parametrize("mode", RC.DEC_MODES)
+@pytest.mark.parametrize("dtype", RC.DEC_DTYPES, ids=lambda d: DEC_NAME[d])
+@pytest.mark.parametrize("i", range(5))
+def test_decoder_block_references_and_anchors(i, dtype, mode):
+    for shape in RC.decoder_block_shapes(i):
+        a, b = RC.decoder_block_case(i, shape, dtype, mode), RC.decoder_block_reference(i, shape, dtype, mode)
+        assert len(a["grads"]) == 6 + (2 if RC.DEC_SKIP[i] else 1) and len(a["anchor_buffers"]) == (4 if mode == "train" else 0)
+        check_decoder_case(a, b, dtype, RC.DEC_ANCHOR_CAP)
+
+
+@pytest.mark.parametrize("mode", RC.DEC_MODES)
+@pytest.mark.parametrize("dtype", RC.DEC_DTYPES, ids=lambda d: DEC_NAME[d])
+def test_decoder_chain_reference_and_anchors(dtype, mode):
+    a, b = RC.decoder_chain_case(dtype, mode), RC.decoder_chain_reference(dtype, mode)
+    assert len(a["grads"]) == 5 + 30 + 2 and len(a["anchor_buffers"]) == (20 if mode == "train" else 0)
+    assert tuple(a["out"].shape) == (RC.DEC_CHAIN_N, 1, 64, 64)
+    check_decoder_case(a, b, dtype, RC.DEC_CHAIN_ANCHOR_CAP)
+
+
+def test_decoder_helpers_are_the_forward_of_the_restatement():
+    """``_Ref.forward`` goes through ``decoder`` / ``decoder_block``: the chain on given inputs is the blocks one by one and the head."""
+    inputs, _ = RC.decoder_chain_inputs(torch.bfloat16)
+    ref = RC._Ref(RC.decoder_state(), False, torch.float64)
+    x, skips = inputs["x"].double(), [inputs[f"skip{j}"].double() for j in range(4)] + [None]
+    a = x
+    for i, s in enumerate(skips):
+        a = ref.decoder_block(a, s, i)
+        assert tuple(a.shape) == (RC.DEC_CHAIN_N, RC.DEC_OUT[i], 4 << i, 4 << i)
+    p = ref.p
+    assert torch.equal(ref.decoder(x, skips), torch.nn.functional.conv2d(a, p["head.0.weight"], p["head.0.bias"], 1, 1))

@@ -718,14 +718,18 @@ class PretrainedTemporalUNet(nn.Module):
         gamma, beta, rm, rv, training, mom, eps = _bn_args(seq[1], pending)
         return ops.ConvBNReLU.apply(x0, x1, seq[0].weight, None, gamma, beta, rm, rv, tuple(c_valid), (0, 0), 1, training, mom, eps, False)
 
+    def _decoder_block(self, blk: DecoderBlock, x: Tensor, skip: Optional[Tensor], pending: list) -> Tensor:
+        """One DecoderBlock: ``x`` [n, h, w, cin] and ``skip`` [n, 2h, 2w, cskip] (None: the last block) -> [n, 2h, 2w, cout]."""
+        cin, cskip, cout = blk.channels
+        up = Upsample2.apply(x)
+        x = self._stage(blk.conv1, up, skip, (cin, cskip) if skip is not None else (cin,), pending)
+        return self._stage(blk.conv2, x, None, (cout,), pending)
+
     def _decode(self, x: Tensor, skips, pending: list) -> Tensor:
         """The five blocks of the decoder on ``x`` (the bottleneck, 16-bit NHWC) and ``skips`` (deepest first, None for the last block),
         then the head: f32 ``[n, out_channels, H, W]``."""
         for blk, skip in zip(self.decoder.blocks, skips):
-            cin, cskip, cout = blk.channels
-            up = Upsample2.apply(x)
-            x = self._stage(blk.conv1, up, skip, (cin, cskip) if skip is not None else (cin,), pending)
-            x = self._stage(blk.conv2, x, None, (cout,), pending)
+            x = self._decoder_block(blk, x, skip, pending)
         conv = self.head[0]
         return Head3x3.apply(x, conv.weight, conv.bias)
 
