@@ -359,8 +359,8 @@ def is_trainable(name: str) -> bool:
 
 
 def train_step(p: Params, x: Tensor, y: Tensor, mask: Optional[Tensor], use_mask: bool,
-               m: Optional[Params] = None, v: Optional[Params] = None, step: int = 1):
-    """zero_grad -> forward -> stack -> loss -> backward -> clip(1.0) -> AdamW, main.py:91-108.
+               m: Optional[Params] = None, v: Optional[Params] = None, step: int = 1, lr: float = 1e-3, wd: float = 1e-4):
+    """zero_grad -> forward -> stack -> loss -> backward -> clip(1.0) -> AdamW(lr, weight_decay=wd), main.py:91-108.
 
     Returns ``(loss, new_params_and_buffers, grads_before_clip, m, v, y_pred)``.
     """
@@ -377,7 +377,7 @@ def train_step(p: Params, x: Tensor, y: Tensor, mask: Optional[Tensor], use_mask
     if m is None:
         m = {k: torch.zeros_like(g) for k, g in grads.items()}
         v = {k: torch.zeros_like(g) for k, g in grads.items()}
-    new_p, m, v = adamw_step({k: leaves[k].detach() for k in names}, clipped, m, v, step)
+    new_p, m, v = adamw_step({k: leaves[k].detach() for k in names}, clipped, m, v, step, lr=lr, wd=wd)
     out = dict(p)
     out.update(new_p)
     out.update(buffers)

@@ -837,6 +837,15 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss, self.y_pred = train_step(model, optimizer, self.x, self.y, self.mask, use_mask, None, clip_norm)
+        # The graph owns what it captured.  Everything the capture allocated lives in the graph's own pool, and the model, the
+        # optimiser and the static inputs are held above; the look-ahead batch is the exception: its panels and its device job
+        # table were allocated by an eager step BEFORE the capture, their addresses are baked into the graph, and their only
+        # other owner is the module global ops._PACK_BATCH, which prepack_begin() replaces as soon as another plan comes along
+        # (an eager step of a second model, or of this one after a freeze).  Without this reference a later replay would read
+        # a freed job table and write freed panels.
+        self._pack_batch = ops._PACK_BATCH if (ops.PREPACK and ops.PACK_BATCHED) else None
+        if ops.PREPACK and ops.PACK_BATCHED and self._pack_batch is None:
+            raise ops.L.UclstmError("GraphedTrainStep: look-ahead packing is on but the capture used no batch (no pack call in the step?)")
         self.replays = 0
 
     def __call__(self, x, y, mask=None):
