@@ -351,3 +351,66 @@ def test_splitk_cases_are_what_they_claim():
     want = torch.relu((body.double().sum(0) + bias.double()) * scale.double() + shift.double())
     close(ref, want, "splitk_finish_ref")
     assert bool((mag >= ref.abs()).all())
+
+
+# ---------------------------------------------------------------------------------------------
+# ops.conv_pack_desc is the one builder of both models' convolutions: its fields against those of the two builders it replaced
+# (ops.conv_pack_desc for 9 taps, resnet.conv_desc for one source and any tap count), recorded from them as literals
+# ---------------------------------------------------------------------------------------------
+def _fields(d):
+    out = []
+    for name, _ in L.PackDesc._fields_:
+        v = getattr(d, name)
+        out += list(v) if hasattr(v, "__len__") else [v]
+    return tuple(out)
+
+
+CHOFF1 = 9          # choff[1] in _fields: the old builders disagreed for one source (0 / c_valid[0]); the kernels read it for two only
+# (Co, Ci, k) of every convolution of ResNet18 behind the stem, as resnet.conv_desc(Co, Ci, k, cpad(Ci)) built them
+RESNET18_DESCS = [
+    ((64, 64, 3), (64, 576, 9, 1, 64, 0, 64, 0, 0, 0, 0, 64, 0, 0, 0, 0, 0, 576, 9, 1, 0)),
+    ((128, 64, 3), (128, 576, 9, 1, 64, 0, 64, 0, 0, 0, 0, 128, 0, 0, 0, 0, 0, 576, 9, 1, 0)),
+    ((128, 128, 3), (128, 1152, 9, 1, 128, 0, 128, 0, 0, 0, 0, 128, 0, 0, 0, 0, 0, 1152, 9, 1, 0)),
+    ((128, 64, 1), (128, 64, 1, 1, 64, 0, 64, 0, 0, 0, 0, 128, 0, 0, 0, 0, 0, 64, 1, 1, 0)),
+    ((256, 128, 3), (256, 1152, 9, 1, 128, 0, 128, 0, 0, 0, 0, 256, 0, 0, 0, 0, 0, 1152, 9, 1, 0)),
+    ((256, 256, 3), (256, 2304, 9, 1, 256, 0, 256, 0, 0, 0, 0, 256, 0, 0, 0, 0, 0, 2304, 9, 1, 0)),
+    ((256, 128, 1), (256, 128, 1, 1, 128, 0, 128, 0, 0, 0, 0, 256, 0, 0, 0, 0, 0, 128, 1, 1, 0)),
+    ((512, 256, 3), (512, 2304, 9, 1, 256, 0, 256, 0, 0, 0, 0, 512, 0, 0, 0, 0, 0, 2304, 9, 1, 0)),
+    ((512, 512, 3), (512, 4608, 9, 1, 512, 0, 512, 0, 0, 0, 0, 512, 0, 0, 0, 0, 0, 4608, 9, 1, 0)),
+    ((512, 256, 1), (512, 256, 1, 1, 256, 0, 256, 0, 0, 0, 0, 512, 0, 0, 0, 0, 0, 256, 1, 1, 0)),
+]
+# (Co, valid channels per source) of the conv cases of pack_cases.CASES / test_gpu_pack.py, as the 9-tap ops.conv_pack_desc built them
+STAGE_DESCS = [
+    ((8, (255,)), (8, 2304, 9, 1, 256, 0, 255, 0, 0, 255, 0, 8, 0, 0, 0, 0, 0, 2295, 9, 1, 0)),
+    ((8, (256,)), (8, 2304, 9, 1, 256, 0, 256, 0, 0, 256, 0, 8, 0, 0, 0, 0, 0, 2304, 9, 1, 0)),
+    ((8, (257,)), (8, 2880, 9, 1, 320, 0, 257, 0, 0, 257, 0, 8, 0, 0, 0, 0, 0, 2313, 9, 1, 0)),
+    ((8, (264, 24)), (8, 3456, 9, 2, 320, 64, 264, 24, 0, 264, 0, 8, 0, 0, 0, 0, 0, 2592, 9, 1, 0)),
+    ((40, (24,)), (40, 576, 9, 1, 64, 0, 24, 0, 0, 24, 0, 40, 0, 0, 0, 0, 0, 216, 9, 1, 0)),
+    ((72, (56, 24)), (72, 1152, 9, 2, 64, 64, 56, 24, 0, 56, 0, 72, 0, 0, 0, 0, 0, 720, 9, 1, 0)),
+    ((64, (64,)), (64, 576, 9, 1, 64, 0, 64, 0, 0, 64, 0, 64, 0, 0, 0, 0, 0, 576, 9, 1, 0)),
+]
+
+
+def test_the_one_conv_descriptor_builder_equals_both_builders_it_replaced():
+    def same(got, want, what, one_source):
+        assert len(got) == len(want) == 21
+        for i, (g, w) in enumerate(zip(got, want)):
+            if i == CHOFF1 and one_source:
+                assert g == 0, f"{what}: choff[1] of a one-source descriptor is 0"
+                continue
+            assert g == w, f"{what}: field {i} of _fields is {g}, the replaced builder had {w}"
+
+    for (Co, Ci, k), want in RESNET18_DESCS:
+        same(_fields(ops.conv_pack_desc(Co, Ci, (Ci,), (ops.cpad(Ci),), k)), want, f"ResNet18 {Co} x {Ci} x {k} x {k}", True)
+    for (Co, cs), want in STAGE_DESCS:
+        same(_fields(ops.conv_pack_desc(Co, sum(cs), cs, [ops.cpad(c) for c in cs])), want, f"stage {Co} x {cs}", len(cs) == 1)
+    assert [(Co, cs) for (Co, cs), _ in STAGE_DESCS[:4]] == [(8, (255,)), (8, (256,)), (8, (257,)), (8, (264, 24))]
+    # and the descriptor the models get is this builder's: geometry of a 1x1 / stride 2 downsample convolution
+    import types
+    x, w = types.SimpleNamespace(shape=(2, 8, 8, 64)), types.SimpleNamespace(shape=(128, 64, 1, 1))
+    real, ops.SrcView = ops.SrcView, lambda t, *a: t
+    try:
+        pd, srcs, ktap, scale, pad, Ho, Wo = ops.conv_geometry(x, None, w, (64,), (0, 0), None, 2)
+    finally:
+        ops.SrcView = real
+    assert _fields(pd)[:CHOFF1] == RESNET18_DESCS[3][1][:CHOFF1] and (ktap, scale, pad, Ho, Wo) == (1, 2, 0, 4, 4) and srcs == [x]

@@ -331,18 +331,21 @@ def _fill_seg(sg: L.Seg, t: torch.Tensor, n_begin: int, n_end: int, c_off: int =
     sg.scale, sg.oy, sg.ox = scale, oy, ox
 
 
-def conv_pack_desc(Co: int, Ci_total: int, c_valid: Sequence[int], c_pad: Sequence[int]) -> L.PackDesc:
-    """Forward panel of a 3x3 conv whose input is the channel concat of the sources (train/unet.py:70,:98)."""
+def conv_pack_desc(Co: int, Ci_total: int, c_valid: Sequence[int], c_pad: Sequence[int], k: int = 3) -> L.PackDesc:
+    """Forward panel of a k x k conv whose input is the channel concat of the sources (train/unet.py:70,:98).  THE builder of both
+    models' convolutions: ``bytes(desc)`` is the key of the panel cache and of the look-ahead plan (pack_weights).  One source:
+    ``choff[1]`` is 0 as in every other one-source descriptor here (csrc/pack.hip reads it only for columns of source 1, and with
+    ``kseg[1] == 0`` there are none)."""
     d = L.PackDesc()
-    d.N, d.taps, d.nsrc = cpad(Co), 9, len(c_valid)
-    for i in range(2):
-        d.kseg[i] = kseg(c_pad[i]) if i < len(c_valid) else 0
-        d.cvalid[i] = c_valid[i] if i < len(c_valid) else 0
-    d.choff[0], d.choff[1] = 0, c_valid[0]
-    d.Ktot = 9 * (d.kseg[0] + d.kseg[1])
+    taps, two = k * k, len(c_valid) > 1
+    d.N, d.taps, d.nsrc = cpad(Co), taps, len(c_valid)
+    d.kseg[0], d.kseg[1] = kseg(c_pad[0]), (kseg(c_pad[1]) if two else 0)
+    d.cvalid[0], d.cvalid[1] = c_valid[0], (c_valid[1] if two else 0)
+    d.choff[0], d.choff[1] = 0, (c_valid[0] if two else 0)
+    d.Ktot = taps * (d.kseg[0] + d.kseg[1])
     d.n_mode, d.n_valid, d.n_cp = L.NMODE_IDENTITY, Co, 0
     d.k_mode, d.k_hdp, d.k_hd, d.tap_flip = L.KMODE_IDENTITY, 0, 0, 0
-    d.stride_n, d.stride_k, d.stride_tap, d.stride_ntap = Ci_total * 9, 9, 1, 0
+    d.stride_n, d.stride_k, d.stride_tap, d.stride_ntap = Ci_total * taps, taps, 1, 0
     return d
 
 
@@ -1382,15 +1385,19 @@ def _will_backward(ctx) -> bool:
     return _OUTER_GRAD and any(ctx.needs_input_grad)
 
 
-def _conv_geometry(x0, x1, weight, c_valid, off, im2col):
-    """(pack descriptor, sources, ktap, pad) of the stage's convolution, for the forward GEMM and the weight gradient alike:
-    the pre-gathered first layer as a plain GEMM, or 3x3 taps over one or two sources."""
-    Co, Ci_total = weight.shape[0], weight.shape[1]
-    if im2col:
-        return im2col_pack_desc(Co, Ci_total, x0.shape[3]), [SrcView(x0)], 1, 0
+def conv_geometry(x0, x1, weight, c_valid, off, im2col=None, stride: int = 1):
+    """(pack descriptor, sources, ktap, scale, pad, Ho, Wo) of a convolution in front of a BatchNorm, of either model, for the
+    forward GEMM and the weight gradient alike.  ``im2col``: ``x0`` is a pre-gathered first-layer matrix, a plain GEMM per pixel
+    whose panel descriptor ``im2col(Co, Ci, Kp)`` builds; otherwise k x k taps with pad k // 2 over the output grid and one or two
+    sources, stride 2 as ``scale = 2`` (k = 1: pad 0 on the same grid).  A plain tuple: the eager frame-by-frame path is host-bound."""
+    _, Hs, Ws, Cxp = x0.shape
+    Co, Ci_total, k = weight.shape[0], weight.shape[1], weight.shape[2]
+    if im2col is not None:
+        return im2col(Co, Ci_total, Cxp), [SrcView(x0)], 1, 1, 0, Hs, Ws
+    Ho, Wo = (Hs - 1) // stride + 1, (Ws - 1) // stride + 1
     if x1 is None:
-        return conv_pack_desc(Co, Ci_total, list(c_valid), [x0.shape[3]]), [SrcView(x0)], 3, 1
-    return conv_pack_desc(Co, Ci_total, list(c_valid), [x0.shape[3], x1.shape[3]]), [SrcView(x0), SrcView(x1, off[0], off[1])], 3, 1
+        return conv_pack_desc(Co, Ci_total, c_valid, (Cxp,), k), [SrcView(x0)], k, stride, k // 2, Ho, Wo
+    return conv_pack_desc(Co, Ci_total, c_valid, (Cxp, x1.shape[3]), k), [SrcView(x0), SrcView(x1, off[0], off[1])], k, stride, k // 2, Ho, Wo
 
 
 def _bn_forward_stats(stats, n_img, H, W, groups, Co, gamma, beta, running_mean, running_var, momentum, eps, variant):
@@ -1472,6 +1479,107 @@ def bn_param_grads(need_gamma: bool, need_beta: bool, gamma, beta, sums, Co: int
     return (tot[:Co, 1].contiguous() if need_gamma else None), (tot[:Co, 0].contiguous() if need_beta else None), False
 
 
+# The bodies under the autograd Functions of BOTH models -- ConvBNReLU here (TemporalUNetDualView, the decoder of
+# PretrainedTemporalUNet) and resnet.EncConv / resnet.BnRelu (its encoder, which also calls them without autograd): plain functions
+# on the tuple of conv_geometry and on ``bn`` = (gamma, beta, running mean, running variance, uses batch statistics, momentum
+# argument, eps).  The arithmetic of conv + BatchNorm + ReLU, forward and backward, is written here once.
+def conv_bn_stats(x0, weight, bias, geom, bn, groups: int = 1, variant: str = "plain"):
+    """(z, par, sync): the convolution's pre-BatchNorm output, (scale, shift, mean, rstd) [4, groups, Cop] -- of the batch, with the
+    running statistics updated, or (evaluation statistics with a backward pass; ``groups`` 1) of the running statistics -- and
+    _bn_forward_stats' marker that the statistics are those of all ranks, which the backward pass must get back."""
+    pd, srcs, ktap, scale, pad, Ho, Wo = geom
+    gamma, beta, rm, rv, training, mom, eps = bn
+    n, Co, dev = x0.shape[0], weight.shape[0], x0.device
+    Cop = cpad(Co)
+    wp = pack_weights(pd, weight, 0, x0.dtype)
+    bp = pack_bias(pd, bias) if bias is not None else None
+    z = torch.empty((n, Ho, Wo, Cop), dtype=x0.dtype, device=dev)
+    stats = None
+    if training:
+        stats = torch.empty((groups, L.lib.uclstm_igemm_tiles_per_group(n, Ho, Wo, groups, Cop), Cop, 2), dtype=F32, device=dev)
+    else:
+        join_forward_side(dev)
+    igemm_store(srcs, wp, (Ho, Wo), n, [(z, 0, Cop, 0, 1, 0, 0)], ktap=ktap, scale=scale, pad=pad, groups=groups, bias=bp, stats=stats)
+    par, sync = _bn_forward_stats(stats, n, Ho, Wo, groups, Co, gamma, beta, rm, rv, mom, eps, variant)
+    return z, par, sync
+
+
+def conv_bn_fold(x0, weight, bias, geom, bn, relu: bool) -> torch.Tensor:
+    """Evaluation statistics without a backward pass: ``bn(conv(x))`` (and ReLU) with BatchNorm's scale and shift in the GEMM's
+    epilogue -- one rounding to 16 bits, where ``conv_bn_stats`` + ``bn_relu`` make two."""
+    pd, srcs, ktap, scale, pad, Ho, Wo = geom
+    gamma, beta, rm, rv, _, mom, eps = bn
+    n, Co, dev = x0.shape[0], weight.shape[0], x0.device
+    Cop = cpad(Co)
+    wp = pack_weights(pd, weight, 0, x0.dtype)
+    bp = pack_bias(pd, bias) if bias is not None else None
+    out = torch.empty((n, Ho, Wo, Cop), dtype=x0.dtype, device=dev)
+    join_forward_side(dev)
+    par = _eval_bn_constants(gamma, beta, rm, rv, eps, mom, Co, Cop)
+    igemm_store(srcs, wp, (Ho, Wo), n, [(out, 0, Cop, 0, 1, 0, 0)], ktap=ktap, scale=scale, pad=pad, bias=bp, col_scale=par[0],
+                col_shift=par[1], relu=relu)
+    return out
+
+
+def bn_relu(z: torch.Tensor, par: torch.Tensor, groups: int = 1) -> torch.Tensor:
+    """``relu(z*scale + shift)`` with the constants ``par`` of ``conv_bn_stats``, per group of images."""
+    a = torch.empty_like(z)
+    Cp = z.shape[-1]
+    pixels = z.numel() // Cp
+    ppg = (z.shape[0] // groups) * (pixels // z.shape[0])
+    _timed_hbm("bn_apply_relu", 4.0 * z.numel(),        # 2 B read + 2 B written per element
+               lambda: L.check(_k(z).uclstm_bn_apply_relu(_p(z), _p(a), _p(par[0]), _p(par[1]), pixels, ppg, Cp, _stream()), "bn_apply_relu"))
+    return a
+
+
+def bn_relu_backward(z, par, da, groups: int, training: bool, sync, want_dz: bool = True, want_sums: bool = True, sums=None):
+    """(dz, sums) of ``bn_relu``: uclstm_bn_bwd_reduce for the per-group sums (sum g, sum g*xhat) [groups, Cp, 2] -- dbeta and
+    dgamma -- and uclstm_bn_bwd_apply for the gradient of the conv output; either is None, and its kernel not launched, where the
+    caller wants it not (batch statistics: ``dz`` needs the sums; ``sums``: those of an earlier call, for a caller that launches
+    something between the two kernels).  Training: dz = scale*(g - s1/n - xhat*s2/n), with the sums of all ranks where the forward
+    pass had their statistics (``sync`` of conv_bn_stats).  Evaluation-mode statistics are constants, the two mean terms vanish:
+    the same kernel with zero sums gives dz = scale*g (``sums`` itself still holds dbeta / dgamma)."""
+    Cp, dev = z.shape[-1], z.device
+    pixels = z.numel() // Cp
+    ppg = (z.shape[0] // groups) * (pixels // z.shape[0])
+    K, da = _k(z), da.contiguous()
+    pq = (_p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]))
+    dz = None
+    if want_sums:
+        sums = torch.empty((groups, Cp, 2), dtype=F32, device=dev)
+        partials = torch.empty((int(L.lib.uclstm_bn_bwd_reduce_rows(pixels, ppg)), Cp, 2), dtype=F32, device=dev)
+        _timed_hbm("bn_bwd_reduce", 4.0 * z.numel(),            # z and da read once
+                   lambda: L.check(K.uclstm_bn_bwd_reduce(_p(z), _p(da), *pq, _p(partials), _p(sums), pixels, ppg, Cp, _stream()),
+                                   "bn_bwd_reduce"))
+    if want_dz:
+        dz = torch.empty_like(z)
+        if sync is not None:
+            sums_dz = _bn_bwd_sums_over_ranks(sums, sync, "plain")
+        else:
+            sums_dz = sums if training else torch.zeros((groups, Cp, 2), dtype=F32, device=dev)
+        _timed_hbm("bn_bwd_apply", 6.0 * z.numel(),             # z, da read, dz written
+                   lambda: L.check(K.uclstm_bn_bwd_apply(_p(z), _p(da), *pq, _p(sums_dz), _p(dz), pixels, ppg, Cp, _stream()), "bn_bwd_apply"))
+    return dz, sums
+
+
+def conv_wgrad(weight, geom, dz):
+    """Weight gradient of the convolution of ``geom`` from the gradient ``dz`` of its output, through wgrad_into_param."""
+    pd, srcs, ktap, scale, pad, Ho, Wo = geom
+    n, Cop = dz.shape[0], dz.shape[3]
+    return wgrad_into_param(weight, pd, [s.t for s in srcs] + [dz],
+                            lambda: igemm_wgrad(srcs, [(dz, 0, Cop, 0, 1, 0, 0)], pd.N, pd.Ktot, (Ho, Wo), n, ktap=ktap, scale=scale, pad=pad))
+
+
+def conv3x3_dgrad(dz, weight, like, c_valid_s: int, elem_offset: int = 0, oy: int = 0, ox: int = 0) -> torch.Tensor:
+    """Input gradient of a conv3x3 / stride 1 / pad 1 for ONE source, shaped as ``like``: the source whose ``c_valid_s`` channels
+    start ``elem_offset`` f32 elements into ``weight`` and which was placed at (-oy, -ox) in the output frame."""
+    dd = conv_dgrad_pack_desc(weight.shape[0], weight.shape[1], c_valid_s)
+    wd = pack_weights(dd, weight, elem_offset, dz.dtype)
+    dx = torch.empty_like(like)
+    igemm_store([SrcView(dz)], wd, (dz.shape[1], dz.shape[2]), dz.shape[0], [(dx, 0, dd.N, 0, 1, oy, ox)], ktap=3, pad=1)
+    return dx
+
+
 class ConvBNReLU(_GradAwareFunction):
     """One (conv3x3 pad 1 + bias -> BatchNorm2d -> ReLU) stage on NHWC bf16.
 
@@ -1497,26 +1605,18 @@ class ConvBNReLU(_GradAwareFunction):
         # sizes, at most 256 channel chunks per pixel: uclstm_bn_pool_bwd_rows refuses more) or the plain ones
         variant = "head" if head_w is not None else \
             "pool" if (pool and training and H % 2 == 0 and W % 2 == 0 and Cop // 8 <= 256) else "plain"
-        pd, srcs, ktap, pad = _conv_geometry(x0, x1, weight, c_valid, off, im2col)
-        wp = pack_weights(pd, weight, 0, x0.dtype)
-        bp = pack_bias(pd, bias) if bias is not None else None
-        out = torch.empty((n_img, H, W, Cop), dtype=x0.dtype, device=dev)
+        geom = conv_geometry(x0, x1, weight, c_valid, off, im2col_pack_desc if im2col else None)
+        bn = (gamma, beta, running_mean, running_var, training, momentum, eps)
         K = _k(x0)
         need_bw = _will_backward(ctx)
         pooled = sync = None            # sync: (process group, world size) where this stage's statistics are those of all ranks
         if training or need_bw:
-            stats = None
-            if training:
-                stats = torch.empty((groups, L.lib.uclstm_igemm_tiles_per_group(n_img, H, W, groups, Cop), Cop, 2), dtype=F32, device=dev)
-            else:
+            if not training:
                 # evaluation-mode statistics WITH a backward pass (fine-tuning through frozen BatchNorm): keep the pre-BN conv
                 # output like the training path does, normalise with the running statistics as one group
-                join_forward_side(dev)
                 groups = 1
             pixels, ppg = n_img * H * W, (n_img // groups) * H * W
-            z = out
-            igemm_store(srcs, wp, (H, W), n_img, [(z, 0, Cop, 0, 1, 0, 0)], ktap=ktap, pad=pad, groups=groups, bias=bp, stats=stats)
-            par, sync = _bn_forward_stats(stats, n_img, H, W, groups, Co, gamma, beta, running_mean, running_var, momentum, eps, variant)
+            z, par, sync = conv_bn_stats(x0, weight, bias, geom, bn, groups, variant)
             if variant == "head":
                 a = torch.empty((n_img, 1, H, W), dtype=F32, device=dev)
                 _timed_hbm("bn_head_fwd", 2.0 * z.numel() + 4.0 * pixels,
@@ -1529,19 +1629,12 @@ class ConvBNReLU(_GradAwareFunction):
                            lambda: L.check(K.uclstm_bn_apply_relu_pool(_p(z), _p(a), _p(pooled), _p(par[0]), _p(par[1]), n_img, H, W, Cop,
                                                                        groups, _stream()), "bn_apply_relu_pool"))
             else:
-                a = torch.empty_like(z)
-                _timed_hbm("bn_apply_relu", 4.0 * z.numel(),        # 2 B read + 2 B written per element
-                           lambda: L.check(K.uclstm_bn_apply_relu(_p(z), _p(a), _p(par[0]), _p(par[1]), pixels, ppg, Cop, _stream()),
-                                           "bn_apply_relu"))
+                a = bn_relu(z, par, groups)
             ctx.save_for_backward(x0, x1, weight, z, par, gamma, beta, bias, head_w, head_b)
             if need_bw:
                 note_use(weight, gamma, beta, bias, head_w, head_b)
         else:
-            join_forward_side(dev)
-            par = _eval_bn_constants(gamma, beta, running_mean, running_var, eps, momentum, Co, Cop)
-            a = out
-            igemm_store(srcs, wp, (H, W), n_img, [(a, 0, Cop, 0, 1, 0, 0)], ktap=ktap, pad=pad, groups=1, bias=bp,
-                        col_scale=par[0], col_shift=par[1], relu=True)
+            a = conv_bn_fold(x0, weight, bias, geom, bn, True)
             ctx.save_for_backward(x0, x1, weight, None, None, gamma, beta, bias, None, None)
         ctx.cfg = (tuple(c_valid), tuple(off), groups, training, im2col, Co, Ci_total, bias is not None)
         ctx.variant, ctx.sync_bn, ctx.pool_act = variant, sync, None
@@ -1557,6 +1650,12 @@ class ConvBNReLU(_GradAwareFunction):
     def _bn_backward(ctx, z, par, head_w, head_b, da, dp):
         """Part 1: (dz, sums, d_head_w, d_head_b) -- the gradient of the conv output and the per-group sums (dbeta, dgamma)."""
         groups, training, Co = ctx.cfg[2], ctx.cfg[3], ctx.cfg[5]
+        variant = ctx.variant if (ctx.variant != "pool" or dp is not None) else "plain"          # pooled output unused
+        if variant == "plain":
+            if dp is not None:
+                # pooling not fused (odd sizes / evaluation-mode statistics path): the stand-alone max-pool backward kernel first
+                da = _maxpool2_bwd(ctx.pool_act, dp, da)
+            return bn_relu_backward(z, par, da, groups, training, ctx.sync_bn) + (None, None)
         (n_img, H, W, Cop), dev = z.shape, z.device
         pixels, ppg = n_img * H * W, (n_img // groups) * H * W
         sums = torch.empty((groups, Cop, 2), dtype=F32, device=dev)
@@ -1565,7 +1664,6 @@ class ConvBNReLU(_GradAwareFunction):
         dz = torch.empty_like(z)
         pz, pq = _p(z), (_p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]))
         d_head_w = d_head_b = None
-        variant = ctx.variant if (ctx.variant != "pool" or dp is not None) else "plain"          # pooled output unused
         if variant == "head":
             # fused output head: `da` is dy f32 [n_img, 1, H, W]; the activation gradient bf16(dy * w) is formed on the fly
             dy = _dev(da.contiguous().float(), F32, "dy")
@@ -1594,7 +1692,7 @@ class ConvBNReLU(_GradAwareFunction):
                 d_head_b = dbh if (head_b is not None and ctx.needs_input_grad[16]) else None
             kind, nbytes = "bn_head_bwd_apply", 4.0 * z.numel() + 4.0 * pixels
             apply = lambda s: K.uclstm_bn_head_bwd_apply(pz, _p(dy), *pq, _p(s), _p(head_w), _p(dz), pixels, ppg, Cop, Co, _stream())
-        elif variant == "pool":
+        else:
             # pooling fused: the gradient of the activation is (skip gradient) + scatter(dp), formed inside the BatchNorm kernels
             dsk = None if da is None else da.contiguous()
             dp = dp.contiguous()
@@ -1604,19 +1702,7 @@ class ConvBNReLU(_GradAwareFunction):
                                                                    _stream()), "bn_pool_bwd_reduce"))
             kind, nbytes = "bn_pool_bwd_apply", (6.5 if dsk is not None else 4.5) * z.numel()
             apply = lambda s: K.uclstm_bn_pool_bwd_apply(pz, _p(dsk), _p(dp), *pq, _p(s), _p(dz), n_img, H, W, Cop, groups, _stream())
-        else:
-            if dp is not None:
-                # pooling not fused (odd sizes / evaluation-mode statistics path): the stand-alone max-pool backward kernel first
-                da = _maxpool2_bwd(ctx.pool_act, dp, da)
-            da = da.contiguous()
-            _timed_hbm("bn_bwd_reduce", 4.0 * z.numel(),            # z and da read once
-                       lambda: L.check(K.uclstm_bn_bwd_reduce(pz, _p(da), *pq, _p(partials), _p(sums), pixels, ppg, Cop, _stream()),
-                                       "bn_bwd_reduce"))
-            kind, nbytes = "bn_bwd_apply", 6.0 * z.numel()          # z, da read, dz written
-            apply = lambda s: K.uclstm_bn_bwd_apply(pz, _p(da), *pq, _p(s), _p(dz), pixels, ppg, Cop, _stream())
-        # training: dz = scale*(g - s1/n - xhat*s2/n), with the sums of all ranks where the forward pass had their statistics.
-        # Evaluation-mode statistics are constants, the two mean terms vanish: the same kernel with zero sums gives dz = scale*g
-        # (sums itself still holds dbeta / dgamma)
+        # the sums the apply pass takes: as in bn_relu_backward
         if ctx.sync_bn is not None:
             sums_dz = _bn_bwd_sums_over_ranks(sums, ctx.sync_bn, variant)
         else:
@@ -1650,26 +1736,17 @@ class ConvBNReLU(_GradAwareFunction):
     @staticmethod
     def backward(ctx, da, dp=None):
         x0, x1, weight, z, par, gamma, beta, bias, head_w, head_b = ctx.saved_tensors
-        c_valid, off, _, _, im2col, Co, Ci_total, _ = ctx.cfg
-        n_img, H, W, Cop = z.shape
+        c_valid, off, _, _, im2col, _, _, _ = ctx.cfg
         dz, sums, d_head_w, d_head_b = ConvBNReLU._bn_backward(ctx, z, par, head_w, head_b, da, dp)
         dbias, dgamma, dbeta = ConvBNReLU._param_grads(ctx, dz, sums, gamma, beta, bias)
         # part 3: the weight gradient (not for a frozen weight) and the input gradients
         dweight = dx0 = dx1 = None
         if ctx.needs_input_grad[2]:
-            pd, srcs, ktap, pad = _conv_geometry(x0, x1, weight, c_valid, off, im2col)
-            dweight = wgrad_into_param(weight, pd, [x0, x1, dz], lambda: igemm_wgrad(srcs, [(dz, 0, Cop, 0, 1, 0, 0)], pd.N, pd.Ktot, (H, W),
-                                                                                     n_img, ktap=ktap, pad=pad))
+            dweight = conv_wgrad(weight, conv_geometry(x0, x1, weight, c_valid, off, im2col_pack_desc if im2col else None), dz)
         if ctx.needs_input_grad[0] and not im2col:
-            dd = conv_dgrad_pack_desc(Co, Ci_total, c_valid[0])
-            wd = pack_weights(dd, weight, 0, dz.dtype)
-            dx0 = torch.empty_like(x0)
-            igemm_store([SrcView(dz)], wd, (H, W), n_img, [(dx0, 0, dd.N, 0, 1, 0, 0)], ktap=3, pad=1)
+            dx0 = conv3x3_dgrad(dz, weight, x0, c_valid[0])
         if x1 is not None and ctx.needs_input_grad[1]:
-            dd = conv_dgrad_pack_desc(Co, Ci_total, c_valid[1])
-            wd = pack_weights(dd, weight, c_valid[0] * 9, dz.dtype)
-            dx1 = torch.empty_like(x1)
-            igemm_store([SrcView(dz)], wd, (H, W), n_img, [(dx1, 0, dd.N, 0, 1, -off[0], -off[1])], ktap=3, pad=1)
+            dx1 = conv3x3_dgrad(dz, weight, x1, c_valid[1], c_valid[0] * 9, -off[0], -off[1])
         return dx0, dx1, dweight, dbias, dgamma, dbeta, None, None, None, None, None, None, None, None, None, d_head_w, d_head_b, None
 
 
@@ -1788,41 +1865,54 @@ class OutConv1x1(_GradAwareFunction):
 
     @staticmethod
     def backward(ctx, dy):
-        a, weight, bias = ctx.saved_tensors
-        dy = dy.contiguous().float()
+        a, weight, _ = ctx.saved_tensors
         N, H, W, Cp = a.shape
-        Co, Ci = weight.shape[0], weight.shape[1]
-        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        if not (need_w or need_b):
-            # weight and bias frozen: the library skips the dw / db kernel when given no buffers for them
-            if da is not None:
-                L.check(_k(a).uclstm_outconv_bwd(_p(a), _p(weight), _p(dy), _p(da), None, None, N, H * W, Cp, Ci, Co, _stream()),
-                        "outconv_bwd")
-            return da, None, None
-        # the kernel ADDS its block sums into dw / db: with attached f32 gradients it adds straight into them (no zero-fill,
-        # no accumulate kernels); the weight is a view [Co, Ci] of the parameter [Co, Ci, 1, 1], so is its gradient
-        direct = direct_grad_pair(weight, bias, need_w, need_b)
-        gw, gb = direct or (None, None)
-        if _DETERMINISTIC:
-            dw = gw if direct else torch.empty((Co, Ci), dtype=F32, device=a.device)
-            db = gb if (direct and ctx.has_bias) else (torch.empty((Co,), dtype=F32, device=a.device) if need_b else None)
-            partials = torch.empty((int(L.lib.uclstm_outconv_bwd_ordered_rows(N, H * W)), Co * Ci + Co), dtype=F32, device=a.device)
-            _log_reduce("outconv_bwd_ordered")
-            L.check(L.lib.uclstm_outconv_bwd_ordered(_p(a), _p(weight), _p(dy), _p(da), _p(partials), _p(dw), _p(db), 1 if direct else 0,
-                                                     N, H * W, Cp, Ci, Co, L.act_type(a.dtype), _stream()), "outconv_bwd_ordered")
-        else:
-            dw = gw if direct else torch.zeros((Co, Ci), dtype=F32, device=a.device)
-            db = gb if (direct and ctx.has_bias) else torch.zeros((Co,), dtype=F32, device=a.device)
-            _log_reduce("outconv_bwd")
-            L.check(_k(a).uclstm_outconv_bwd(_p(a), _p(weight), _p(dy), _p(da), _p(dw), _p(db), N, H * W, Cp, Ci, Co, _stream()),
-                    "outconv_bwd")
-        if direct:
-            grad_written(weight)
-            if ctx.has_bias:
-                grad_written(bias)
-            return da, None, None
-        return da, (dw.view_as(weight) if need_w else None), (db if need_b else None)
+        # (the kernels take the parameter [Co, Ci, 1, 1] and its gradient as [Co, Ci])
+        return head_backward(ctx, dy, "outconv_bwd", _k(a).uclstm_outconv_bwd, L.lib.uclstm_outconv_bwd_ordered,
+                             (N, H * W, Cp, weight.shape[1], weight.shape[0]), lambda: L.lib.uclstm_outconv_bwd_ordered_rows(N, H * W),
+                             spare=True)
+
+
+def head_backward(ctx, dy, kind: str, atomic, ordered, geom: tuple, rows, *, spare: bool = False, timed: bool = False):
+    """Backward of an f32 output head that saved ``(a, weight, bias)`` and set ``ctx.has_bias`` (OutConv1x1, resnet.Head3x3):
+    ``(da, dweight, dbias)``.  ``atomic(a, weight, dy, da, dw, db, *geom, stream)`` ADDS its block sums into dw / db with float
+    atomics and skips them when given no buffers (weight and bias frozen); deterministic mode takes
+    ``ordered(a, weight, dy, da, partials, dw, db, accumulate, *geom, act type, stream)`` with ``rows()`` partial rows of
+    (weight elements + Co) columns.  With attached f32 gradients (direct_grad_pair) the kernels add straight into them: no
+    zero-fill, no accumulate kernels.  ``kind`` goes to _log_reduce (plus "_ordered").  ``spare``: the kernels get a scratch buffer
+    for the weight gradient always and (atomic form) for the bias gradient always, where otherwise a gradient nobody wants gets
+    none.  ``timed``: the launch is recorded in PROFILE_HBM as ``kind``."""
+    a, weight, bias = ctx.saved_tensors
+    dy = dy.contiguous().float()
+    Co, dev, det = weight.shape[0], a.device, _DETERMINISTIC
+    da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+    need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+    if not (need_w or need_b):
+        if da is not None:
+            L.check(atomic(_p(a), _p(weight), _p(dy), _p(da), None, None, *geom, _stream()), kind)
+        return da, None, None
+    direct = direct_grad_pair(weight, bias, need_w, need_b)
+    gw, gb = direct or (None, None)
+    fresh = torch.empty if det else torch.zeros          # the ordered form writes, the atomic form adds
+    dw = gw if direct else (fresh(weight.shape, dtype=F32, device=dev) if (need_w or spare) else None)
+    db = gb if (direct and ctx.has_bias) else (fresh((Co,), dtype=F32, device=dev) if (need_b or (spare and not det)) else None)
+    if det:
+        partials = torch.empty((int(rows()) * (weight.numel() + Co),), dtype=F32, device=dev)
+        launch = lambda: L.check(ordered(_p(a), _p(weight), _p(dy), _p(da), _p(partials), _p(dw), _p(db), 1 if direct else 0, *geom,
+                                         L.act_type(a.dtype), _stream()), kind + "_ordered")
+    else:
+        launch = lambda: L.check(atomic(_p(a), _p(weight), _p(dy), _p(da), _p(dw), _p(db), *geom, _stream()), kind)
+    _log_reduce(kind + "_ordered" if det else kind)
+    if timed:
+        _timed_hbm(kind, 2.0 * a.numel() * (2 if da is not None else 1) + 4.0 * dy.numel(), launch)
+    else:
+        launch()
+    if direct:
+        grad_written(weight)
+        if ctx.has_bias:
+            grad_written(bias)
+        return da, None, None
+    return da, (dw if need_w else None), (db if need_b else None)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -9,8 +9,9 @@ implicit-GEMM family for the convolutions (stride 2 is a descriptor with ``scale
 stages, this package's ``ConvLSTM`` for the recurrences and the kernels of ``csrc/resnet.hip`` around them.
 
 The encoder has ONE route (``_encode`` / ``_block`` / ``_conv_bn``), and every forward body is a plain function without autograd:
-``_conv_stats`` (convolution + BatchNorm constants), ``conv_bn_fold`` (evaluation statistics in the GEMM's epilogue), ``bn_relu``,
-``bn_add_relu``, ``maxpool3s2``, all on the one ``conv_geometry``.  A frozen stage calls them directly.  After
+those of ops.py that ``ops.ConvBNReLU`` runs on too -- ``ops.conv_bn_stats`` (convolution + BatchNorm constants), ``ops.conv_bn_fold``
+(evaluation statistics in the GEMM's epilogue), ``ops.bn_relu``, all on the one ``ops.conv_geometry`` -- and ``bn_add_relu``,
+``maxpool3s2`` here.  A frozen stage calls them directly.  After
 ``model.unfreeze_encoder(stages)`` the stages from the lowest trainable one up call them through the autograd Functions ``EncConv``,
 ``BnRelu``, ``BnAddRelu``, ``MaxPool3s2``, whose backward is the kernels of ``csrc/resnet_bwd.hip``, the stride-2 weight gradients as
 descriptors of the weight-gradient family over the OUTPUT grid, and the stride-2 input gradient as one launch of the forward family
@@ -122,20 +123,6 @@ def adapt_first_conv(w: Tensor) -> Tensor:
 # ---------------------------------------------------------------------------------------------
 # host wiring of csrc/resnet.hip
 # ---------------------------------------------------------------------------------------------
-def conv_desc(Co: int, Ci: int, k: int, c_pad: int) -> L.PackDesc:
-    """Forward panel of a k x k convolution over one source (ops.conv_pack_desc for any tap count)."""
-    d = L.PackDesc()
-    d.N, d.taps, d.nsrc = cpad(Co), k * k, 1
-    d.kseg[0], d.kseg[1] = kseg(c_pad), 0
-    d.cvalid[0], d.cvalid[1] = Ci, 0
-    d.choff[0] = d.choff[1] = 0
-    d.Ktot = k * k * d.kseg[0]
-    d.n_mode, d.n_valid, d.n_cp = L.NMODE_IDENTITY, Co, 0
-    d.k_mode, d.k_hdp, d.k_hd, d.tap_flip = L.KMODE_IDENTITY, 0, 0, 0
-    d.stride_n, d.stride_k, d.stride_tap, d.stride_ntap = Ci * k * k, k * k, 1, 0
-    return d
-
-
 def im2col7_pack_desc(Co: int, Ci: int, Kp: int) -> L.PackDesc:
     """Panel of the pre-gathered 7x7 first layer: K = (tap, ci), 49 taps (ops.im2col_pack_desc for the 3x3 one)."""
     d = ops.im2col_pack_desc(Co, Ci, Kp)
@@ -219,45 +206,11 @@ class Head3x3(ops._GradAwareFunction):
 
     @staticmethod
     def backward(ctx, dy):
-        a, weight, bias = ctx.saved_tensors
-        dy = dy.contiguous().float()
+        a, weight, _ = ctx.saved_tensors
         N, H, W, Cp = a.shape
-        Co, Ci = weight.shape[0], weight.shape[1]
-        dev = a.device
-        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        geom = (N, H, W, Cp, Ci, Co)
-        if not (need_w or need_b):
-            if da is not None:
-                L.check(ops._k(a).uclstm_head3x3_bwd(_p(a), _p(weight), _p(dy), _p(da), None, None, *geom, _stream()), "head3x3_bwd")
-            return da, None, None
-        # the kernels ADD into dw / db: with attached f32 gradients straight into them, as ops.OutConv1x1
-        direct = ops.direct_grad_pair(weight, bias, need_w, need_b)
-        gw, gb = direct or (None, None)
-        nbytes = 2.0 * a.numel() * (2 if da is not None else 1) + 4.0 * dy.numel()
-        if ops.is_deterministic():
-            dw = gw if direct else (torch.empty_like(weight, memory_format=torch.contiguous_format) if need_w else None)
-            db = gb if (direct and ctx.has_bias) else (torch.empty((Co,), dtype=F32, device=dev) if need_b else None)
-            rows = int(L.lib.uclstm_head3x3_bwd_ordered_rows(N, H, W))
-            partials = torch.empty((rows * (Co * Ci * 9 + Co),), dtype=F32, device=dev)
-            ops._log_reduce("head3x3_bwd_ordered")
-            ops._timed_hbm("head3x3_bwd", nbytes,
-                           lambda: L.check(L.lib.uclstm_head3x3_bwd_ordered(_p(a), _p(weight), _p(dy), _p(da), _p(partials), _p(dw), _p(db),
-                                                                            1 if direct else 0, *geom, L.act_type(a.dtype), _stream()),
-                                           "head3x3_bwd_ordered"))
-        else:
-            dw = gw if direct else (torch.zeros_like(weight, memory_format=torch.contiguous_format) if need_w else None)
-            db = gb if (direct and ctx.has_bias) else (torch.zeros((Co,), dtype=F32, device=dev) if need_b else None)
-            ops._log_reduce("head3x3_bwd")
-            ops._timed_hbm("head3x3_bwd", nbytes,
-                           lambda: L.check(ops._k(a).uclstm_head3x3_bwd(_p(a), _p(weight), _p(dy), _p(da), _p(dw), _p(db), *geom, _stream()),
-                                           "head3x3_bwd"))
-        if direct:
-            ops.grad_written(weight)
-            if ctx.has_bias:
-                ops.grad_written(bias)
-            return da, None, None
-        return da, (dw if need_w else None), (db if need_b else None)
+        return ops.head_backward(ctx, dy, "head3x3_bwd", ops._k(a).uclstm_head3x3_bwd, L.lib.uclstm_head3x3_bwd_ordered,
+                                 (N, H, W, Cp, weight.shape[1], weight.shape[0]), lambda: L.lib.uclstm_head3x3_bwd_ordered_rows(N, H, W),
+                                 timed=True)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -354,121 +307,58 @@ def _bn_args(bn: nn.BatchNorm2d, pending: list):
     return bn.weight, bn.bias, bn.running_mean, bn.running_var, training, mom, bn.eps
 
 
-def conv_geometry(x: Tensor, weight: Tensor, stride: int, im2col: bool):
-    """(pack descriptor, ktap, scale, pad, Ho, Wo) of a bias-free convolution of the encoder, for the forward GEMM and the weight
-    gradient alike.  ``im2col``: ``x`` is the pre-gathered 7x7 stem matrix, a plain GEMM per pixel; otherwise k x k taps with pad
-    k // 2 over the output grid, stride 2 as ``scale = 2`` (the 1x1 downsample convolution: k = 1, pad 0 on the same grid)."""
-    _, Hs, Ws, Cxp = x.shape
-    Co, Ci, k, s = weight.shape[0], weight.shape[1], weight.shape[2], stride
-    if im2col:
-        return im2col7_pack_desc(Co, Ci, Cxp), 1, 1, 0, Hs, Ws
-    return conv_desc(Co, Ci, k, Cxp), k, s, k // 2, (Hs - 1) // s + 1, (Ws - 1) // s + 1
-
-
-def _conv_stats(x: Tensor, weight: Tensor, geom, bn):
-    """(z, par): the convolution's pre-BatchNorm output and (scale, shift, mean, rstd) [4, 1, Cop] -- of the batch, with the running
-    statistics updated, or (evaluation statistics with a backward pass) of the running statistics."""
-    pd, k, s, pad, Ho, Wo = geom
-    gamma, beta, rm, rv, training, mom, eps = bn
-    n, Co, dev = x.shape[0], weight.shape[0], x.device
-    Cop = cpad(Co)
-    wp = ops.pack_weights(pd, weight, 0, x.dtype)
-    z = torch.empty((n, Ho, Wo, Cop), dtype=x.dtype, device=dev)
-    stats = None
-    if training:
-        stats = torch.empty((1, L.lib.uclstm_igemm_tiles_per_group(n, Ho, Wo, 1, Cop), Cop, 2), dtype=F32, device=dev)
-    else:
-        ops.join_forward_side(dev)
-    ops.igemm_store([SrcView(x)], wp, (Ho, Wo), n, [(z, 0, Cop, 0, 1, 0, 0)], ktap=k, scale=s, pad=pad, groups=1, stats=stats)
-    par, _ = ops._bn_forward_stats(stats, n, Ho, Wo, 1, Co, gamma, beta, rm, rv, mom, eps, "plain")
-    return z, par
-
-
-def conv_bn_fold(x: Tensor, weight: Tensor, geom, bn, relu: bool) -> Tensor:
-    """Evaluation statistics without a backward pass: ``bn(conv(x))`` (and ReLU) with BatchNorm's scale and shift in the GEMM's
-    epilogue -- one rounding to 16 bits, where ``_conv_stats`` + ``bn_relu`` make two."""
-    pd, k, s, pad, Ho, Wo = geom
-    gamma, beta, rm, rv, _, mom, eps = bn
-    n, Co, dev = x.shape[0], weight.shape[0], x.device
-    Cop = cpad(Co)
-    wp = ops.pack_weights(pd, weight, 0, x.dtype)
-    out = torch.empty((n, Ho, Wo, Cop), dtype=x.dtype, device=dev)
-    ops.join_forward_side(dev)
-    par = ops._eval_bn_constants(gamma, beta, rm, rv, eps, mom, Co, Cop)
-    ops.igemm_store([SrcView(x)], wp, (Ho, Wo), n, [(out, 0, Cop, 0, 1, 0, 0)], ktap=k, scale=s, pad=pad, col_scale=par[0], col_shift=par[1],
-                    relu=relu)
-    return out
-
-
 def _conv_bn_forward(x: Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, stride: int, pending: list, relu: bool, im2col: bool):
-    """A convolution that is not under autograd: (z, par), or (the finished activation, None) where BatchNorm (and ReLU if ``relu``)
-    went into the GEMM's epilogue -- exactly when this BatchNorm uses its running statistics."""
-    args, geom = _bn_args(bn, pending), conv_geometry(x, conv.weight, stride, im2col)
-    return _conv_stats(x, conv.weight, geom, args) if args[4] else (conv_bn_fold(x, conv.weight, geom, args, relu), None)
-
-
-def bn_relu(z: Tensor, par: Tensor) -> Tensor:
-    """``relu(z*scale + shift)`` with the constants ``par`` of ``_conv_stats``."""
-    a = torch.empty_like(z)
-    pixels, Cp = z.numel() // z.shape[-1], z.shape[-1]
-    ops._timed_hbm("bn_apply_relu", 4.0 * z.numel(),
-                   lambda: L.check(ops._k(z).uclstm_bn_apply_relu(_p(z), _p(a), _p(par[0]), _p(par[1]), pixels, pixels, Cp, _stream()),
-                                   "bn_apply_relu"))
-    return a
+    """A bias-free convolution of the encoder that is not under autograd, on the bodies of ops.py (``im2col``: ``x`` is the
+    pre-gathered 7x7 stem matrix): (z, par), or (the finished activation, None) where BatchNorm (and ReLU if ``relu``) went into the
+    GEMM's epilogue -- exactly when this BatchNorm uses its running statistics."""
+    w, args = conv.weight, _bn_args(bn, pending)
+    geom = ops.conv_geometry(x, None, w, (w.shape[1],), (0, 0), im2col7_pack_desc if im2col else None, stride)
+    if args[4]:
+        return ops.conv_bn_stats(x, w, None, geom, args)[:2]
+    return ops.conv_bn_fold(x, w, None, geom, args, relu), None
 
 
 class EncConv(ops._GradAwareFunction):
     """A bias-free convolution of the trainable encoder and its BatchNorm constants: ``(z, par, z_ds, par_ds)``, ``z`` the
     pre-BatchNorm output.  ``w_ds``: the conv1x1 / stride 2 of the same input (a strided BasicBlock), so that the block's input
     gradient is ONE launch (conv_s2_dgrad).  ``im2col``: ``x`` is the pre-gathered 7x7 stem matrix, which gets no gradient.
-    Backward: weight gradients over the OUTPUT grid (ktap k, scale = stride), through ops.wgrad_into_param."""
+    Forward and backward on the bodies of ops.py (ops.conv_bn_stats, ops.conv_wgrad -- weight gradients over the OUTPUT grid:
+    ktap k, scale = stride -- and ops.conv3x3_dgrad).  The ``sync`` marker of conv_bn_stats is dropped here and BnRelu / BnAddRelu
+    differentiate with this rank's sums: sync_batchnorm is not supported with a trainable encoder."""
+
+    @staticmethod
+    def _geometry(x, w, stride, im2col):
+        return ops.conv_geometry(x, None, w, (w.shape[1],), (0, 0), im2col7_pack_desc if im2col else None, stride)
 
     @staticmethod
     def forward(ctx, x, weight, w_ds, bn, bn_ds, stride, im2col):
         ops._dev(x, ops.ACT, "activation")
-        g = conv_geometry(x, weight, stride, im2col)
-        if g[2] == 2 and (x.shape[1] % 2 or x.shape[2] % 2):          # scale 2: conv_s2_dgrad writes a (2 Ho, 2 Wo) input
+        if stride == 2 and not im2col and (x.shape[1] % 2 or x.shape[2] % 2):          # conv_s2_dgrad writes a (2 Ho, 2 Wo) input
             raise UclstmError("EncConv: a stride-2 convolution with a backward pass needs even input sizes")
-        z, par = _conv_stats(x, weight, g, bn)
-        g_ds = z_ds = par_ds = None
+        z, par, _ = ops.conv_bn_stats(x, weight, None, EncConv._geometry(x, weight, stride, im2col), bn)
+        z_ds = par_ds = None
         if w_ds is not None:
-            g_ds = conv_geometry(x, w_ds, stride, False)
-            z_ds, par_ds = _conv_stats(x, w_ds, g_ds, bn_ds)
+            z_ds, par_ds, _ = ops.conv_bn_stats(x, w_ds, None, EncConv._geometry(x, w_ds, stride, False), bn_ds)
         ctx.mark_non_differentiable(*[t for t in (par, par_ds) if t is not None])
         ctx.save_for_backward(x, weight, w_ds)
-        ctx.geom = (g, g_ds, im2col)
+        ctx.cfg = (stride, im2col)
         if ops._will_backward(ctx):
             ops.note_use(weight, w_ds)
         return z, par, z_ds, par_ds
 
     @staticmethod
-    def _wgrad(x, weight, dz, geom):
-        pd, k, s, pad, Ho, Wo = geom
-        n, Cop = x.shape[0], dz.shape[3]
-        return ops.wgrad_into_param(weight, pd, [x, dz], lambda: ops.igemm_wgrad([SrcView(x)], [(dz, 0, Cop, 0, 1, 0, 0)], pd.N, pd.Ktot,
-                                                                                 (Ho, Wo), n, ktap=k, scale=s, pad=pad))
-
-    @staticmethod
     def backward(ctx, dz, _dpar, dz_ds, _dpar_ds):
         x, weight, w_ds = ctx.saved_tensors
-        g, g_ds, im2col = ctx.geom
-        _, _, scale, _, Ho, Wo = g
+        stride, im2col = ctx.cfg
         dz = dz.contiguous()
         dz_ds = None if (dz_ds is None or w_ds is None) else dz_ds.contiguous()
         dweight = dw_ds = dx = None
         if ctx.needs_input_grad[1]:
-            dweight = EncConv._wgrad(x, weight, dz, g)
+            dweight = ops.conv_wgrad(weight, EncConv._geometry(x, weight, stride, im2col), dz)
         if dz_ds is not None and ctx.needs_input_grad[2]:
-            dw_ds = EncConv._wgrad(x, w_ds, dz_ds, g_ds)
+            dw_ds = ops.conv_wgrad(w_ds, EncConv._geometry(x, w_ds, stride, False), dz_ds)
         if ctx.needs_input_grad[0] and not im2col:
-            if scale == 2:
-                dx = conv_s2_dgrad(dz, weight, dz_ds, w_ds)
-            else:
-                Co, Ci = weight.shape[0], weight.shape[1]
-                dd = ops.conv_dgrad_pack_desc(Co, Ci, Ci)
-                wd = ops.pack_weights(dd, weight, 0, dz.dtype)
-                dx = torch.empty_like(x)
-                ops.igemm_store([SrcView(dz)], wd, (Ho, Wo), x.shape[0], [(dx, 0, dd.N, 0, 1, 0, 0)], ktap=3, pad=1)
+            dx = conv_s2_dgrad(dz, weight, dz_ds, w_ds) if stride == 2 else ops.conv3x3_dgrad(dz, weight, x, weight.shape[1])
         return dx, dweight, dw_ds, None, None, None, None
 
 
@@ -478,7 +368,7 @@ class BnRelu(ops._GradAwareFunction):
 
     @staticmethod
     def forward(ctx, z, par, gamma, beta, training):
-        a = bn_relu(z, par)
+        a = ops.bn_relu(z, par)
         ctx.save_for_backward(z, par, gamma, beta)
         ctx.training = training
         if ops._will_backward(ctx):
@@ -489,24 +379,14 @@ class BnRelu(ops._GradAwareFunction):
     def backward(ctx, da):
         z, par, gamma, beta = ctx.saved_tensors
         need_z, _, need_gamma, need_beta, _ = ctx.needs_input_grad
-        pixels, Cp, dev = z.numel() // z.shape[-1], z.shape[-1], z.device
-        K, da = ops._k(z), da.contiguous()
-        pq = (_p(par[0]), _p(par[1]), _p(par[2]), _p(par[3]))
-        sums = None
+        # ops.bn_relu_backward, one kernel per call: no reduction where the statistics are frozen and neither gamma nor beta wants a
+        # gradient, the parameter gradients launched between the two kernels, no apply pass where z needs no gradient
+        sums = dz = None
         if ctx.training or need_gamma or need_beta:
-            sums = torch.empty((1, Cp, 2), dtype=F32, device=dev)
-            partials = torch.empty((int(L.lib.uclstm_bn_bwd_reduce_rows(pixels, pixels)), Cp, 2), dtype=F32, device=dev)
-            ops._timed_hbm("bn_bwd_reduce", 4.0 * z.numel(),
-                           lambda: L.check(K.uclstm_bn_bwd_reduce(_p(z), _p(da), *pq, _p(partials), _p(sums), pixels, pixels, Cp, _stream()),
-                                           "bn_bwd_reduce"))
+            _, sums = ops.bn_relu_backward(z, par, da, 1, ctx.training, None, want_dz=False)
         dgamma, dbeta, _ = ops.bn_param_grads(need_gamma, need_beta, gamma, beta, sums, gamma.shape[0])
-        dz = None
         if need_z:
-            dz = torch.empty_like(z)
-            sums_dz = sums if ctx.training else torch.zeros((1, Cp, 2), dtype=F32, device=dev)
-            ops._timed_hbm("bn_bwd_apply", 6.0 * z.numel(),
-                           lambda: L.check(K.uclstm_bn_bwd_apply(_p(z), _p(da), *pq, _p(sums_dz), _p(dz), pixels, pixels, Cp, _stream()),
-                                           "bn_bwd_apply"))
+            dz, _ = ops.bn_relu_backward(z, par, da, 1, ctx.training, None, want_sums=False, sums=sums)
         return dz, None, dgamma, dbeta, None
 
 
@@ -670,7 +550,7 @@ class PretrainedTemporalUNet(nn.Module):
     def _bn_relu(z: Tensor, par: Optional[Tensor], bn: nn.BatchNorm2d, grad: bool) -> Tensor:
         if par is None:
             return z
-        return BnRelu.apply(z, par, bn.weight, bn.bias, bn_mode(bn, bn.training)[0]) if grad else bn_relu(z, par)
+        return BnRelu.apply(z, par, bn.weight, bn.bias, bn_mode(bn, bn.training)[0]) if grad else ops.bn_relu(z, par)
 
     def _block(self, x: Tensor, blk: BasicBlock, pending: list, grad: bool) -> Tensor:
         ds = blk.downsample
