@@ -497,6 +497,38 @@ int32_t uclstm_loss_fwd_ordered(const float* y_pred, const float* y, const float
 int32_t uclstm_loss_bwd(const float* y_pred, const float* y, const float* mask, const float* coefs,
                         float* grad, int64_t planes, int32_t H, int32_t W, void* stream);
 
+/* The same loss with its point term and its weight as parameters (LossSpec).  With d = y_pred - y:
+ *   rho(d)  = |d| (L1) / d^2 (L2) / Huber: 0.5 d^2 where |d| <= delta, else delta (|d| - 0.5 delta)
+ *   rho'(d) = sign(d), sign(0) = 0 / 2 d / clamp(d, -delta, delta)
+ *   w       = 1 + weight_gain * |y|^weight_power, the power by repeated multiplication
+ * The gradient term is the one above (L1 on the forward differences of the cropped (H-1) x (W-1) cells, the mask at the cell);
+ * with grad_term == 0 it does not exist: no neighbour is read, sums[2] and sums[3] are stored as 0 and coefs[1] is not used.
+ * The struct lives in HOST memory and is read at launch; the weight of the gradient term and the epsilon of the denominators
+ * stay with the caller (they enter through the denominators and coefs, as above).  f32 planes only: no _f16 twin.
+ * UCLSTM_E_BADARG before any launch: NULL spec / inputs / outputs / coefs, point or weight_power out of range, Huber with
+ * delta <= 0 or not finite, weight_gain negative or not finite, sizes <= 0, planes*H*W >= 2^31. */
+#define UCLSTM_LOSS_POINT_L1 0
+#define UCLSTM_LOSS_POINT_L2 1
+#define UCLSTM_LOSS_POINT_HUBER 2
+typedef struct uclstm_loss_spec {
+    int32_t point;         /* UCLSTM_LOSS_POINT_* */
+    int32_t weight_power;  /* 1 .. 4 */
+    float delta;           /* Huber threshold; ignored by L1 and L2 */
+    float weight_gain;     /* >= 0 */
+    int32_t grad_term;     /* 0: no gradient term */
+    int32_t reserved[3];   /* 0 */
+} uclstm_loss_spec;
+/* sums[0..3] = sum(rho*w*m), sum(w*m), sum(gd*mc), sum(mc) as uclstm_loss_fwd: f64 atomics, caller zeroes sums. */
+int32_t uclstm_loss_spec_fwd(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask, double* sums,
+                             int64_t planes, int32_t H, int32_t W, void* stream);
+/* Ordered form: partials f64 [uclstm_loss_fwd_ordered_rows][4] and sums as uclstm_loss_fwd_ordered; nobody zeroes anything. */
+int32_t uclstm_loss_spec_fwd_ordered(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                     double* partials, double* sums, int32_t accumulate, int64_t planes, int32_t H, int32_t W,
+                                     void* stream);
+/* grad = coefs[0] * rho'(d) * w * m + coefs[1] * d(sum gd*mc)/dy_pred; coefs is a DEVICE f32[2] as for uclstm_loss_bwd. */
+int32_t uclstm_loss_spec_bwd(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                             const float* coefs, float* grad, int64_t planes, int32_t H, int32_t W, void* stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* Optimiser (main.py:106-108): global-norm clip + AdamW on flat f32 buffers            */
 /* ------------------------------------------------------------------------------------ */

@@ -102,6 +102,13 @@ class EvalDesc(C.Structure):
                 ("seed", C.c_uint64), ("K", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class LossSpecDesc(C.Structure):
+    """uclstm_loss_spec: host memory, read at launch (grad_weight and eps of loss.LossSpec stay on the host side)."""
+    _fields_ = [("point", C.c_int32), ("weight_power", C.c_int32), ("delta", C.c_float), ("weight_gain", C.c_float),
+                ("grad_term", C.c_int32), ("reserved_", C.c_int32 * 3)]
+
+
+LOSS_POINT_L1, LOSS_POINT_L2, LOSS_POINT_HUBER = 0, 1, 2
 EVAL_ROW = 16
 EVAL_NONE, EVAL_ASINH, EVAL_SIGNED_LOG = 0, 1, 2
 
@@ -187,6 +194,9 @@ _PROTOS = {
     "uclstm_loss_fwd_ordered_rows": [_L, _I, _I],
     "uclstm_loss_fwd_ordered": [_P, _P, _P, _P, _P, _I, _L, _I, _I, _P],
     "uclstm_loss_bwd": [_P, _P, _P, _P, _P, _L, _I, _I, _P],
+    "uclstm_loss_spec_fwd": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _L, _I, _I, _P],
+    "uclstm_loss_spec_fwd_ordered": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _P, _I, _L, _I, _I, _P],
+    "uclstm_loss_spec_bwd": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _P, _L, _I, _I, _P],
     "uclstm_sumsq": [_P, _L, _P, _P],
     "uclstm_sumsq_ordered_rows": [_L],
     "uclstm_sumsq_ordered": [_P, _L, _P, _P, _I, _P],

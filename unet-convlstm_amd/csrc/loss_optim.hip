@@ -3,6 +3,9 @@
 // three reductions (deterministic mode), one stored row of block totals per block and a second launch that adds the rows in order.
 #include "common.h"
 
+#include <cfloat>
+#include <type_traits>
+
 namespace {
 
 constexpr int NT = 256;
@@ -698,6 +701,270 @@ extern "C" int32_t uclstm_ordered_sum_f64(const double* partials, int32_t rows, 
     if (!partials || !out || rows <= 0 || cols <= 0) return UCLSTM_E_BADARG;
     UCLSTM_LAUNCH(ordered_sum_f64_kernel, dim3((cols + 63) / 64), dim3(64), 0, (hipStream_t)stream, partials, rows, cols, out, accumulate);
     return UCLSTM_OK;
+}
+
+// ---- the loss with its point term and weight as parameters (uclstm_loss_spec) ----
+// The kernels above with the spec as template parameters: POINT (L1 / L2 / Huber), POWER of the weight (1..4), GRAD (the gradient
+// term exists) and V, the elements one thread takes from a row (4 with 16-byte loads when the row length allows, else 1).  The
+// host picks the instance, so no element branches on the spec.  Without the gradient term the planes are one flat array.
+namespace {
+
+constexpr int SPEC_GRID_CAP_V4 = 512;           // blocks of the V = 4 instances (fwd atomic form and bwd): 16 bytes per stream and thread
+
+template <int V>
+__device__ __forceinline__ void load_v(const float* __restrict__ p, float (&o)[V]) {
+    if constexpr (V == 4) {
+        const float4 t = *(const float4*)p;
+        o[0] = t.x, o[1] = t.y, o[2] = t.z, o[3] = t.w;
+    } else {
+        o[0] = *p;
+    }
+}
+
+template <int POWER>
+__device__ __forceinline__ float spec_weight(float b, float gain) {
+    const float ab = fabsf(b);
+    if constexpr (POWER == 1) return 1.f + gain * ab;
+    else if constexpr (POWER == 2) return 1.f + gain * ab * ab;
+    else if constexpr (POWER == 3) return 1.f + gain * ab * ab * ab;          // main.py:38 at gain 4
+    else return 1.f + gain * ab * ab * ab * ab;
+}
+
+template <int POINT>
+__device__ __forceinline__ float spec_rho(float d, float delta) {
+    if constexpr (POINT == UCLSTM_LOSS_POINT_L1) return fabsf(d);
+    else if constexpr (POINT == UCLSTM_LOSS_POINT_L2) return d * d;
+    else {
+        const float ad = fabsf(d);
+        return ad <= delta ? 0.5f * d * d : delta * (ad - 0.5f * delta);
+    }
+}
+
+template <int POINT>
+__device__ __forceinline__ float spec_drho(float d, float delta) {
+    if constexpr (POINT == UCLSTM_LOSS_POINT_L1) return sgn(d);
+    else if constexpr (POINT == UCLSTM_LOSS_POINT_L2) return 2.f * d;
+    else return fminf(fmaxf(d, -delta), delta);
+}
+
+// items = total / V groups of V elements of one row; dHW / dW divide by the groups of a plane / of a row (GRAD only).
+// sums as loss_fwd_kernel; without GRAD columns 2 and 3 are the zeros acc starts with.
+template <int POINT, int POWER, bool GRAD, bool ORDERED, int V>
+__global__ void loss_spec_fwd_kernel(const float* __restrict__ yp, const float* __restrict__ y, const float* __restrict__ mask,
+                                     double* __restrict__ sums, int64_t items, FastDiv dHW, FastDiv dW, int H, int W, float delta,
+                                     float gain) {
+    __shared__ double red[16];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t it = (int64_t)blockIdx.x * NT + threadIdx.x; it < items; it += (int64_t)gridDim.x * NT) {
+        const int64_t idx = it * V;
+        float a[V], b[V], m[V];
+        load_v<V>(yp + idx, a);
+        load_v<V>(y + idx, b);
+        if (mask) load_v<V>(mask + idx, m);
+        else
+#pragma unroll
+            for (int u = 0; u < V; ++u) m[u] = 1.f;
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+            const float w = spec_weight<POWER>(b[u], gain);
+            acc[0] += (double)(spec_rho<POINT>(a[u] - b[u], delta) * w * m[u]);
+            acc[1] += (double)(w * m[u]);
+        }
+        if constexpr (GRAD) {
+            const uint32_t pl = fdiv((uint32_t)it, dHW);
+            const uint32_t pix = (uint32_t)it - pl * dHW.d;
+            const int i = (int)fdiv(pix, dW);
+            const int j = ((int)pix - i * (int)dW.d) * V;
+            if (i < H - 1) {                                     // main.py:57-62 crop
+                float an[V], bn[V];
+                load_v<V>(yp + idx + W, an);
+                load_v<V>(y + idx + W, bn);
+                const bool has_r = j + V < W;                    // the group's last element has a right neighbour
+                const float ar = has_r ? yp[idx + V] : 0.f, br = has_r ? y[idx + V] : 0.f;
+#pragma unroll
+                for (int u = 0; u < V; ++u) {
+                    if (u < V - 1 || has_r) {
+                        const float axr = (u < V - 1) ? a[(u + 1) % V] : ar, bxr = (u < V - 1) ? b[(u + 1) % V] : br;
+                        const float dxp = axr - a[u], dyp = an[u] - a[u];
+                        const float dxg = bxr - b[u], dyg = bn[u] - b[u];
+                        acc[2] += (double)((fabsf(dxp - dxg) + fabsf(dyp - dyg)) * m[u]);
+                        acc[3] += (double)m[u];
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (ORDERED) {
+        block_sum_store<4>(acc, red, sums + (int64_t)blockIdx.x * 4);
+    } else {
+        block_sum<4>(acc, red);
+        if (threadIdx.x == 0)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) atomicAdd(sums + k, acc[k]);
+    }
+}
+
+template <int POINT, int POWER, bool GRAD, int V>
+__global__ void loss_spec_bwd_kernel(const float* __restrict__ yp, const float* __restrict__ y, const float* __restrict__ mask,
+                                     const float* __restrict__ coefs, float* __restrict__ grad, int64_t items, FastDiv dHW, FastDiv dW,
+                                     int H, int W, float delta, float gain) {
+    const float c1 = coefs[0];
+    float c2 = 0.f;
+    if constexpr (GRAD) c2 = coefs[1];
+    for (int64_t it = (int64_t)blockIdx.x * NT + threadIdx.x; it < items; it += (int64_t)gridDim.x * NT) {
+        const int64_t idx = it * V;
+        float a[V], b[V], m[V], g[V];
+        load_v<V>(yp + idx, a);
+        load_v<V>(y + idx, b);
+        if (mask) load_v<V>(mask + idx, m);
+        else
+#pragma unroll
+            for (int u = 0; u < V; ++u) m[u] = 1.f;
+#pragma unroll
+        for (int u = 0; u < V; ++u) g[u] = c1 * spec_drho<POINT>(a[u] - b[u], delta) * spec_weight<POWER>(b[u], gain) * m[u];
+        if constexpr (GRAD) {
+            const uint32_t pl = fdiv((uint32_t)it, dHW);
+            const uint32_t pix = (uint32_t)it - pl * dHW.d;
+            const int i = (int)fdiv(pix, dW);
+            const int j = ((int)pix - i * (int)dW.d) * V;
+            float gg[V];
+#pragma unroll
+            for (int u = 0; u < V; ++u) gg[u] = 0.f;
+            if (i < H - 1) {
+                // cell (i,j) itself: -sx(i,j) - sy(i,j)
+                float an[V], bn[V];
+                load_v<V>(yp + idx + W, an);
+                load_v<V>(y + idx + W, bn);
+                const bool has_r = j + V < W;
+                const float ar = has_r ? yp[idx + V] : 0.f, br = has_r ? y[idx + V] : 0.f;
+#pragma unroll
+                for (int u = 0; u < V; ++u) {
+                    if (u < V - 1 || has_r) {
+                        const float axr = (u < V - 1) ? a[(u + 1) % V] : ar, bxr = (u < V - 1) ? b[(u + 1) % V] : br;
+                        const float sx = sgn((axr - a[u]) - (bxr - b[u]));
+                        const float sy = sgn((an[u] - a[u]) - (bn[u] - b[u]));
+                        gg[u] -= (sx + sy) * m[u];
+                    }
+                }
+                // cell (i,j-1): +sx(i,j-1)
+                const bool has_l = j >= 1;
+                const float al = has_l ? yp[idx - 1] : 0.f, bl = has_l ? y[idx - 1] : 0.f;
+                const float ml = (has_l && mask) ? mask[idx - 1] : 1.f;
+#pragma unroll
+                for (int u = 0; u < V; ++u) {
+                    if (u > 0 || has_l) {
+                        const float axl = (u > 0) ? a[(u + V - 1) % V] : al, bxl = (u > 0) ? b[(u + V - 1) % V] : bl;
+                        const float mxl = (u > 0) ? m[(u + V - 1) % V] : ml;
+                        gg[u] += sgn((a[u] - axl) - (b[u] - bxl)) * mxl;
+                    }
+                }
+            }
+            // cell (i-1,j): +sy(i-1,j)
+            if (i >= 1) {
+                float au[V], bu[V], mu[V];
+                load_v<V>(yp + idx - W, au);
+                load_v<V>(y + idx - W, bu);
+                if (mask) load_v<V>(mask + idx - W, mu);
+                else
+#pragma unroll
+                    for (int u = 0; u < V; ++u) mu[u] = 1.f;
+#pragma unroll
+                for (int u = 0; u < V; ++u)
+                    if (j + u < W - 1) gg[u] += sgn((a[u] - au[u]) - (b[u] - bu[u])) * mu[u];
+            }
+#pragma unroll
+            for (int u = 0; u < V; ++u) g[u] += c2 * gg[u];
+        }
+        if constexpr (V == 4) *(float4*)(grad + idx) = make_float4(g[0], g[1], g[2], g[3]);
+        else grad[idx] = g[0];
+    }
+}
+
+bool loss_spec_ok(const uclstm_loss_spec* s) {
+    if (!s || s->point < UCLSTM_LOSS_POINT_L1 || s->point > UCLSTM_LOSS_POINT_HUBER || s->weight_power < 1 || s->weight_power > 4)
+        return false;
+    if (s->point == UCLSTM_LOSS_POINT_HUBER && !(s->delta > 0.f && s->delta <= FLT_MAX)) return false;
+    return s->weight_gain >= 0.f && s->weight_gain <= FLT_MAX;               // false for NaN as well
+}
+
+// Calls f(point, power, grad, v) with integral constants for the spec's instance.
+template <typename T, T X>
+using ic = std::integral_constant<T, X>;
+template <typename F>
+int32_t loss_spec_dispatch(const uclstm_loss_spec* s, bool vec, F&& f) {
+    auto on_v = [&](auto point, auto power, auto grad) { return vec ? f(point, power, grad, ic<int, 4>{}) : f(point, power, grad, ic<int, 1>{}); };
+    auto on_grad = [&](auto point, auto power) { return s->grad_term ? on_v(point, power, ic<bool, true>{}) : on_v(point, power, ic<bool, false>{}); };
+    auto on_power = [&](auto point) {
+        switch (s->weight_power) {
+            case 1: return on_grad(point, ic<int, 1>{});
+            case 2: return on_grad(point, ic<int, 2>{});
+            case 3: return on_grad(point, ic<int, 3>{});
+            default: return on_grad(point, ic<int, 4>{});
+        }
+    };
+    switch (s->point) {
+        case UCLSTM_LOSS_POINT_L1: return on_power(ic<int, UCLSTM_LOSS_POINT_L1>{});
+        case UCLSTM_LOSS_POINT_L2: return on_power(ic<int, UCLSTM_LOSS_POINT_L2>{});
+        default: return on_power(ic<int, UCLSTM_LOSS_POINT_HUBER>{});
+    }
+}
+
+// V = 4: every base 16-byte aligned and rows (with the gradient term) or the whole array (without) a multiple of four long
+bool loss_spec_vec(const uclstm_loss_spec* s, int64_t total, int W, const void* p0, const void* p1, const void* p2, const void* p3) {
+    const uintptr_t bases = (uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3;
+    return bases % 16 == 0 && (s->grad_term ? W % 4 == 0 : total % 4 == 0);
+}
+
+template <bool ORDERED>
+int32_t loss_spec_fwd_launch(const uclstm_loss_spec* s, const float* y_pred, const float* y, const float* mask, double* out, int64_t total,
+                             int H, int W, int rows, hipStream_t stream) {
+    const bool vec = loss_spec_vec(s, total, W, y_pred, y, mask, nullptr);
+    return loss_spec_dispatch(s, vec, [&](auto point, auto power, auto grad, auto v) -> int32_t {
+        constexpr int V = decltype(v)::value;
+        const int grid = ORDERED ? rows : grid_for(total / V, V == 4 ? SPEC_GRID_CAP_V4 : 1024);
+        UCLSTM_LAUNCH((loss_spec_fwd_kernel<decltype(point)::value, decltype(power)::value, decltype(grad)::value, ORDERED, V>), dim3(grid),
+                      dim3(NT), 0, stream, y_pred, y, mask, out, total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H, W, s->delta,
+                      s->weight_gain);
+        return UCLSTM_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" int32_t uclstm_loss_spec_fwd(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask, double* sums,
+                                        int64_t planes, int32_t H, int32_t W, void* stream) {
+    if (!loss_spec_ok(spec) || !y_pred || !y || !sums || planes <= 0 || H <= 0 || W <= 0) return UCLSTM_E_BADARG;
+    const int64_t total = planes * H * W;
+    if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    return loss_spec_fwd_launch<false>(spec, y_pred, y, mask, sums, total, H, W, 0, (hipStream_t)stream);
+}
+
+extern "C" int32_t uclstm_loss_spec_fwd_ordered(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                                double* partials, double* sums, int32_t accumulate, int64_t planes, int32_t H, int32_t W,
+                                                void* stream) {
+    if (!loss_spec_ok(spec) || !y_pred || !y || !partials || !sums || planes <= 0 || H <= 0 || W <= 0) return UCLSTM_E_BADARG;
+    const int64_t total = planes * H * W;
+    if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    const int rows = grid_for(total, ORDERED_ROWS_CAP);          // = uclstm_loss_fwd_ordered_rows, whatever V is
+    const int32_t rc = loss_spec_fwd_launch<true>(spec, y_pred, y, mask, partials, total, H, W, rows, (hipStream_t)stream);
+    if (rc != UCLSTM_OK) return rc;
+    UCLSTM_LAUNCH(ordered_sum_f64_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, rows, 4, sums, accumulate);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_loss_spec_bwd(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                        const float* coefs, float* grad, int64_t planes, int32_t H, int32_t W, void* stream) {
+    if (!loss_spec_ok(spec) || !y_pred || !y || !grad || !coefs || planes <= 0 || H <= 0 || W <= 0) return UCLSTM_E_BADARG;
+    const int64_t total = planes * H * W;
+    if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    const bool vec = loss_spec_vec(spec, total, W, y_pred, y, mask, grad);
+    return loss_spec_dispatch(spec, vec, [&](auto point, auto power, auto grd, auto v) -> int32_t {
+        constexpr int V = decltype(v)::value;
+        UCLSTM_LAUNCH((loss_spec_bwd_kernel<decltype(point)::value, decltype(power)::value, decltype(grd)::value, V>),
+                      dim3(grid_for(total / V, V == 4 ? SPEC_GRID_CAP_V4 : 2048)), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, coefs,
+                      grad, total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H, W, spec->delta, spec->weight_gain);
+        return UCLSTM_OK;
+    });
 }
 
 namespace {

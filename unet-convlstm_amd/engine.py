@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .loss import compute_loss
+from .loss import compute_loss, check_spec, LossSpec
 from .optim import FusedAdamW
 
 
@@ -757,9 +757,12 @@ def _stack(output):
     return torch.stack(output, dim=1) if isinstance(output, (list, tuple)) else output      # main.py:97-100
 
 
-def train_step(model, optimizer, x, y, mask=None, use_mask=True, ddp=None, clip_norm: Optional[float] = 1.0):
+def train_step(model, optimizer, x, y, mask=None, use_mask=True, ddp=None, clip_norm: Optional[float] = 1.0,
+               loss: Optional[LossSpec] = None):
     """zero_grad -> forward -> stack -> loss -> backward -> [gradient all-reduce] -> clip(1.0) -> optimiser step
-    (main.py:91-108).  Returns ``(loss, y_pred)`` as device tensors; nothing here waits for the GPU."""
+    (main.py:91-108).  Returns ``(loss, y_pred)`` as device tensors; nothing here waits for the GPU.  ``loss``: the
+    ``LossSpec`` of ``compute_loss(spec=...)``; None is the reference's loss."""
+    spec = check_spec(loss)
     optimizer.zero_grad(set_to_none=True)
     if ddp is not None:
         ddp.reset()
@@ -775,7 +778,7 @@ def train_step(model, optimizer, x, y, mask=None, use_mask=True, ddp=None, clip_
         with sync:
             output, _ = model(x)
             y_pred = _stack(output)
-            loss = compute_loss(y_pred, y, mask, use_mask)
+            loss = compute_loss(y_pred, y, mask, use_mask, spec)
             # fp16 compute: backward runs on loss * scale (FusedAdamW(loss_scale=...) owns the device-side dynamic scale)
             (optimizer.scale_loss(loss) if hasattr(optimizer, "scale_loss") else loss).backward()
     finally:
@@ -800,8 +803,8 @@ class GraphedTrainStep:
     What makes the step capturable: no host synchronisation anywhere in it; the optimiser reads its hyper-parameters and step
     count from device memory (``FusedAdamW(capturable=True)``); the weight-gradient / BatchNorm side stream forks from and joins
     the capturing stream through events; the look-ahead panel packing uses a persistent job table.  Inputs are copied into
-    static buffers; ``loss`` / ``y_pred`` are static outputs (valid until the next call).  Shapes, ``use_mask`` and the model's
-    mode are fixed at capture; ``clip_norm`` / lr changes (of every parameter group) reach the device through
+    static buffers; ``loss`` / ``y_pred`` are static outputs (valid until the next call).  Shapes, ``use_mask``, the ``loss``
+    keyword (a ``LossSpec`` or None, kept as ``self.loss_spec``) and the model's mode are fixed at capture; ``clip_norm`` / lr changes (of every parameter group) reach the device through
     ``optimizer.sync_hyper()`` before a replay.  fp16 compute (``ops.compute_dtype(torch.float16)`` around construction and
     calls, ``FusedAdamW(loss_scale=..., capturable=True)``): the loss scale, the overflow test, the skipped step and the scale
     update all live on the device, so an overflowed replay leaves parameters and moments alone without the host knowing.
@@ -811,7 +814,9 @@ class GraphedTrainStep:
     ordered or the atomic reductions according to the switch at construction (``self.deterministic``), and every replay keeps
     that mode whatever the switch says later."""
 
-    def __init__(self, model, optimizer, x, y, mask=None, use_mask: bool = True, clip_norm: Optional[float] = 1.0, warmup: int = 3):
+    def __init__(self, model, optimizer, x, y, mask=None, use_mask: bool = True, clip_norm: Optional[float] = 1.0, warmup: int = 3,
+                 loss: Optional[LossSpec] = None):
+        self.loss_spec = check_spec(loss)
         if not (isinstance(optimizer, FusedAdamW) and optimizer.capturable):
             raise ValueError("GraphedTrainStep needs FusedAdamW(..., capturable=True)")
         if not x.is_cuda:
@@ -831,12 +836,12 @@ class GraphedTrainStep:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(max(warmup, 2)):
-                train_step(model, optimizer, self.x, self.y, self.mask, use_mask, None, clip_norm)
+                train_step(model, optimizer, self.x, self.y, self.mask, use_mask, None, clip_norm, self.loss_spec)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.loss, self.y_pred = train_step(model, optimizer, self.x, self.y, self.mask, use_mask, None, clip_norm)
+            self.loss, self.y_pred = train_step(model, optimizer, self.x, self.y, self.mask, use_mask, None, clip_norm, self.loss_spec)
         # The graph owns what it captured.  Everything the capture allocated lives in the graph's own pool, and the model, the
         # optimiser and the static inputs are held above; the look-ahead batch is the exception: its panels and its device job
         # table were allocated by an eager step BEFORE the capture, their addresses are baked into the graph, and their only
@@ -919,8 +924,9 @@ def quiesce_host_gc() -> None:
     gc.freeze()
 
 
-def train_one_epoch(model, loader, optimizer, device, dataset_obj, use_mask=True, ddp=None):
-    """Reference main.py:77-144; returns ``(avg_loss, avg_mae, avg_rmse, avg_me)``."""
+def train_one_epoch(model, loader, optimizer, device, dataset_obj, use_mask=True, ddp=None, loss: Optional[LossSpec] = None):
+    """Reference main.py:77-144; returns ``(avg_loss, avg_mae, avg_rmse, avg_me)``.  ``loss``: as in ``train_step``."""
+    spec = check_spec(loss)
     model.train()
     total = torch.zeros((), dtype=torch.float64, device=device)
     n = 0
@@ -929,7 +935,7 @@ def train_one_epoch(model, loader, optimizer, device, dataset_obj, use_mask=True
         if it == 2:
             quiesce_host_gc()
         x, y, mask = x.to(device, non_blocking=True), y.to(device, non_blocking=True), mask.to(device, non_blocking=True)
-        loss, y_pred = train_step(model, optimizer, x, y, mask, use_mask, ddp)
+        loss, y_pred = train_step(model, optimizer, x, y, mask, use_mask, ddp, loss=spec)
         total += loss.double() * x.size(0)
         n += x.size(0)
         met.add(dataset_obj, y, y_pred, mask, use_mask)
@@ -938,9 +944,10 @@ def train_one_epoch(model, loader, optimizer, device, dataset_obj, use_mask=True
 
 
 @torch.no_grad()
-def evaluate(model, loader, device, dataset_obj, use_mask=True, tta=None):
+def evaluate(model, loader, device, dataset_obj, use_mask=True, tta=None, loss: Optional[LossSpec] = None):
     """Reference main.py:150-205.  ``tta``: None, or the ``codes`` of ``predict_tta`` (``"flips"``, ``"d4"``, an iterable): the
-    prediction is then the test-time-augmented mean."""
+    prediction is then the test-time-augmented mean.  ``loss``: the ``LossSpec`` whose value is averaged (None: the reference's)."""
+    spec = check_spec(loss)
     model.eval()
     total = torch.zeros((), dtype=torch.float64, device=device)
     n = 0
@@ -948,7 +955,7 @@ def evaluate(model, loader, device, dataset_obj, use_mask=True, tta=None):
     for x, y, mask in loader:
         x, y, mask = x.to(device, non_blocking=True), y.to(device, non_blocking=True), mask.to(device, non_blocking=True)
         y_pred = _stack(model(x)[0]) if tta is None else predict_tta(model, x, tta)
-        loss = compute_loss(y_pred, y, mask, use_mask)
+        loss = compute_loss(y_pred, y, mask, use_mask, spec)
         total += loss.double() * x.size(0)
         n += x.size(0)
         met.add(dataset_obj, y, y_pred, mask, use_mask)
@@ -1140,13 +1147,14 @@ class EvalReport:
 
 
 @torch.no_grad()
-def evaluate_report(model, loader, device, dataset_obj, use_mask=True, tta=None, **report_kwargs):
+def evaluate_report(model, loader, device, dataset_obj, use_mask=True, tta=None, loss: Optional[LossSpec] = None, **report_kwargs):
     """``evaluate()``'s loop with an ``EvalReport`` fed from the same ``y_pred``: returns ``(avg_loss, mae, rmse, me, report)``.
     The first four are computed as ``evaluate`` computes them, from the same launches as the report (``report`` is the dict
     of ``EvalReport.result``).  Against a SEPARATE ``evaluate()`` pass they agree as far as ``evaluate`` agrees with itself:
     its loss and metric kernels add block partials with f64 atomics in arrival order, so two passes can differ in the last
     bits (~1e-13 relative); the report's own sums do not have that freedom.  (In deterministic mode, ``ops.deterministic()``, those
-    kernels add their block partials in a fixed order and two passes are identical.)  ``tta``: as in ``evaluate``."""
+    kernels add their block partials in a fixed order and two passes are identical.)  ``tta`` and ``loss``: as in ``evaluate``."""
+    spec = check_spec(loss)
     model.eval()
     total = torch.zeros((), dtype=torch.float64, device=device)
     n = 0
@@ -1155,7 +1163,7 @@ def evaluate_report(model, loader, device, dataset_obj, use_mask=True, tta=None,
     for x, y, mask in loader:
         x, y, mask = x.to(device, non_blocking=True), y.to(device, non_blocking=True), mask.to(device, non_blocking=True)
         y_pred = _stack(model(x)[0]) if tta is None else predict_tta(model, x, tta)
-        loss = compute_loss(y_pred, y, mask, use_mask)
+        loss = compute_loss(y_pred, y, mask, use_mask, spec)
         total += loss.double() * x.size(0)
         n += x.size(0)
         met.add(dataset_obj, y, y_pred, mask, use_mask)

@@ -2404,34 +2404,62 @@ def convlstm_group_ok(members) -> bool:
 # ---------------------------------------------------------------------------------------------
 # Loss (main.py:28-72)
 # ---------------------------------------------------------------------------------------------
+_LOSS_POINTS = {"l1": L.LOSS_POINT_L1, "l2": L.LOSS_POINT_L2, "huber": L.LOSS_POINT_HUBER}
+
+
+def loss_spec_desc(spec) -> "L.LossSpecDesc":
+    """uclstm_loss_spec of a loss.LossSpec: what the kernels read (grad_weight and eps stay on the host side)."""
+    return L.LossSpecDesc(_LOSS_POINTS[spec.point], int(spec.weight_power), float(spec.delta), float(spec.weight_gain),
+                          int(spec.grad_weight != 0))
+
+
 class LossFn(torch.autograd.Function):
+    """``spec``: None = the reference's loss on uclstm_loss_fwd / _bwd; a loss.LossSpec = uclstm_loss_spec_fwd / _bwd (loss.py
+    sends the default spec here as None).  Both are logged as the reduction they are, loss_fwd / loss_fwd_ordered."""
+
     @staticmethod
-    def forward(ctx, y_pred, y, mask, use_mask):
+    def forward(ctx, y_pred, y, mask, use_mask, spec=None):
         _dev(y_pred, F32, "y_pred")
         y = _dev(y.contiguous(), F32, "y")
         H, W = y_pred.shape[-2], y_pred.shape[-1]
         planes = y_pred.numel() // (H * W)
         m = _dev(mask.contiguous().float(), F32, "mask") if (use_mask and mask is not None) else None
+        desc = None if spec is None else loss_spec_desc(spec)
+        ctx.desc = desc
         if _DETERMINISTIC:
             sums = torch.empty((4,), dtype=torch.float64, device=y_pred.device)
             partials = torch.empty((int(L.lib.uclstm_loss_fwd_ordered_rows(planes, H, W)), 4), dtype=torch.float64, device=y_pred.device)
             _log_reduce("loss_fwd_ordered")
-            L.check(L.lib.uclstm_loss_fwd_ordered(_p(y_pred), _p(y), _p(m), _p(partials), _p(sums), 0, planes, H, W, _stream()),
-                    "loss_fwd_ordered")
+            if desc is None:
+                L.check(L.lib.uclstm_loss_fwd_ordered(_p(y_pred), _p(y), _p(m), _p(partials), _p(sums), 0, planes, H, W, _stream()),
+                        "loss_fwd_ordered")
+            else:
+                L.check(L.lib.uclstm_loss_spec_fwd_ordered(C.byref(desc), _p(y_pred), _p(y), _p(m), _p(partials), _p(sums), 0, planes, H, W,
+                                                           _stream()), "loss_spec_fwd_ordered")
         else:
             sums = torch.zeros((4,), dtype=torch.float64, device=y_pred.device)
             _log_reduce("loss_fwd")
-            L.check(L.lib.uclstm_loss_fwd(_p(y_pred), _p(y), _p(m), _p(sums), planes, H, W, _stream()), "loss_fwd")
+            if desc is None:
+                L.check(L.lib.uclstm_loss_fwd(_p(y_pred), _p(y), _p(m), _p(sums), planes, H, W, _stream()), "loss_fwd")
+            else:
+                L.check(L.lib.uclstm_loss_spec_fwd(C.byref(desc), _p(y_pred), _p(y), _p(m), _p(sums), planes, H, W, _stream()),
+                        "loss_spec_fwd")
+        eps, gw = (1e-8, 0.005) if spec is None else (float(spec.eps), float(spec.grad_weight))
         n1 = float(y_pred.numel())
         n2 = float(planes * (H - 1) * (W - 1))
         if m is not None:
-            d1 = sums[1] + 1e-8
-            d2 = sums[3] + 1e-8
+            d1 = sums[1] + eps
+            d2 = sums[3] + eps
         else:
             d1 = torch.full((), n1, dtype=torch.float64, device=y_pred.device)
             d2 = torch.full((), n2, dtype=torch.float64, device=y_pred.device)
-        loss = (sums[0] / d1 + 0.005 * sums[2] / d2).float()
-        ctx.save_for_backward(y_pred, y, m, (1.0 / d1).float(), (0.005 / d2).float())
+        if gw == 0:                                                     # the gradient term does not exist (no 0 / 0 of an empty crop)
+            loss = (sums[0] / d1).float()
+            c2 = torch.zeros((), dtype=torch.float32, device=y_pred.device)
+        else:
+            loss = (sums[0] / d1 + gw * sums[2] / d2).float()
+            c2 = (gw / d2).float()
+        ctx.save_for_backward(y_pred, y, m, (1.0 / d1).float(), c2)
         return loss
 
     @staticmethod
@@ -2441,5 +2469,9 @@ class LossFn(torch.autograd.Function):
         planes = y_pred.numel() // (H * W)
         grad = torch.empty_like(y_pred)
         coefs = torch.stack((c1 * g, c2 * g)).float().contiguous()      # stays on device: no host sync in the step
-        L.check(L.lib.uclstm_loss_bwd(_p(y_pred), _p(y), _p(m), _p(coefs), _p(grad), planes, H, W, _stream()), "loss_bwd")
-        return grad, None, None, None
+        if ctx.desc is None:
+            L.check(L.lib.uclstm_loss_bwd(_p(y_pred), _p(y), _p(m), _p(coefs), _p(grad), planes, H, W, _stream()), "loss_bwd")
+        else:
+            L.check(L.lib.uclstm_loss_spec_bwd(C.byref(ctx.desc), _p(y_pred), _p(y), _p(m), _p(coefs), _p(grad), planes, H, W, _stream()),
+                    "loss_spec_bwd")
+        return grad, None, None, None, None
