@@ -706,6 +706,85 @@ int32_t uclstm_eval_stats(const uclstm_eval_desc* d, void* stream);
  * UCLSTM_E_BADARG. */
 int64_t uclstm_eval_stats_rows(int64_t P, int64_t frames);
 
+/* ------------------------------------------------------------------------------------ */
+/* Dataset statistics (train/unet.py:222-262, get_data_min_max.py) -- csrc/dataset_stats.hip */
+/* ------------------------------------------------------------------------------------ */
+/* The percentile branch of the reference dataset's constructor needs order statistics of Y and |Y| and the maximum of X.  Both
+ * entry-point families below work on the order-preserving u32 KEY of an f32: -0.0 becomes +0.0 (numpy compares them equal), then
+ * all bits are inverted for a negative value and the sign bit is set for a non-negative one.  NaNs are counted and take no part.
+ * Integer atomics only: every result is a pure function of the multiset of elements, identical from run to run.
+ *
+ * Rank select: up to UCLSTM_SELECT_MAX_SLOTS slots (rank, kind) are served together; slot s yields the element at index rank[s]
+ * of the ascending order of the non-NaN elements (kind UCLSTM_SELECT_SIGNED) or of their absolute values (UCLSTM_SELECT_ABS).
+ * Most significant digit first in three passes of 11 / 11 / 10 key bits.  The array may arrive in pieces, and every piece is read
+ * once per pass for all slots:
+ *     begin;  for pass in 0, 1, 2: { accumulate(pass, piece) for every piece, any number, any split;  narrow(pass) };  finish
+ * Everything is chained on `stream`; the host reads nothing back in between.  The pieces of the three passes must hold the same
+ * elements (in any order).
+ *
+ * uclstm_select_state is HOST memory, owned by the caller and written by these calls only (it records the workspace and which
+ * call comes next).  `workspace` is DEVICE memory, uclstm_select_workspace_bytes() bytes, 8-byte aligned, as u64 words:
+ *     [UCLSTM_SELECT_WS_COUNT] elements seen in pass 0     [UCLSTM_SELECT_WS_NAN] NaNs among them
+ *     [UCLSTM_SELECT_WS_FLAGS] bit s: slot s is out of range
+ *     [UCLSTM_SELECT_WS_PREFIX + s] the key digits of slot s decided so far, in place (lower bits zero)
+ *     [UCLSTM_SELECT_WS_RANK + s]   the slot's rank among the elements that share those digits
+ *     [UCLSTM_SELECT_WS_LEADER + s] the slot whose counters slot s reads in the current pass (slots of one kind with equal
+ *                                   decided digits share them; all ones for an out-of-range slot)
+ *     [UCLSTM_SELECT_WS_HIST + s*UCLSTM_SELECT_BINS + d] elements counted for digit d (2048 digits in passes 0 and 1, 1024 in pass 2)
+ * narrow(pass) turns the counters into the next digit and the remaining rank of every slot and clears them.  Counters and ranks
+ * are 64-bit throughout.
+ *
+ * begin: ranks and kinds are host arrays of n_slots entries.  accumulate: v f32 device, 4-byte aligned, 0 <= n < 2^31 elements per
+ * call (n = 0 launches nothing); larger arrays are split by the caller.  A 16-byte aligned base is read with 16-byte loads, any
+ * other base through a scalar head and tail.  finish: out_values f32 [n_slots] and out_info u64 [4] are device memory;
+ * out_info = { NaN count, element count, out-of-range mask, 0 }.  A slot whose rank is negative or not below the number of
+ * non-NaN elements is out of range: its bit is set in out_info[2] and its out_values entry is a quiet NaN; the other slots are
+ * unaffected.  finish ends the state; begin starts it again.
+ * UCLSTM_E_BADARG before any launch for: a NULL state / workspace / ranks / kinds / v / out_values / out_info, a misaligned
+ * workspace, v or output, n_slots outside [1, 8], an unknown kind, n outside [0, 2^31), a state that begin has not set up, and a
+ * call out of the order above (accumulate or narrow of another pass than the current one, finish before narrow(2)). */
+#define UCLSTM_SELECT_MAX_SLOTS 8
+#define UCLSTM_SELECT_BINS 2048
+#define UCLSTM_SELECT_SIGNED 0
+#define UCLSTM_SELECT_ABS 1
+#define UCLSTM_SELECT_WS_COUNT 0
+#define UCLSTM_SELECT_WS_NAN 1
+#define UCLSTM_SELECT_WS_FLAGS 2
+#define UCLSTM_SELECT_WS_PREFIX 8
+#define UCLSTM_SELECT_WS_RANK 16
+#define UCLSTM_SELECT_WS_LEADER 24
+#define UCLSTM_SELECT_WS_HIST 32
+#define UCLSTM_SELECT_WS_WORDS (UCLSTM_SELECT_WS_HIST + UCLSTM_SELECT_MAX_SLOTS * UCLSTM_SELECT_BINS)
+typedef struct {
+    void* workspace;
+    int32_t n_slots;
+    uint32_t abs_mask;
+    int32_t phase;
+    uint32_t magic;
+} uclstm_select_state;
+int64_t uclstm_select_workspace_bytes(void);
+int32_t uclstm_select_begin(uclstm_select_state* state, void* workspace, const int64_t* ranks, const int32_t* kinds, int32_t n_slots,
+                            void* stream);
+int32_t uclstm_select_accumulate(uclstm_select_state* state, int32_t pass, const float* v, int64_t n, void* stream);
+int32_t uclstm_select_narrow(uclstm_select_state* state, int32_t pass, void* stream);
+int32_t uclstm_select_finish(uclstm_select_state* state, float* out_values, uint64_t* out_info, void* stream);
+/* Extremes in one pass, accumulating over calls like the select: out u64 [UCLSTM_EXTREMES_WORDS] device memory, set up by
+ * uclstm_dataset_extremes_begin and updated by every uclstm_dataset_extremes(v, n) on the same stream:
+ *     [UCLSTM_EXTREMES_MIN_KEY] / [UCLSTM_EXTREMES_MAX_KEY] smallest / largest signed key of the non-NaN elements (0xffffffff / 0
+ *                               while there is none: min key > max key means "no such element")
+ *     [UCLSTM_EXTREMES_NAN] NaNs   [UCLSTM_EXTREMES_NONZERO] elements != 0 (NaNs included, as np.count_nonzero)
+ *     [UCLSTM_EXTREMES_COUNT] elements
+ * The value behind a key k: the f32 with bits k ^ 0x80000000 when k >= 2^31, ~k otherwise.  v, n and UCLSTM_E_BADARG as
+ * uclstm_select_accumulate (plus a NULL or misaligned out). */
+#define UCLSTM_EXTREMES_MIN_KEY 0
+#define UCLSTM_EXTREMES_MAX_KEY 1
+#define UCLSTM_EXTREMES_NAN 2
+#define UCLSTM_EXTREMES_NONZERO 3
+#define UCLSTM_EXTREMES_COUNT 4
+#define UCLSTM_EXTREMES_WORDS 8
+int32_t uclstm_dataset_extremes_begin(uint64_t* out, void* stream);
+int32_t uclstm_dataset_extremes(const float* v, int64_t n, uint64_t* out, void* stream);
+
 /* Scheduling aid, no reference counterpart: one wavefront that busy-waits `microseconds` of the constant 100 MHz wall clock on
  * `stream`.  The host layer uses it to find out whether two HIP streams really execute concurrently (streams that the
  * runtime multiplexes onto the same hardware queue serialise; which streams collide changes when e.g. an RCCL

@@ -108,7 +108,15 @@ class LossSpecDesc(C.Structure):
                 ("grad_term", C.c_int32), ("reserved_", C.c_int32 * 3)]
 
 
+class SelectState(C.Structure):
+    """uclstm_select_state: host memory, written by the uclstm_select_* calls only."""
+    _fields_ = [("workspace", C.c_void_p), ("n_slots", C.c_int32), ("abs_mask", C.c_uint32), ("phase", C.c_int32), ("magic", C.c_uint32)]
+
+
 LOSS_POINT_L1, LOSS_POINT_L2, LOSS_POINT_HUBER = 0, 1, 2
+SELECT_MAX_SLOTS, SELECT_BINS, SELECT_SIGNED, SELECT_ABS = 8, 2048, 0, 1
+SELECT_WS_COUNT, SELECT_WS_NAN, SELECT_WS_FLAGS, SELECT_WS_PREFIX, SELECT_WS_RANK, SELECT_WS_LEADER, SELECT_WS_HIST = 0, 1, 2, 8, 16, 24, 32
+EXTREMES_MIN_KEY, EXTREMES_MAX_KEY, EXTREMES_NAN, EXTREMES_NONZERO, EXTREMES_COUNT, EXTREMES_WORDS = 0, 1, 2, 3, 4, 8
 EVAL_ROW = 16
 EVAL_NONE, EVAL_ASINH, EVAL_SIGNED_LOG = 0, 1, 2
 
@@ -215,6 +223,13 @@ _PROTOS = {
     "uclstm_metric_sums_ordered": [_P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _P],
     "uclstm_eval_stats": [C.POINTER(EvalDesc), _P],
     "uclstm_eval_stats_rows": [_L, _L],
+    "uclstm_select_workspace_bytes": [],
+    "uclstm_select_begin": [C.POINTER(SelectState), _P, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _I, _P],
+    "uclstm_select_accumulate": [C.POINTER(SelectState), _I, _P, _L, _P],
+    "uclstm_select_narrow": [C.POINTER(SelectState), _I, _P],
+    "uclstm_select_finish": [C.POINTER(SelectState), _P, _P, _P],
+    "uclstm_dataset_extremes_begin": [_P, _P],
+    "uclstm_dataset_extremes": [_P, _L, _P, _P],
     "uclstm_stream_spin": [_I, _P],
     "uclstm_abi_version": [],
     "uclstm_build_arch": [],
@@ -224,7 +239,7 @@ _PROTOS = {
 _RESTYPES = {"uclstm_build_arch": C.c_char_p, "uclstm_source_hash": C.c_char_p, "uclstm_last_error_string": C.c_char_p, "uclstm_bn_bwd_reduce_rows": C.c_int64, "uclstm_bn_pool_bwd_rows": C.c_int64,
              "uclstm_eval_stats_rows": C.c_int64, "uclstm_colsum_ordered_rows": C.c_int64, "uclstm_outconv_bwd_ordered_rows": C.c_int64, "uclstm_head3x3_bwd_ordered_rows": C.c_int64,
              "uclstm_loss_fwd_ordered_rows": C.c_int64, "uclstm_sumsq_ordered_rows": C.c_int64, "uclstm_metric_sums_ordered_rows": C.c_int64,
-             "uclstm_bn_add_relu_bwd_rows": C.c_int64}
+             "uclstm_bn_add_relu_bwd_rows": C.c_int64, "uclstm_select_workspace_bytes": C.c_int64}
 
 
 # entry points that exist twice: name (bfloat16) and name_f16 (IEEE binary16), identical signatures (include/uclstm.h)

@@ -495,6 +495,269 @@ class DeviceSequenceLoader:
 
 
 # ---------------------------------------------------------------------------------------------
+# dataset statistics on the device: order statistics by radix select, extremes, the dataset's normalisation constants
+# ---------------------------------------------------------------------------------------------
+SELECT_MAX_LAUNCH = 1 << 30          # elements per uclstm_select_accumulate / uclstm_dataset_extremes call (the ABI takes n < 2^31)
+_KIND_IDS = {"signed": 0, "abs": 1}
+
+
+def _stat_pieces(t, what: str):
+    """``t`` (an f32 device tensor, or a re-iterable of them standing for their concatenation) -> a callable that yields
+    ``(data_ptr, n, keepalive)`` launches of at most ``SELECT_MAX_LAUNCH`` elements, anew on every call."""
+    if isinstance(t, torch.Tensor):
+        t = (t,)
+    elif iter(t) is t:
+        raise TypeError(f"{what}: the pieces are read once per pass, so a one-shot iterator cannot be used; "
+                        "pass a list, a tuple or an object whose __iter__ starts over")
+
+    def launches():
+        for piece in t:
+            piece = ops._dev(piece, torch.float32, what)
+            n, step = piece.numel(), int(SELECT_MAX_LAUNCH)
+            for off in range(0, n, step):          # an empty piece launches nothing
+                yield piece.data_ptr() + 4 * off, min(step, n - off), piece
+    return launches
+
+
+def _stat_device(t) -> torch.device:
+    if isinstance(t, torch.Tensor):
+        return t.device
+    if getattr(t, "device", None) is not None:
+        return torch.device(t.device)
+    for piece in t:
+        return piece.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _launch_select(t, ranks, kinds, what: str) -> torch.Tensor:
+    """Every launch of one select over ``t``; returns the device int64 [8] result (words 0..3: out_info, words 4..7: the f32
+    values) without synchronising."""
+    import ctypes as C
+    from . import _lib as L
+    ranks, kinds = [int(r) for r in ranks], list(kinds)
+    if not 1 <= len(ranks) <= L.SELECT_MAX_SLOTS or len(kinds) != len(ranks):
+        raise ValueError(f"{what}: between 1 and {L.SELECT_MAX_SLOTS} ranks with one kind each are required, got {len(ranks)} and {len(kinds)}")
+    for k in kinds:
+        if k not in _KIND_IDS:
+            raise ValueError(f"{what}: kind must be 'signed' or 'abs', got {k!r}")
+    launches, device = _stat_pieces(t, what), _stat_device(t)
+    with torch.cuda.device(device):
+        ws = torch.empty(int(L.lib.uclstm_select_workspace_bytes()) // 8, dtype=torch.int64, device=device)
+        out = torch.zeros(8, dtype=torch.int64, device=device)
+        st = L.SelectState()
+        c_ranks = (C.c_int64 * len(ranks))(*ranks)
+        c_kinds = (C.c_int32 * len(ranks))(*[_KIND_IDS[k] for k in kinds])
+        L.check(L.lib.uclstm_select_begin(C.byref(st), ops._p(ws), c_ranks, c_kinds, len(ranks), ops._stream()), "select_begin")
+        for p in range(3):
+            for ptr, n, _keep in launches():
+                if ops.LAUNCH_LOG is not None:
+                    ops.LAUNCH_LOG.append(("select", "accumulate", p, n))
+                L.check(L.lib.uclstm_select_accumulate(C.byref(st), p, C.c_void_p(ptr), n, ops._stream()), "select_accumulate")
+            L.check(L.lib.uclstm_select_narrow(C.byref(st), p, ops._stream()), "select_narrow")
+        L.check(L.lib.uclstm_select_finish(C.byref(st), C.c_void_p(out.data_ptr() + 32), ops._p(out), ops._stream()), "select_finish")
+    return out
+
+
+def _read_select(out: torch.Tensor, n_slots: int):
+    """The one host synchronisation of a select: ``(values f32 [n_slots], nan count, element count, out-of-range mask)``."""
+    host = out.cpu().numpy()
+    info = host[:4].view(np.uint64)
+    return host[4:].view(np.float32)[:n_slots].copy(), int(info[0]), int(info[1]), int(info[2])
+
+
+def device_order_statistics(t, ranks, kinds) -> np.ndarray:
+    """Exact order statistics of f32 device data: ``values[i]`` is the element at index ``ranks[i]`` of the ascending order of
+    the non-NaN elements of ``t`` (``kinds[i] == "signed"``) or of their absolute values (``"abs"``), as a float32 array; up to
+    8 of them from ONE radix select (``uclstm_select_*``: three passes over the data for all ranks together, integer counts
+    only, so the result does not depend on the run).  A zero comes back as +0.0.  ``t``: a contiguous f32 device tensor, or an
+    iterable of them treated as one concatenated array -- it is iterated once per pass, so it must start over on every
+    ``iter()`` (a list, or an object that uploads its chunks anew); a one-shot iterator is refused.  Tensors of more than
+    ``SELECT_MAX_LAUNCH`` elements go to the kernel in several calls.  A rank outside ``[0, number of non-NaN elements)``
+    raises ``IndexError``.  One host synchronisation, at the end."""
+    values, _, count, bad = _read_select(_launch_select(t, ranks, kinds, "device_order_statistics"), len(list(kinds)))
+    if bad:
+        s = (bad & -bad).bit_length() - 1
+        raise IndexError(f"device_order_statistics: rank {int(list(ranks)[s])} (slot {s}) is outside the non-NaN elements of an array of {count}")
+    return values
+
+
+def percentile_ranks(n: int, q: float, exact: bool = False):
+    """``(lo, hi, gamma)`` of ``np.percentile(a, q)`` (method 'linear') for a float32 ``a`` of ``n`` elements: the two ranks it
+    reads and the weight between them.  numpy forms the virtual index in the ARRAY's precision: ``f32(n-1) * (f32(q) / f32(100))``,
+    so above 2^24 elements the rank itself is rounded -- reproduced here on purpose (parity with the host dataset).
+    ``exact=True``: the same in f64, the true rank."""
+    ft = np.float64 if exact else np.float32
+    vi = ft(n - 1) * (ft(q) / ft(100))
+    if vi >= ft(n - 1):
+        lo = hi = n - 1
+        prev = -1                       # numpy's index of "the last element"; its gamma is formed from it (and multiplies a zero difference)
+    else:
+        lo = prev = int(np.floor(vi))
+        hi = lo + 1
+    return lo, hi, ft(np.float64(vi) - np.float64(prev))
+
+
+def percentile_lerp(a, b, gamma):
+    """numpy's interpolation between the two order statistics ``a <= b`` in their own precision:
+    ``a + (b-a)*g``, and ``b - (b-a)*(1-g)`` when ``g >= 0.5``."""
+    ft = type(gamma)
+    a, b = ft(a), ft(b)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = b - a
+        return b - d * (ft(1) - gamma) if gamma >= 0.5 else a + d * gamma
+
+
+def device_percentile(t, q, absolute: bool = False, exact: bool = False):
+    """``float(np.percentile(t.cpu().numpy(), q))`` (of ``np.abs(...)`` with ``absolute=True``) from the device, bit for bit:
+    numpy's rank rule for float32 data (``percentile_ranks``) on two order statistics of one radix select.  ``q``: a number, or a
+    sequence of up to 4 (a list is returned).  ``exact=True`` forms the rank and the interpolation in f64 instead -- numpy's own
+    rank is rounded to f32 above 2^24 elements.  NaN if the data holds a NaN, as numpy.  ``t`` as in
+    ``device_order_statistics``.  One host synchronisation, at the end."""
+    qs = [float(q)] if np.isscalar(q) else [float(v) for v in q]
+    if not qs or len(qs) > 4 or any(not 0.0 <= v <= 100.0 for v in qs):
+        raise ValueError(f"device_percentile: between 1 and 4 percentiles in [0, 100] are required, got {q!r}")
+    launches = _stat_pieces(t, "device_percentile")
+    n = sum(m for _, m, _ in launches())
+    if n == 0:
+        raise ValueError("device_percentile: the data is empty")
+    rk = [percentile_ranks(n, v, exact) for v in qs]
+    kind = "abs" if absolute else "signed"
+    values, nan, _, _ = _read_select(_launch_select(t, [r for lo, hi, _ in rk for r in (lo, hi)], [kind] * (2 * len(qs)), "device_percentile"),
+                                     2 * len(qs))
+    res = [float("nan") if nan else float(percentile_lerp(values[2 * i], values[2 * i + 1], g)) for i, (_, _, g) in enumerate(rk)]
+    return res[0] if np.isscalar(q) else res
+
+
+def _key_value(k: int) -> float:
+    k = int(k) & 0xffffffff
+    return float(np.array([k ^ 0x80000000 if k & 0x80000000 else ~k & 0xffffffff], dtype=np.uint32).view(np.float32)[0])
+
+
+def _launch_extremes(t, what: str) -> torch.Tensor:
+    from . import _lib as L
+    import ctypes as C
+    launches, device = _stat_pieces(t, what), _stat_device(t)
+    with torch.cuda.device(device):
+        out = torch.empty(L.EXTREMES_WORDS, dtype=torch.int64, device=device)
+        L.check(L.lib.uclstm_dataset_extremes_begin(ops._p(out), ops._stream()), "dataset_extremes_begin")
+        for ptr, n, _keep in launches():
+            if ops.LAUNCH_LOG is not None:
+                ops.LAUNCH_LOG.append(("extremes", n))
+            L.check(L.lib.uclstm_dataset_extremes(C.c_void_p(ptr), n, ops._p(out), ops._stream()), "dataset_extremes")
+    return out
+
+
+def _read_extremes(out: torch.Tensor) -> dict:
+    from . import _lib as L
+    w = out.cpu().numpy().view(np.uint64)
+    some = int(w[L.EXTREMES_MIN_KEY]) <= int(w[L.EXTREMES_MAX_KEY])
+    return {"min": _key_value(w[L.EXTREMES_MIN_KEY]) if some else float("nan"),
+            "max": _key_value(w[L.EXTREMES_MAX_KEY]) if some else float("nan"),
+            "nan_count": int(w[L.EXTREMES_NAN]), "nonzero": int(w[L.EXTREMES_NONZERO]), "count": int(w[L.EXTREMES_COUNT])}
+
+
+def device_extremes(t) -> dict:
+    """``{"min", "max", "nan_count", "nonzero", "count"}`` of f32 device data in one pass (``uclstm_dataset_extremes``): min and
+    max ignore NaNs (NaN when there is no other element; a zero is +0.0), ``nonzero`` counts like ``np.count_nonzero`` (NaNs
+    included).  ``t`` as in ``device_order_statistics`` (read once here).  One host synchronisation."""
+    return _read_extremes(_launch_extremes(t, "device_extremes"))
+
+
+class _HostChunks:
+    """A host array as device pieces of at most ``chunk_elems`` elements, uploaded anew on every iteration."""
+
+    def __init__(self, arr: np.ndarray, chunk_elems: int, device):
+        self.flat, self.step, self.device = np.ascontiguousarray(arr).reshape(-1), max(int(chunk_elems), 1), device
+
+    def __iter__(self):
+        for off in range(0, self.flat.size, self.step):
+            yield torch.from_numpy(self.flat[off:off + self.step]).to(self.device)
+
+
+class DeviceNPZDataset(NPZSequenceDataset):
+    """``NPZSequenceDataset`` whose normalisation constants come from the device: the same constructor arguments, attributes,
+    ``__getitem__`` and ``denormalize``, and the same values bit for bit, but ``np.max(X)`` is one ``uclstm_dataset_extremes``
+    pass and every percentile the host constructor would take comes out of ONE radix select over ``Y`` (up to 6 order
+    statistics, three passes), launched only on the branches the host constructor takes.  The percentiles of the TRANSFORMED
+    targets need no pass of their own: the transforms are monotone, so they are the transform of the same two order statistics
+    of the raw ``Y``, finished on the host with numpy's own ``arcsinh`` / ``log1p`` and numpy's f32 rank rule
+    (``percentile_ranks``; above 2^24 elements that rule rounds the rank itself, which is kept for parity).
+
+    When ``X`` and ``Y`` fit ``max_resident_bytes`` (default: 80 % of the device memory free at that moment) they are uploaded
+    once and left in the cache that ``DeviceSequenceLoader`` reads, so a loader over this dataset uploads nothing.  Otherwise
+    they are streamed in pieces of ``chunk_bytes``, once per pass, and the cache stays empty (``DeviceSequenceLoader`` then raises
+    its "does not fit" error as before)."""
+
+    def __init__(self, npz_path, lower_percentile=0.00001, upper_percentile=99.99999, clip_outliers=True,
+                 min_y=-7.5987958908081055, max_y=8.784920692443848, y_transform="asinh", y_transform_scale=None,
+                 y_transform_percentile=99, device="cuda", max_resident_bytes: Optional[int] = None, chunk_bytes: int = 256 << 20):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ops.L.UclstmError(f"DeviceNPZDataset: a HIP device is required, got {dev} (this package has no CPU path)")
+        dev = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+        if int(chunk_bytes) < 4:
+            raise ValueError(f"DeviceNPZDataset: chunk_bytes must hold at least one element, got {chunk_bytes}")
+        if y_transform not in ("asinh", "signed_log", None, "none"):
+            raise ValueError(y_transform)
+        with np.load(npz_path, allow_pickle=False) as data:
+            self.X = data["X"].astype(np.float32)
+            self.Y = data["Y"].astype(np.float32)
+        self.N, self.T, _, self.H, self.W = self.X.shape
+        need = int(self.X.nbytes) + int(self.Y.nbytes)
+        limit = int(0.8 * torch.cuda.mem_get_info(dev)[0]) if max_resident_bytes is None else int(max_resident_bytes)
+        if need <= limit:
+            self._device_resident = {dev: (torch.from_numpy(np.ascontiguousarray(self.X)).to(dev),
+                                           torch.from_numpy(np.ascontiguousarray(self.Y)).to(dev))}
+            x_src, y_src = self._device_resident[dev]
+        else:
+            x_src, y_src = _HostChunks(self.X, int(chunk_bytes) // 4, dev), _HostChunks(self.Y, int(chunk_bytes) // 4, dev)
+        self.y_transform, self.clip_outliers = y_transform, clip_outliers
+        explicit = (min_y is not None) and (max_y is not None)
+        # the order statistics the host constructor's branches read, all in one select
+        n = int(self.Y.size)
+        want = {}                       # name -> (q, kind) of the percentiles this call takes
+        if y_transform_scale is None and y_transform_percentile is not None:
+            want["scale"] = (y_transform_percentile, "abs")
+        if not explicit:
+            want["lo"], want["hi"] = (lower_percentile, "signed"), (upper_percentile, "signed")
+        rk = {name: percentile_ranks(n, q) for name, (q, _) in want.items()}
+        x_out = _launch_extremes(x_src, "DeviceNPZDataset X")
+        sel = _launch_select(y_src, [r for name in want for r in rk[name][:2]], [want[name][1] for name in want for _ in range(2)],
+                             "DeviceNPZDataset Y") if want else None
+        xs = _read_extremes(x_out)
+        self.x_max = float("nan") if xs["nan_count"] else xs["max"]
+        self.norm_const = max(self.x_max, 1.0)
+        values, nan = (None, 0) if sel is None else _read_select(sel, 2 * len(want))[:2]
+        pair = {name: values[2 * i:2 * i + 2] for i, name in enumerate(want)}
+
+        def pct(name, fwd=None):
+            """numpy's percentile from its two order statistics; ``fwd``: that of the transformed array (monotone: same ranks)."""
+            if nan:
+                return float("nan")
+            a, b = pair[name] if fwd is None else fwd(pair[name])
+            return float(percentile_lerp(a, b, rk[name][2]))
+        if y_transform_scale is None:
+            self.y_scale = pct("scale") if y_transform_percentile is not None else 1.0
+        else:
+            self.y_scale = float(y_transform_scale)
+        if explicit:
+            self.min_vel, self.max_vel = float(min_y), float(max_y)
+            self.trans_min = float(self._fwd(np.float64(self.min_vel)))
+            self.trans_max = float(self._fwd(np.float64(self.max_vel)))
+        else:
+            self.min_vel, self.max_vel = pct("lo"), pct("hi")
+            self.trans_min, self.trans_max = pct("lo", self._fwd), pct("hi", self._fwd)
+            if self.y_scale == 0.0 and self.y_transform in ("asinh", "signed_log"):
+                # the one case where the transformed ARRAY holds NaNs that its two order statistics do not show: 0 / 0 at every
+                # zero target.  numpy's percentile of it is NaN then; one extremes pass tells whether there is such a target.
+                ys = device_extremes(y_src)
+                if ys["nonzero"] < ys["count"]:
+                    self.trans_min = self.trans_max = float("nan")
+        if self.trans_max == self.trans_min:
+            self.trans_max = self.trans_min + 1.0
+
+
+# ---------------------------------------------------------------------------------------------
 # moving sprites (Moving-MNIST, digits/build_moving_mnist.py) rendered on the device
 # ---------------------------------------------------------------------------------------------
 MAX_SPRITES, MAX_GLYPH, MAX_SPRITE_SPEED = 8, 64, 127          # what uclstm_sprites_render accepts / clamps to
