@@ -528,6 +528,19 @@ int32_t uclstm_loss_spec_fwd_ordered(const uclstm_loss_spec* spec, const float* 
 /* grad = coefs[0] * rho'(d) * w * m + coefs[1] * d(sum gd*mc)/dy_pred; coefs is a DEVICE f32[2] as for uclstm_loss_bwd. */
 int32_t uclstm_loss_spec_bwd(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
                              const float* coefs, float* grad, int64_t planes, int32_t H, int32_t W, void* stream);
+/* The three entry points above with a mask that is BROADCAST over channels (main.py:40-43, :64-66 with y [B,T,Cy,H,W] and
+ * mask [B,T,1,H,W]): plane p of y_pred / y / grad reads mask plane p / mask_div, so mask holds ceil(planes / mask_div) planes of
+ * H x W.  Same partition of the elements over blocks and the same arithmetic per element as the entry points above: with the
+ * mask expanded to one plane per plane of y they return the same bits (ordered form and bwd; the atomic form up to the order of
+ * its atomics).  16-byte loads need W % 4 == 0 with the gradient term, H*W % 4 == 0 without.  UCLSTM_E_BADARG as above, and for a
+ * NULL mask or mask_div < 1. */
+int32_t uclstm_loss_spec_fwd_bc(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask, double* sums,
+                                int64_t planes, int32_t H, int32_t W, int32_t mask_div, void* stream);
+int32_t uclstm_loss_spec_fwd_ordered_bc(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                        double* partials, double* sums, int32_t accumulate, int64_t planes, int32_t H, int32_t W,
+                                        int32_t mask_div, void* stream);
+int32_t uclstm_loss_spec_bwd_bc(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                const float* coefs, float* grad, int64_t planes, int32_t H, int32_t W, int32_t mask_div, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Optimiser (main.py:106-108): global-norm clip + AdamW on flat f32 buffers            */
@@ -613,7 +626,8 @@ int32_t uclstm_dataset_gather_transform(const float* x_all, const float* y_all, 
  * x_all f32 [n_seq][T_src][C][Hs][Ws], y_all f32 [n_seq][T_src][1][Hs][Ws] -> x [n_out][T_out][C][Ho][Wo], y, mask
  * [n_out][T_out][1][Ho][Wo].  The mask is raw channel 0 > 1.1 at the SOURCE pixel; the arithmetic is per pixel and that of
  * uclstm_dataset_gather_transform, so the result is bit-identical to that entry point's output moved the same way.  Scalar
- * targets only: a vector target (horizontal velocity components) would need sign changes under mirrors.
+ * targets only: a vector target (horizontal velocity components) needs sign changes under mirrors and a swap under transposes;
+ * that is uclstm_dataset_gather_vec below.
  * flags: bit 0 = the table may hold codes with t (requires Ho == Wo); bit 1 = every ox in the table is a multiple of 4.
  * The kernel clamps what it reads from the table like idx (the caller validates): code & 7, or & 3 when bit 0 is clear; oy, ox, t0
  * into the range that keeps the window inside the source (ox rounded down to a multiple of 4 on the 16-byte path).
@@ -628,6 +642,41 @@ int32_t uclstm_dataset_gather_augment(const float* x_all, const float* y_all, co
  * [n_planes][H][W], or [n_planes][W][H] for codes with t.  src and dst must not overlap.  Requires n_planes * H * W < 2^31. */
 int32_t uclstm_plane_d4(const float* src, float* dst, int64_t n_planes, int32_t H, int32_t W, int32_t code, int32_t accumulate,
                         float scale, void* stream);
+/* Vector targets: Cy = 1 .. UCLSTM_VEC_MAX target channels per frame (the reference's u_map, v_map, w_map,
+ * preprocessing/build_WVU_maps.py:162), each with its own normalisation constants.  UCLSTM_VEC_MAX equals the head kernels'
+ * limit on output channels (HEAD_MAX_OUT). */
+#define UCLSTM_VEC_MAX 4
+typedef struct {
+    float min_vel, max_vel, y_scale, trans_min, trans_max;
+} uclstm_target_consts;
+/* uclstm_dataset_gather_augment for y_all f32 [n_seq][T_src][Cy][Hs][Ws] -> y [n_out][T_out][Cy][Ho][Wo]; x_all, x and mask
+ * ([n_out][T_out][1][Ho][Wo], raw x channel 0 > 1.1 at the source pixel) as there.  A move also acts on the channels: a component
+ * along image columns changes sign under h, one along rows under v, and the two change places under t.  chan_map is a HOST table
+ * int8 [8][Cy], row = code: output channel c takes the plane of source channel (entry & 7), clamped into [0, Cy), and negates
+ * its RAW value when bit 7 of the entry is set; NULL = identity.  Output channel c is then clipped and transformed with
+ * consts[c] (HOST [Cy]) by the arithmetic of uclstm_dataset_gather_transform; 1 / norm_const, 1 / y_scale and
+ * 1 / (trans_max - trans_min) are derived as there.  Both tables are read at launch and travel as kernel arguments: nothing is
+ * allocated, copied or synchronised.  aug == NULL: no remap (code 0, window at the origin, t0 = 0).
+ * Bit for bit: without aug, channel c equals uclstm_dataset_gather_transform on channel c with consts[c]; with aug, the batch
+ * equals the plain call on the raw data moved with flip / transpose / channel permutation / negation; with Cy = 1 and an
+ * identity chan_map it equals uclstm_dataset_gather_augment.  flags, the clamping of idx and of the table, the conditions of the
+ * 16-byte path and the tile mover are those of uclstm_dataset_gather_augment.  f32 only (no _f16 twin).
+ * UCLSTM_E_BADARG before any launch for: Cy outside [1, UCLSTM_VEC_MAX], a NULL x_all / y_all / x / y / mask / consts, y_scale <= 0
+ * under transforms 1 / 2, trans_max == trans_min, and the limits of uclstm_dataset_gather_augment with Cy in the products
+ * (n_out * T_out * Cy * Ho * Wo < 2^31, Cy * Hs * Ws < 2^31). */
+int32_t uclstm_dataset_gather_vec(const float* x_all, const float* y_all, const int64_t* idx, const int32_t* aug /* NULL: no remap */,
+        int64_t n_seq, int64_t n_out, int32_t T_src, int32_t T_out, int32_t C, int32_t Cy, int32_t Hs, int32_t Ws, int32_t Ho, int32_t Wo,
+        int32_t flags, const int8_t* chan_map /* HOST [8][Cy]: bits 0-2 source channel, bit 7 negate; NULL: identity */,
+        float* x, float* y, float* mask, int32_t transform, float norm_const, int32_t clip,
+        const uclstm_target_consts* consts /* HOST [Cy] */, void* stream);
+/* uclstm_plane_d4 over frames of Cy channels with a channel map and an affine term, the way back of test-time averaging for
+ * NORMALISED vector predictions: src f32 [n_frames][Cy][H][W], dst [n_frames][Cy][H][W] ([W][H] for codes with t),
+ *   dst[f][c] = (accumulate ? dst[f][c] : 0) + scale * (s * move(src[f][source channel]) + offset[c]),  s = -1 with bit 7, else 1,
+ * evaluated in that order in f32.  chan_map HOST int8 [Cy] (one row of the table above, NULL = identity), offset HOST f32 [Cy]
+ * (NULL = zeros); both travel as kernel arguments.  src and dst must not overlap.  UCLSTM_E_BADARG for a NULL src / dst, Cy
+ * outside [1, UCLSTM_VEC_MAX], code outside [0, 7], sizes <= 0, n_frames * Cy * H * W >= 2^31. */
+int32_t uclstm_plane_d4_vec(const float* src, float* dst, int64_t n_frames, int32_t Cy, int32_t H, int32_t W, int32_t code,
+        const int8_t* chan_map /* HOST [Cy], as above */, const float* offset /* HOST [Cy] */, int32_t accumulate, float scale, void* stream);
 /* Moving-sprite sequences rendered on the device (digits/build_moving_mnist.py:16-47), one launch per batch.
  * bank: uint8 [n_glyph][gh][gw]; table: int32 [n_out][D][5], rows {glyph, x0, y0, vx, vy}.  Per sequence, sprites d = 0..D-1 in
  * order, frames t = 0..T-1: where the glyph byte g > 0 inside the box at (x, y): frame = g / 255 (a later sprite overwrites) and
@@ -653,6 +702,17 @@ int32_t uclstm_metric_sums(const float* y_pred, const float* y, const float* mas
 int64_t uclstm_metric_sums_ordered_rows(int64_t n);
 int32_t uclstm_metric_sums_ordered(const float* y_pred, const float* y, const float* mask, double* partials, double* sums,
                                    int32_t accumulate, int64_t n, float y_scale, float trans_min, float trans_max, void* stream);
+/* The same four running sums PER TARGET CHANNEL: y_pred / y f32 [n_frames][Cy][HW], mask [n_frames][1][HW] broadcast over the
+ * channels (may be NULL), sums f64 [Cy][4].  Channel c is de-normalised with consts[c] (HOST [Cy], a kernel argument; min_vel and
+ * max_vel are not used) and by `transform` (0 none, 1 asinh: sinh(yt) * y_scale, 2 signed_log: sign(yt) * expm1(|yt|) * y_scale).
+ * One form only, the ordered one: partials f64 [uclstm_metric_sums_vec_rows][Cy][4] hold one stored block total each (a block
+ * owns a slice of every frame, all channels), and sums[c][k] = (accumulate ? sums[c][k] : 0) + p[0][c][k] + p[1][c][k] + ...,
+ * left to right.  No floating-point atomics: the result is a function of the inputs alone.  UCLSTM_E_BADARG for a NULL y_pred / y /
+ * partials / sums / consts, Cy outside [1, UCLSTM_VEC_MAX], transform outside [0, 2], sizes <= 0, n_frames * Cy * HW >= 2^31. */
+int64_t uclstm_metric_sums_vec_rows(int64_t n_frames, int32_t Cy, int32_t HW);
+int32_t uclstm_metric_sums_vec(const float* y_pred, const float* y, const float* mask, double* partials, double* sums,
+                               int32_t accumulate, int64_t n_frames, int32_t Cy, int32_t HW, int32_t transform,
+                               const uclstm_target_consts* consts /* HOST [Cy] */, void* stream);
 
 /* Evaluation report of train/get_metrics.py:117-358 and test.py:333-351 in one pass over f32 y_pred / y / mask (mask may be
  * NULL; a pixel counts when mask != 0).  Each tensor is [B][T] frames of P = C*H*W contiguous elements, addressed as

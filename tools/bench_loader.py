@@ -22,9 +22,15 @@ kernel writing the same OUTPUT shape in the same run (both write 16 B per pixel;
 optional raw planes; then an epoch of ``train_one_epoch`` fed by ``render_sprites_host`` plus a pinned host-to-device copy per
 batch against one fed by ``DeviceSpriteLoader`` (same model, the arms alternating epoch by epoch).
 
+``--vector`` times the vector-target gather kernel (``uclstm_dataset_gather_vec``) alone, same protocol, in A/B/A order inside a
+round: the scalar augmenting kernel (the yardstick), the new kernel at ``Cy = 1`` (the same bytes), the new kernel at ``Cy = 3``
+(44 B per pixel instead of 28: compared by achieved bandwidth), and the scalar kernel again -- the distance between the two runs of
+the yardstick is the spread the others are read against.  Full frames, all eight codes.
+
     python tools/bench_loader.py [--epochs 3] [--out profiles/device_loader_ab.txt]
     python tools/bench_loader.py --augment [--out profiles/device_loader_augment_ab.txt]
     python tools/bench_loader.py --sprites [--out profiles/sprites_ab.txt]
+    python tools/bench_loader.py --vector [--out profiles/vector_targets_ab.txt]
 """
 import argparse
 import os
@@ -50,6 +56,9 @@ ap.add_argument("--kernel-rounds", type=int, default=9)
 ap.add_argument("--augment", action="store_true", help="time the augmenting gather kernel against the plain one, nothing else")
 ap.add_argument("--sprites", action="store_true", help="time the sprite render kernel against the plain gather kernel, and an epoch "
                 "fed by the host mirror against one fed by DeviceSpriteLoader")
+ap.add_argument("--vector", action="store_true", help="time the vector-target gather kernel against the scalar augmenting kernel (A/B/A)")
+ap.add_argument("--vector-transform", default="asinh", choices=["asinh", "signed_log", "none"],
+                help="target transform of the --vector arms ('none' separates the traffic from the per-pixel arithmetic)")
 ap.add_argument("--out", default=None, help="also append the table to this file")
 a = ap.parse_args()
 if a.epochs < 3:
@@ -167,6 +176,73 @@ def augment_kernel(T, S, tmp):
         say(f"  {name:38s} {med:8.1f} {min(v):8.1f} {max(v):8.1f} {nbytes / med / 1e3:7.0f}   {note}")
     say()
     del flush
+
+
+def vector_kernel(T, S, tmp):
+    """uclstm_dataset_gather_vec against uclstm_dataset_gather_augment, the yardstick, which runs first AND last in every round.
+    Random device tensors as raw arrays (the dataset objects only supply constants and the channel map); every launch follows a
+    1 GiB fill."""
+    rng = np.random.default_rng(0)
+    path1, path3 = os.path.join(tmp, f"consts1_{T}x{S}.npz"), os.path.join(tmp, f"consts3_{T}x{S}.npz")
+    write_npz(path1, 4, T, S)
+    X = (rng.random((4, T, 2, S, S), dtype=np.float32) * 30).astype(np.float32)
+    np.savez(path3, X=X, Y=(rng.standard_normal((4, T, 3, S, S), dtype=np.float32) * np.float32([9, 9, 2]).reshape(1, 1, 3, 1, 1)))
+    tr = None if a.vector_transform == "none" else a.vector_transform
+    ds = U.NPZSequenceDataset(path1, y_transform=tr)
+    ds1 = U.VectorNPZDataset(path1, (None,), min_y=ds.min_vel, max_y=ds.max_vel, y_transform=tr)
+    ds3 = U.VectorNPZDataset(path3, ("+w", "-h", None), tie_horizontal=True, y_transform=tr)
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.rand((a.n, T, 2, S, S), device=dev, generator=g) * 30
+    x = x * (x >= 6)
+    y3 = torch.randn((a.n, T, 3, S, S), device=dev, generator=g) * 2
+    y1 = y3[:, :, :1].contiguous()
+    idx = torch.randperm(a.n, generator=torch.Generator().manual_seed(1))[:a.batch].to(dev)
+    tab = torch.zeros((a.batch, 4), dtype=torch.int32)
+    tab[:, 0] = torch.randint(0, 8, (a.batch,), generator=torch.Generator().manual_seed(2))
+    tab = tab.to(dev)
+    out1 = tuple(torch.empty((a.batch, T, c, S, S), device=dev) for c in (2, 1, 1))
+    out3 = tuple(torch.empty((a.batch, T, c, S, S), device=dev) for c in (2, 3, 1))
+    arms = {
+        "scalar augment (A)": (lambda: E._gather_augment(ds, x, y1, idx, tab, a.batch, (T, S, S), 3, out1), 28),
+        "vector, Cy = 1": (lambda: E._gather_vec(ds1, x, y1, idx, tab, a.batch, (T, S, S), 3, out1), 28),
+        "vector, Cy = 3": (lambda: E._gather_vec(ds3, x, y3, idx, tab, a.batch, (T, S, S), 3, out3), 44),
+        "scalar augment (A again)": (lambda: E._gather_augment(ds, x, y1, idx, tab, a.batch, (T, S, S), 3, out1), 28),
+    }
+    flush = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+    st = torch.cuda.current_stream()
+    ts = {k: [] for k in arms}
+    for r in range(a.kernel_rounds + 1):
+        for name, (launch, _) in arms.items():
+            flush.fill_(1.0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            launch()
+            e1.record(st)
+            torch.cuda.synchronize()
+            if r:                               # round 0 warms up (code-object load)
+                ts[name].append(e0.elapsed_time(e1) * 1e3)
+    del flush
+    px = a.batch * T * S * S
+    base, again = ts["scalar augment (A)"], ts["scalar augment (A again)"]
+    bm, am = statistics.median(base), statistics.median(again)
+    lo, hi = min(base + again), max(base + again)
+    say(f"shape: T = {T}, 2 x {S} x {S}, batch {a.batch} of {a.n} resident sequences, all eight codes, transform {a.vector_transform}; "
+        f"cold caches, {a.kernel_rounds} rounds, us")
+    say(f"  {'arm':26s} {'median':>8s} {'min':>8s} {'max':>8s} {'B/px':>5s} {'GB/s':>7s}   against the yardstick (medians {bm:.1f} and {am:.1f}, "
+        f"A-to-A {abs(am - bm) / bm * 100:.1f} %, min-max of both runs [{lo:.1f}, {hi:.1f}])")
+    gbase = px * 28 / ((bm + am) / 2) / 1e3
+    for name, v in ts.items():
+        med, bpp = statistics.median(v), arms[name][1]
+        gbs = px * bpp / med / 1e3
+        if name.startswith("scalar"):
+            note = "the yardstick"
+        elif bpp == 28:
+            where = "inside" if lo <= med <= hi else ("below" if med < lo else "above")
+            note = f"{med / ((bm + am) / 2):.3f} x the yardstick's median; {where} its min-max spread"
+        else:
+            note = f"{gbs / gbase:.3f} x the yardstick's achieved bandwidth ({gbase:.0f} GB/s)"
+        say(f"  {name:26s} {med:8.1f} {min(v):8.1f} {max(v):8.1f} {bpp:5d} {gbs:7.0f}   {note}")
+    say()
 
 
 class HostSpriteLoader:
@@ -325,7 +401,9 @@ with tempfile.TemporaryDirectory() as tmp:
     torch.zeros(1 << 20, device=dev).sum().item()          # the HIP context and the allocator exist before the first timed upload
     for shape in a.shapes.split(","):
         T, S = (int(v) for v in shape.split("x"))
-        if a.augment:
+        if a.vector:
+            vector_kernel(T, S, tmp)
+        elif a.augment:
             augment_kernel(T, S, tmp)
         elif a.sprites:
             sprites(T, S, tmp)

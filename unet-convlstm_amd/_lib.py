@@ -113,7 +113,13 @@ class SelectState(C.Structure):
     _fields_ = [("workspace", C.c_void_p), ("n_slots", C.c_int32), ("abs_mask", C.c_uint32), ("phase", C.c_int32), ("magic", C.c_uint32)]
 
 
+class TargetConsts(C.Structure):
+    """uclstm_target_consts: the normalisation constants of ONE target channel; arrays of it live in host memory, read at launch."""
+    _fields_ = [("min_vel", C.c_float), ("max_vel", C.c_float), ("y_scale", C.c_float), ("trans_min", C.c_float), ("trans_max", C.c_float)]
+
+
 LOSS_POINT_L1, LOSS_POINT_L2, LOSS_POINT_HUBER = 0, 1, 2
+VEC_MAX = 4                  # UCLSTM_VEC_MAX: target channels of the vector data path
 SELECT_MAX_SLOTS, SELECT_BINS, SELECT_SIGNED, SELECT_ABS = 8, 2048, 0, 1
 SELECT_WS_COUNT, SELECT_WS_NAN, SELECT_WS_FLAGS, SELECT_WS_PREFIX, SELECT_WS_RANK, SELECT_WS_LEADER, SELECT_WS_HIST = 0, 1, 2, 8, 16, 24, 32
 EXTREMES_MIN_KEY, EXTREMES_MAX_KEY, EXTREMES_NAN, EXTREMES_NONZERO, EXTREMES_COUNT, EXTREMES_WORDS = 0, 1, 2, 3, 4, 8
@@ -205,6 +211,9 @@ _PROTOS = {
     "uclstm_loss_spec_fwd": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _L, _I, _I, _P],
     "uclstm_loss_spec_fwd_ordered": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _P, _I, _L, _I, _I, _P],
     "uclstm_loss_spec_bwd": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _P, _L, _I, _I, _P],
+    "uclstm_loss_spec_fwd_bc": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _L, _I, _I, _I, _P],
+    "uclstm_loss_spec_fwd_ordered_bc": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _P],
+    "uclstm_loss_spec_bwd_bc": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _P, _L, _I, _I, _I, _P],
     "uclstm_sumsq": [_P, _L, _P, _P],
     "uclstm_sumsq_ordered_rows": [_L],
     "uclstm_sumsq_ordered": [_P, _L, _P, _P, _I, _P],
@@ -217,10 +226,14 @@ _PROTOS = {
     "uclstm_dataset_gather_transform": [_P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _I, _F, _F, _F, _P],
     "uclstm_dataset_gather_augment": [_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _I, _F, _F, _F, _P],
     "uclstm_plane_d4": [_P, _P, _L, _I, _I, _I, _I, _F, _P],
+    "uclstm_dataset_gather_vec": [_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _I, C.POINTER(TargetConsts), _P],
+    "uclstm_plane_d4_vec": [_P, _P, _L, _I, _I, _I, _I, _P, _P, _I, _F, _P],
     "uclstm_sprites_render": [_P, _I, _I, _I, _P, _L, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P],
     "uclstm_metric_sums": [_P, _P, _P, _P, _L, _F, _F, _F, _P],
     "uclstm_metric_sums_ordered_rows": [_L],
     "uclstm_metric_sums_ordered": [_P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _P],
+    "uclstm_metric_sums_vec_rows": [_L, _I, _I],
+    "uclstm_metric_sums_vec": [_P, _P, _P, _P, _P, _I, _L, _I, _I, _I, C.POINTER(TargetConsts), _P],
     "uclstm_eval_stats": [C.POINTER(EvalDesc), _P],
     "uclstm_eval_stats_rows": [_L, _L],
     "uclstm_select_workspace_bytes": [],
@@ -238,7 +251,7 @@ _PROTOS = {
 }
 _RESTYPES = {"uclstm_build_arch": C.c_char_p, "uclstm_source_hash": C.c_char_p, "uclstm_last_error_string": C.c_char_p, "uclstm_bn_bwd_reduce_rows": C.c_int64, "uclstm_bn_pool_bwd_rows": C.c_int64,
              "uclstm_eval_stats_rows": C.c_int64, "uclstm_colsum_ordered_rows": C.c_int64, "uclstm_outconv_bwd_ordered_rows": C.c_int64, "uclstm_head3x3_bwd_ordered_rows": C.c_int64,
-             "uclstm_loss_fwd_ordered_rows": C.c_int64, "uclstm_sumsq_ordered_rows": C.c_int64, "uclstm_metric_sums_ordered_rows": C.c_int64,
+             "uclstm_loss_fwd_ordered_rows": C.c_int64, "uclstm_sumsq_ordered_rows": C.c_int64, "uclstm_metric_sums_ordered_rows": C.c_int64, "uclstm_metric_sums_vec_rows": C.c_int64,
              "uclstm_bn_add_relu_bwd_rows": C.c_int64, "uclstm_select_workspace_bytes": C.c_int64}
 
 

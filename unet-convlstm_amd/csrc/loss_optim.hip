@@ -697,6 +697,85 @@ extern "C" int32_t uclstm_metric_sums_ordered(const float* y_pred, const float* 
     return UCLSTM_OK;
 }
 
+// ---- the metric sums per target channel (vector targets): ordered form only ----
+namespace {
+
+struct MetricConsts {                               // uclstm_target_consts [Cy] as a kernel argument
+    float yscale[UCLSTM_VEC_MAX], tmin[UCLSTM_VEC_MAX], trange[UCLSTM_VEC_MAX];
+};
+
+__device__ __forceinline__ float metric_denorm(float v, int transform, float yscale, float tmin, float trange) {
+    const float yt = (v + 1.f) * 0.5f * trange + tmin;          // as metric_sums_kernel
+    if (transform == 1) return sinhf(yt) * yscale;
+    if (transform == 2) return sgn(yt) * expm1f(fabsf(yt)) * yscale;
+    return yt;
+}
+
+// An item is one pixel of one frame: its mask is read once and serves the CY channels of that pixel.  The block's row of the
+// partial buffer is [CY][4]; no atomics.
+template <int CY>
+__global__ __launch_bounds__(NT) void metric_sums_vec_kernel(const float* __restrict__ yp, const float* __restrict__ y,
+                                                             const float* __restrict__ mask, double* __restrict__ partials, int64_t items,
+                                                             FastDiv dHW, int transform, MetricConsts k) {
+    __shared__ double red[4 * CY * 4];
+    double acc[CY * 4];
+#pragma unroll
+    for (int u = 0; u < CY * 4; ++u) acc[u] = 0.0;
+    const int HW = (int)dHW.d;
+    for (int64_t q = (int64_t)blockIdx.x * NT + threadIdx.x; q < items; q += (int64_t)gridDim.x * NT) {
+        const uint32_t f = fdiv((uint32_t)q, dHW);
+        const int64_t base = q + (int64_t)f * (CY - 1) * HW;     // element of channel 0: (f * CY) * HW + pixel
+        const float m = mask ? (mask[q] != 0.f ? 1.f : 0.f) : 1.f;
+#pragma unroll
+        for (int c = 0; c < CY; ++c) {
+            const float a = metric_denorm(yp[base + (int64_t)c * HW], transform, k.yscale[c], k.tmin[c], k.trange[c]);
+            const float b = metric_denorm(y[base + (int64_t)c * HW], transform, k.yscale[c], k.tmin[c], k.trange[c]);
+            const double d = (double)(a - b);
+            acc[c * 4 + 0] += fabs(d) * m;
+            acc[c * 4 + 1] += d * d * m;
+            acc[c * 4 + 2] += d * m;
+            acc[c * 4 + 3] += m;
+        }
+    }
+    block_sum_store<CY * 4>(acc, red, partials + (int64_t)blockIdx.x * (CY * 4));
+}
+
+}  // namespace
+
+extern "C" int64_t uclstm_metric_sums_vec_rows(int64_t n_frames, int32_t Cy, int32_t HW) {
+    if (n_frames <= 0 || Cy < 1 || Cy > UCLSTM_VEC_MAX || HW <= 0 || n_frames > (((int64_t)1 << 31) - 1) / ((int64_t)Cy * HW))
+        return UCLSTM_E_BADARG;
+    return grid_for(n_frames * HW, ORDERED_ROWS_CAP);
+}
+extern "C" int32_t uclstm_metric_sums_vec(const float* y_pred, const float* y, const float* mask, double* partials, double* sums,
+                                          int32_t accumulate, int64_t n_frames, int32_t Cy, int32_t HW, int32_t transform,
+                                          const uclstm_target_consts* consts, void* stream) {
+    if (!y_pred || !y || !partials || !sums || !consts || transform < 0 || transform > 2) return UCLSTM_E_BADARG;
+    const int64_t rows64 = uclstm_metric_sums_vec_rows(n_frames, Cy, HW);
+    if (rows64 < 1) return UCLSTM_E_BADARG;
+    const int rows = (int)rows64;
+    MetricConsts k;
+    for (int c = 0; c < UCLSTM_VEC_MAX; ++c) {
+        const uclstm_target_consts& t = consts[c < Cy ? c : 0];
+        k.yscale[c] = t.y_scale;
+        k.tmin[c] = t.trans_min;
+        k.trange[c] = t.trans_max - t.trans_min;
+    }
+    const int64_t items = n_frames * HW;
+#define UCLSTM_METRIC_VEC_LAUNCH(CY)                                                                                                   \
+    UCLSTM_LAUNCH(metric_sums_vec_kernel<CY>, dim3(rows), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, partials, items,           \
+                  make_fastdiv(HW), transform, k)
+    switch (Cy) {
+        case 1: UCLSTM_METRIC_VEC_LAUNCH(1); break;
+        case 2: UCLSTM_METRIC_VEC_LAUNCH(2); break;
+        case 3: UCLSTM_METRIC_VEC_LAUNCH(3); break;
+        default: UCLSTM_METRIC_VEC_LAUNCH(4); break;
+    }
+#undef UCLSTM_METRIC_VEC_LAUNCH
+    UCLSTM_LAUNCH(ordered_sum_f64_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, rows, Cy * 4, sums, accumulate);
+    return UCLSTM_OK;
+}
+
 extern "C" int32_t uclstm_ordered_sum_f64(const double* partials, int32_t rows, int32_t cols, double* out, int32_t accumulate, void* stream) {
     if (!partials || !out || rows <= 0 || cols <= 0) return UCLSTM_E_BADARG;
     UCLSTM_LAUNCH(ordered_sum_f64_kernel, dim3((cols + 63) / 64), dim3(64), 0, (hipStream_t)stream, partials, rows, cols, out, accumulate);
@@ -747,12 +826,33 @@ __device__ __forceinline__ float spec_drho(float d, float delta) {
     else return fminf(fmaxf(d, -delta), delta);
 }
 
+// The mask of the V elements at idx when it is BROADCAST over channels (the _bc entry points): plane p reads mask plane p / mask_div.
+// dPl divides by the H*W elements of a plane, dMd by mask_div.  Returns the pointer mk with mk[idx + j] = the mask of element idx + j
+// for every j inside the plane of idx (the neighbours the backward kernel reads).  A group of V lies inside one plane with the
+// gradient term (rows are a multiple of V long) or when H*W is a multiple of V; otherwise every element finds its own plane.
+template <int V, bool GRAD>
+__device__ __forceinline__ const float* load_mask_bc(const float* __restrict__ mask, int64_t idx, const FastDiv& dPl, const FastDiv& dMd,
+                                                     float (&m)[V]) {
+    const uint32_t pl = fdiv((uint32_t)idx, dPl);
+    const float* mk = mask - (int64_t)(pl - fdiv(pl, dMd)) * dPl.d;
+    if (GRAD || V == 1 || dPl.d % V == 0) {
+        load_v<V>(mk + idx, m);
+    } else {
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+            const uint32_t q = fdiv((uint32_t)(idx + u), dPl);
+            m[u] = mask[idx + u - (int64_t)(q - fdiv(q, dMd)) * dPl.d];
+        }
+    }
+    return mk;
+}
+
 // items = total / V groups of V elements of one row; dHW / dW divide by the groups of a plane / of a row (GRAD only).
 // sums as loss_fwd_kernel; without GRAD columns 2 and 3 are the zeros acc starts with.
-template <int POINT, int POWER, bool GRAD, bool ORDERED, int V>
+template <int POINT, int POWER, bool GRAD, bool ORDERED, int V, bool BC = false>
 __global__ void loss_spec_fwd_kernel(const float* __restrict__ yp, const float* __restrict__ y, const float* __restrict__ mask,
                                      double* __restrict__ sums, int64_t items, FastDiv dHW, FastDiv dW, int H, int W, float delta,
-                                     float gain) {
+                                     float gain, FastDiv dPl, FastDiv dMd) {
     __shared__ double red[16];
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     for (int64_t it = (int64_t)blockIdx.x * NT + threadIdx.x; it < items; it += (int64_t)gridDim.x * NT) {
@@ -760,7 +860,8 @@ __global__ void loss_spec_fwd_kernel(const float* __restrict__ yp, const float* 
         float a[V], b[V], m[V];
         load_v<V>(yp + idx, a);
         load_v<V>(y + idx, b);
-        if (mask) load_v<V>(mask + idx, m);
+        if constexpr (BC) load_mask_bc<V, GRAD>(mask, idx, dPl, dMd, m);
+        else if (mask) load_v<V>(mask + idx, m);
         else
 #pragma unroll
             for (int u = 0; u < V; ++u) m[u] = 1.f;
@@ -804,10 +905,10 @@ __global__ void loss_spec_fwd_kernel(const float* __restrict__ yp, const float* 
     }
 }
 
-template <int POINT, int POWER, bool GRAD, int V>
+template <int POINT, int POWER, bool GRAD, int V, bool BC = false>
 __global__ void loss_spec_bwd_kernel(const float* __restrict__ yp, const float* __restrict__ y, const float* __restrict__ mask,
                                      const float* __restrict__ coefs, float* __restrict__ grad, int64_t items, FastDiv dHW, FastDiv dW,
-                                     int H, int W, float delta, float gain) {
+                                     int H, int W, float delta, float gain, FastDiv dPl, FastDiv dMd) {
     const float c1 = coefs[0];
     float c2 = 0.f;
     if constexpr (GRAD) c2 = coefs[1];
@@ -816,7 +917,9 @@ __global__ void loss_spec_bwd_kernel(const float* __restrict__ yp, const float* 
         float a[V], b[V], m[V], g[V];
         load_v<V>(yp + idx, a);
         load_v<V>(y + idx, b);
-        if (mask) load_v<V>(mask + idx, m);
+        const float* mk = mask;                                  // BC: shifted so that mk + idx is the mask of this plane
+        if constexpr (BC) mk = load_mask_bc<V, GRAD>(mask, idx, dPl, dMd, m);
+        else if (mask) load_v<V>(mask + idx, m);
         else
 #pragma unroll
             for (int u = 0; u < V; ++u) m[u] = 1.f;
@@ -849,7 +952,7 @@ __global__ void loss_spec_bwd_kernel(const float* __restrict__ yp, const float* 
                 // cell (i,j-1): +sx(i,j-1)
                 const bool has_l = j >= 1;
                 const float al = has_l ? yp[idx - 1] : 0.f, bl = has_l ? y[idx - 1] : 0.f;
-                const float ml = (has_l && mask) ? mask[idx - 1] : 1.f;
+                const float ml = (has_l && mask) ? mk[idx - 1] : 1.f;
 #pragma unroll
                 for (int u = 0; u < V; ++u) {
                     if (u > 0 || has_l) {
@@ -864,7 +967,7 @@ __global__ void loss_spec_bwd_kernel(const float* __restrict__ yp, const float* 
                 float au[V], bu[V], mu[V];
                 load_v<V>(yp + idx - W, au);
                 load_v<V>(y + idx - W, bu);
-                if (mask) load_v<V>(mask + idx - W, mu);
+                if (mask) load_v<V>(mk + idx - W, mu);
                 else
 #pragma unroll
                     for (int u = 0; u < V; ++u) mu[u] = 1.f;
@@ -915,16 +1018,18 @@ bool loss_spec_vec(const uclstm_loss_spec* s, int64_t total, int W, const void* 
     return bases % 16 == 0 && (s->grad_term ? W % 4 == 0 : total % 4 == 0);
 }
 
-template <bool ORDERED>
+// BC: the mask is broadcast over channels, plane p reads mask plane p / mask_div (the _bc entry points); the grids, and so the
+// partition of the elements over blocks and threads, are those of the plain form.
+template <bool ORDERED, bool BC = false>
 int32_t loss_spec_fwd_launch(const uclstm_loss_spec* s, const float* y_pred, const float* y, const float* mask, double* out, int64_t total,
-                             int H, int W, int rows, hipStream_t stream) {
+                             int H, int W, int rows, hipStream_t stream, int mask_div = 1) {
     const bool vec = loss_spec_vec(s, total, W, y_pred, y, mask, nullptr);
     return loss_spec_dispatch(s, vec, [&](auto point, auto power, auto grad, auto v) -> int32_t {
         constexpr int V = decltype(v)::value;
         const int grid = ORDERED ? rows : grid_for(total / V, V == 4 ? SPEC_GRID_CAP_V4 : 1024);
-        UCLSTM_LAUNCH((loss_spec_fwd_kernel<decltype(point)::value, decltype(power)::value, decltype(grad)::value, ORDERED, V>), dim3(grid),
-                      dim3(NT), 0, stream, y_pred, y, mask, out, total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H, W, s->delta,
-                      s->weight_gain);
+        UCLSTM_LAUNCH((loss_spec_fwd_kernel<decltype(point)::value, decltype(power)::value, decltype(grad)::value, ORDERED, V, BC>),
+                      dim3(grid), dim3(NT), 0, stream, y_pred, y, mask, out, total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H, W,
+                      s->delta, s->weight_gain, make_fastdiv(H * W), make_fastdiv(mask_div));
         return UCLSTM_OK;
     });
 }
@@ -962,7 +1067,49 @@ extern "C" int32_t uclstm_loss_spec_bwd(const uclstm_loss_spec* spec, const floa
         constexpr int V = decltype(v)::value;
         UCLSTM_LAUNCH((loss_spec_bwd_kernel<decltype(point)::value, decltype(power)::value, decltype(grd)::value, V>),
                       dim3(grid_for(total / V, V == 4 ? SPEC_GRID_CAP_V4 : 2048)), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, coefs,
-                      grad, total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H, W, spec->delta, spec->weight_gain);
+                      grad, total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H, W, spec->delta, spec->weight_gain,
+                      make_fastdiv(H * W), make_fastdiv(1));
+        return UCLSTM_OK;
+    });
+}
+
+// ---- the same three with the mask broadcast over channels: plane p reads mask plane p / mask_div ----
+extern "C" int32_t uclstm_loss_spec_fwd_bc(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask, double* sums,
+                                           int64_t planes, int32_t H, int32_t W, int32_t mask_div, void* stream) {
+    if (!loss_spec_ok(spec) || !y_pred || !y || !mask || !sums || planes <= 0 || H <= 0 || W <= 0 || mask_div < 1) return UCLSTM_E_BADARG;
+    const int64_t total = planes * H * W;
+    if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    return loss_spec_fwd_launch<false, true>(spec, y_pred, y, mask, sums, total, H, W, 0, (hipStream_t)stream, mask_div);
+}
+
+extern "C" int32_t uclstm_loss_spec_fwd_ordered_bc(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                                   double* partials, double* sums, int32_t accumulate, int64_t planes, int32_t H,
+                                                   int32_t W, int32_t mask_div, void* stream) {
+    if (!loss_spec_ok(spec) || !y_pred || !y || !mask || !partials || !sums || planes <= 0 || H <= 0 || W <= 0 || mask_div < 1)
+        return UCLSTM_E_BADARG;
+    const int64_t total = planes * H * W;
+    if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    const int rows = grid_for(total, ORDERED_ROWS_CAP);          // = uclstm_loss_fwd_ordered_rows, whatever V is
+    const int32_t rc = loss_spec_fwd_launch<true, true>(spec, y_pred, y, mask, partials, total, H, W, rows, (hipStream_t)stream, mask_div);
+    if (rc != UCLSTM_OK) return rc;
+    UCLSTM_LAUNCH(ordered_sum_f64_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, rows, 4, sums, accumulate);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_loss_spec_bwd_bc(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                           const float* coefs, float* grad, int64_t planes, int32_t H, int32_t W, int32_t mask_div,
+                                           void* stream) {
+    if (!loss_spec_ok(spec) || !y_pred || !y || !mask || !grad || !coefs || planes <= 0 || H <= 0 || W <= 0 || mask_div < 1)
+        return UCLSTM_E_BADARG;
+    const int64_t total = planes * H * W;
+    if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    const bool vec = loss_spec_vec(spec, total, W, y_pred, y, mask, grad);
+    return loss_spec_dispatch(spec, vec, [&](auto point, auto power, auto grd, auto v) -> int32_t {
+        constexpr int V = decltype(v)::value;
+        UCLSTM_LAUNCH((loss_spec_bwd_kernel<decltype(point)::value, decltype(power)::value, decltype(grd)::value, V, true>),
+                      dim3(grid_for(total / V, V == 4 ? SPEC_GRID_CAP_V4 : 2048)), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, coefs,
+                      grad, total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H, W, spec->delta, spec->weight_gain,
+                      make_fastdiv(H * W), make_fastdiv(mask_div));
         return UCLSTM_OK;
     });
 }

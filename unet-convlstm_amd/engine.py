@@ -147,6 +147,215 @@ class NPZSequenceDataset(torch.utils.data.Dataset):
         return yt
 
 
+VEC_MAX = 4          # UCLSTM_VEC_MAX: target channels of the vector data path (the head kernels' limit on output channels)
+_AXES = ("+w", "-w", "+h", "-h", None)
+
+
+def _per_channel(v, Cy: int, what: str):
+    """A scalar or one value per channel -> a list of ``Cy`` values (None stays None for every channel)."""
+    if v is None or np.ndim(v) == 0:
+        return [v] * Cy
+    v = list(v)
+    if len(v) != Cy:
+        raise ValueError(f"VectorNPZDataset: {what} must be a scalar or one value per channel ({Cy}), got {len(v)}")
+    return v
+
+
+class VectorNPZDataset(NPZSequenceDataset):
+    """``NPZSequenceDataset`` for a VECTOR target: ``Y [N,T,Cy,H,W]`` with ``1 <= Cy <= 4`` channels (the reference's ``u_map``,
+    ``v_map``, ``w_map``, preprocessing/build_WVU_maps.py:162), each with normalisation constants of its own: ``y_scale``,
+    ``min_vel``, ``max_vel``, ``trans_min``, ``trans_max`` are float64 arrays ``[Cy]`` (``x_max`` / ``norm_const`` stay scalars).
+    Channel ``c``'s constants equal those of ``NPZSequenceDataset`` built with the same arguments on ``Y[:, :, c:c+1]``, and
+    channel ``c`` of an item's ``y`` equals that dataset's ``y``, bit for bit.  ``min_y``, ``max_y`` and ``y_transform_scale``
+    take a scalar or one value per channel.
+
+    ``axes``: one entry per channel saying how it turns with the image.  ``"+w"`` / ``"-w"``: the component along image COLUMNS,
+    positive towards increasing / decreasing column index; ``"+h"`` / ``"-h"``: the component along image ROWS; None: a scalar
+    (such as ``w``).  At most one w-channel and one h-channel.  ``u`` east, ``v`` north on rows that run south:
+    ``("+w", "-h", None)``.  ``channel_map(code)`` says what a move of ``Augment`` does to the channels (a mirror negates the
+    component across it, a transpose swaps the two), ``tta_affine(code)`` says it for NORMALISED values.
+
+    ``tie_horizontal=True``: the w- and the h-channel share ONE set of constants, computed from both channels together (as
+    ``NPZSequenceDataset`` on the two channels concatenated along ``N``): horizontal wind has one scale, and only with shared
+    constants is a transpose an exact map between normalised values (``tta_affine``).
+
+    A subclass of ``NPZSequenceDataset`` (``Subset``, ``random_split`` and ``DeviceSequenceLoader`` take it) that does not run its
+    constructor; code that reads a constant as a scalar fails on the array."""
+
+    def __init__(self, npz_path, axes, tie_horizontal=False, lower_percentile=0.00001, upper_percentile=99.99999, clip_outliers=True,
+                 min_y=None, max_y=None, y_transform="asinh", y_transform_scale=None, y_transform_percentile=99):
+        with np.load(npz_path, allow_pickle=False) as data:
+            self.X = data["X"].astype(np.float32)
+            self.Y = data["Y"].astype(np.float32)
+        self.N, self.T, _, self.H, self.W = self.X.shape
+        if self.Y.ndim != 5 or not 1 <= self.Y.shape[2] <= VEC_MAX:
+            raise ValueError(f"VectorNPZDataset: Y must be [N,T,Cy,H,W] with 1 <= Cy <= {VEC_MAX}, got {self.Y.shape}")
+        self.Cy = Cy = int(self.Y.shape[2])
+        self.axes = tuple(axes)
+        if len(self.axes) != Cy or any(a not in _AXES for a in self.axes):
+            raise ValueError(f"VectorNPZDataset: axes must hold one of {_AXES} per target channel ({Cy}), got {axes!r}")
+        w = [c for c, a in enumerate(self.axes) if a is not None and a[1] == "w"]
+        h = [c for c, a in enumerate(self.axes) if a is not None and a[1] == "h"]
+        if len(w) > 1 or len(h) > 1:
+            raise ValueError(f"VectorNPZDataset: at most one w-channel and one h-channel, got {axes!r}")
+        self.w_channel, self.h_channel = (w[0] if w else None), (h[0] if h else None)
+        self.tie_horizontal = bool(tie_horizontal)
+        self.x_max = float(np.max(self.X))
+        self.norm_const = max(self.x_max, 1.0)
+        if y_transform not in ("asinh", "signed_log", None, "none"):
+            raise ValueError(y_transform)
+        self.y_transform, self.clip_outliers = y_transform, clip_outliers
+        lo, hi, sc = (_per_channel(v, Cy, n) for v, n in ((min_y, "min_y"), (max_y, "max_y"), (y_transform_scale, "y_transform_scale")))
+        tied = (self.w_channel, self.h_channel) if self.tie_horizontal and w and h else ()
+        names = ("y_scale", "min_vel", "max_vel", "trans_min", "trans_max")
+        for name in names:
+            setattr(self, name, np.zeros(Cy, dtype=np.float64))
+        shared = None
+        for c in range(Cy):
+            if c in tied:
+                if shared is None:
+                    both = np.concatenate([self.Y[:, :, k:k + 1] for k in tied], axis=0)
+                    shared = self._constants(both, lo[c], hi[c], sc[c], lower_percentile, upper_percentile, y_transform_percentile)
+                vals = shared
+            else:
+                vals = self._constants(self.Y[:, :, c:c + 1], lo[c], hi[c], sc[c], lower_percentile, upper_percentile,
+                                       y_transform_percentile)
+            for name, v in zip(names, vals):
+                getattr(self, name)[c] = v
+
+    def _fwd_with(self, arr, y_scale):
+        if self.y_transform == "asinh":
+            return np.arcsinh(arr / y_scale)
+        if self.y_transform == "signed_log":
+            return np.sign(arr) * np.log1p(np.abs(arr) / y_scale)
+        return arr
+
+    def _fwd(self, arr):
+        raise TypeError("VectorNPZDataset has one transform scale per channel: there is no scalar _fwd")
+
+    def _constants(self, Y, min_y, max_y, y_transform_scale, lower_percentile, upper_percentile, y_transform_percentile):
+        """The constants ``NPZSequenceDataset.__init__`` derives from the one-channel array ``Y``, statement for statement."""
+        if y_transform_scale is None:
+            y_scale = float(np.percentile(np.abs(Y), y_transform_percentile)) if y_transform_percentile is not None else 1.0
+        else:
+            y_scale = float(y_transform_scale)
+        if (min_y is not None) and (max_y is not None):
+            min_vel, max_vel = float(min_y), float(max_y)
+            trans_min = float(self._fwd_with(np.float64(min_vel), y_scale))
+            trans_max = float(self._fwd_with(np.float64(max_vel), y_scale))
+        else:
+            min_vel = float(np.percentile(Y, lower_percentile))
+            max_vel = float(np.percentile(Y, upper_percentile))
+            yt = self._fwd_with(Y, y_scale)
+            trans_min = float(np.percentile(yt, lower_percentile))
+            trans_max = float(np.percentile(yt, upper_percentile))
+        if trans_max == trans_min:
+            trans_max = trans_min + 1.0
+        return y_scale, min_vel, max_vel, trans_min, trans_max
+
+    def __getitem__(self, idx):
+        x = torch.from_numpy(self.X[idx])
+        mask = (x[:, 0:1] > 1.1).float()
+        x = x / self.norm_const
+        y_raw = self.Y[idx]
+        y = np.empty(y_raw.shape, dtype=np.float32)
+        for c in range(self.Cy):                                   # NPZSequenceDataset.__getitem__ with channel c's Python floats
+            v = y_raw[..., c, :, :]
+            tmin, tmax = float(self.trans_min[c]), float(self.trans_max[c])
+            if self.clip_outliers:
+                v = np.clip(v, float(self.min_vel[c]), float(self.max_vel[c]))
+            y[..., c, :, :] = (2 * (self._fwd_with(v, float(self.y_scale[c])) - tmin) / (tmax - tmin) - 1.0).astype(np.float32)
+        return x, torch.from_numpy(y), mask
+
+    def denormalize(self, y_norm):
+        """``NPZSequenceDataset.denormalize`` with the per-channel constants broadcast along dim -3."""
+        if np.ndim(y_norm) < 3 or y_norm.shape[-3] != self.Cy:
+            raise ValueError(f"VectorNPZDataset.denormalize: dim -3 must hold the {self.Cy} target channels, got {tuple(y_norm.shape)}")
+        if isinstance(y_norm, torch.Tensor):
+            def col(a):
+                return torch.as_tensor(a, dtype=y_norm.dtype if y_norm.is_floating_point() else torch.float64,
+                                       device=y_norm.device).reshape(-1, 1, 1)
+            tmin, tmax, scale = col(self.trans_min), col(self.trans_max), col(self.y_scale)
+            yt = (y_norm + 1.0) / 2.0 * (tmax - tmin) + tmin
+            if self.y_transform == "asinh":
+                return torch.sinh(yt) * scale
+            if self.y_transform == "signed_log":
+                return torch.sign(yt) * torch.expm1(yt.abs()) * scale
+            return yt
+        tmin, tmax, scale = (a.reshape(-1, 1, 1) for a in (self.trans_min, self.trans_max, self.y_scale))
+        if getattr(y_norm, "dtype", None) == np.float32:           # the scalar class keeps f32 arrays f32 (Python-float constants)
+            tmin, tmax, scale = (a.astype(np.float32) for a in (tmin, tmax, scale))
+        yt = (y_norm + 1.0) / 2.0 * (tmax - tmin) + tmin
+        if self.y_transform == "asinh":
+            return np.sinh(yt) * scale
+        if self.y_transform == "signed_log":
+            return np.sign(yt) * (np.expm1(np.abs(yt)) * scale)
+        return yt
+
+    def channel_map(self, code: int):
+        """What the move ``code`` of ``Augment`` (``h | v << 1 | t << 2``, applied h, then v, then t) does to the channels: per
+        OUTPUT channel ``(source channel, negate)``.  h negates the w-channel, v the h-channel; t lets the w-channel take the
+        h-channel's plane and the reverse, both times ``s_w * s_h`` (the signs in ``axes``); scalars map to themselves.
+        ``ValueError`` for a code with t when exactly one of the two horizontal channels exists."""
+        code = int(code)
+        if not 0 <= code <= 7:
+            raise ValueError(f"code must be in 0..7, got {code}")
+        w, h = self.w_channel, self.h_channel
+        cur = [(c, False) for c in range(self.Cy)]
+        if code & 1 and w is not None:
+            cur[w] = (cur[w][0], not cur[w][1])
+        if code & 2 and h is not None:
+            cur[h] = (cur[h][0], not cur[h][1])
+        if code & 4 and (w is not None or h is not None):
+            if w is None or h is None:
+                raise ValueError(f"VectorNPZDataset: a transpose swaps the w- and the h-channel, axes {self.axes!r} name only one")
+            flip = self.axes[w][0] != self.axes[h][0]              # s_w * s_h == -1
+            cur[w], cur[h] = (cur[h][0], cur[h][1] != flip), (cur[w][0], cur[w][1] != flip)
+        return cur
+
+    def chan_map_table(self) -> np.ndarray:
+        """``channel_map`` of all eight codes as the kernels read it: int8 ``[8, Cy]``, bits 0-2 source channel, bit 7 negate.
+        Codes with t are the identity where ``channel_map`` refuses them (the loader never sends such a code)."""
+        tab = np.zeros((8, self.Cy), dtype=np.uint8)
+        for code in range(8):
+            try:
+                cm = self.channel_map(code)
+            except ValueError:
+                cm = [(c, False) for c in range(self.Cy)]
+            tab[code] = [src | (0x80 if neg else 0) for src, neg in cm]
+        return tab.view(np.int8)
+
+    def tta_affine(self, code: int):
+        """The move ``code`` on NORMALISED values: per output channel ``(source channel, sign, offset)`` with
+        ``out[c] = sign * move(y_n[source]) + offset``.  All three transforms are odd, so negating the physical value is
+        ``y_n -> -y_n - 2 (trans_max + trans_min) / (trans_max - trans_min)`` (exact where nothing was clipped); a swap is exact
+        only between channels with the same constants: ``ValueError`` otherwise (build the dataset with ``tie_horizontal=True``)."""
+        out = []
+        for c, (src, neg) in enumerate(self.channel_map(code)):
+            if src != c and any(getattr(self, n)[src] != getattr(self, n)[c] for n in ("y_scale", "trans_min", "trans_max")):
+                raise ValueError(f"VectorNPZDataset.tta_affine: code {code} swaps channels {src} and {c}, whose normalisation constants "
+                                 "differ; build the dataset with tie_horizontal=True")
+            tmin, tmax = float(self.trans_min[c]), float(self.trans_max[c])
+            out.append((src, -1.0, -2.0 * (tmax + tmin) / (tmax - tmin)) if neg else (src, 1.0, 0.0))
+        return out
+
+    def target_consts(self):
+        """``uclstm_target_consts [Cy]`` for the entry points (host memory, read at launch); built once."""
+        from . import _lib as L
+        arr = self.__dict__.get("_target_consts")
+        if arr is None:
+            arr = (L.TargetConsts * self.Cy)(*[L.TargetConsts(float(self.min_vel[c]), float(self.max_vel[c]), float(self.y_scale[c]),
+                                                               float(self.trans_min[c]), float(self.trans_max[c])) for c in range(self.Cy)])
+            self.__dict__["_target_consts"] = arr
+        return arr
+
+
+def _refuse_vector(ds, what: str):
+    if isinstance(ds, VectorNPZDataset):
+        raise TypeError(f"{what} does not take a vector dataset (VectorNPZDataset): it de-normalises with one scalar set of "
+                        "constants; use evaluate(..., per_channel=True) for per-component metrics")
+
+
 def device_transform(ds, x_raw: torch.Tensor, y_raw: torch.Tensor):
     """``NPZSequenceDataset.__getitem__`` (train/unet.py:273-304) for a whole RAW batch already on the device:
     ``x_raw [B,T,C,H,W]``, ``y_raw [B,T,1,H,W]`` f32 -> ``(x, y, mask)`` exactly as the host dataset would yield them
@@ -156,6 +365,8 @@ def device_transform(ds, x_raw: torch.Tensor, y_raw: torch.Tensor):
     from . import _lib as L
     x_raw = ops._dev(x_raw.contiguous(), torch.float32, "x_raw")
     y_raw = ops._dev(y_raw.contiguous(), torch.float32, "y_raw")
+    if isinstance(ds, VectorNPZDataset):   # y_raw [B,T,Cy,H,W]: the vector gather over the batch itself, identity order, no remap
+        return _gather_vec(ds, x_raw, y_raw, None, None, x_raw.shape[0], (x_raw.shape[1],) + tuple(x_raw.shape[3:]), 2)
     if ds.y_transform != "asinh":          # 'signed_log' / None: the gather kernel over the batch itself, identity order
         return _gather_transform(ds, x_raw, y_raw, None, x_raw.shape[0])
     B, T, Cc, H, W = x_raw.shape
@@ -199,8 +410,9 @@ class Augment:
     source (``crop_align=4`` keeps the kernel's 16-byte path when the widths are multiples of 4).  ``frames=T_out``: a window of
     ``T_out`` consecutive frames at a uniform start.  ``transpose`` needs a square output frame.
 
-    Scalar targets only (the reference's ``MAP_TYPE = 'w'``): a vector target (horizontal velocity components) would have to
-    change sign under mirrors and swap under transposes, which the remap does not do."""
+    The draw knows nothing about the target.  For a scalar target (the reference's ``MAP_TYPE = 'w'``) the remap is everything;
+    the horizontal components of a vector target also change sign under mirrors and swap under transposes:
+    ``DeviceSequenceLoader`` over a ``VectorNPZDataset`` does that with the dataset's ``axes`` (``uclstm_dataset_gather_vec``)."""
     hflip: bool = False
     vflip: bool = False
     transpose: bool = False
@@ -291,6 +503,36 @@ def _gather_augment(ds, x_all, y_all, idx, aug, n_out, shape, flags, out=None):
     return x, y, mask
 
 
+def _gather_vec(ds, x_all, y_all, idx, aug, n_out, shape, flags, out=None):
+    """One launch of ``uclstm_dataset_gather_vec`` for a ``VectorNPZDataset``: ``_gather_augment`` with ``y_all [N,T,Cy,H,W]`` ->
+    ``y [n_out,T_out,Cy,Ho,Wo]``, the channels moved by ``ds.chan_map_table()`` and normalised with their own constants.
+    ``aug=None``: no remap (the plain gather; ``shape`` is then the source's)."""
+    from . import _lib as L
+    N, T, Cc, H, W = x_all.shape
+    Cy = ds.Cy
+    To, Ho, Wo = (int(v) for v in shape)
+    if y_all.dim() != 5 or y_all.shape[2] != Cy or y_all.shape[:2] != x_all.shape[:2] or y_all.shape[3:] != x_all.shape[3:]:
+        raise L.UclstmError(f"_gather_vec: y must be [{N},{T},{Cy},{H},{W}] beside x {tuple(x_all.shape)}, got {tuple(y_all.shape)}")
+    if aug is not None:
+        aug = ops._dev(aug, torch.int32, "aug")
+        if aug.dim() != 2 or aug.shape[1] != 4 or aug.shape[0] < n_out:
+            raise L.UclstmError(f"_gather_vec: aug must be int32 [>= {n_out}, 4], got {tuple(aug.shape)}")
+    if out is None:
+        x = torch.empty((n_out, To, Cc, Ho, Wo), dtype=torch.float32, device=x_all.device)
+        y = torch.empty((n_out, To, Cy, Ho, Wo), dtype=torch.float32, device=x_all.device)
+        mask = torch.empty((n_out, To, 1, Ho, Wo), dtype=torch.float32, device=x_all.device)
+    else:
+        x, y, mask = out
+    table = ds.__dict__.get("_chan_map_host")
+    if table is None:
+        table = ds.__dict__["_chan_map_host"] = np.ascontiguousarray(ds.chan_map_table())
+    L.check(L.lib.uclstm_dataset_gather_vec(
+        ops._p(x_all), ops._p(y_all), ops._p(idx), ops._p(aug), N, n_out, T, To, Cc, Cy, H, W, Ho, Wo, int(flags),
+        table.ctypes.data, ops._p(x), ops._p(y), ops._p(mask), _TRANSFORM_IDS[ds.y_transform], float(ds.norm_const),
+        int(bool(ds.clip_outliers)), ds.target_consts(), ops._stream()), "dataset_gather_vec")
+    return x, y, mask
+
+
 def plane_d4(t: torch.Tensor, code: int, out: Optional[torch.Tensor] = None, accumulate: bool = False, scale: float = 1.0):
     """Move the last two dims of the contiguous f32 device tensor ``t`` by ``code`` (0..7, as in ``Augment``):
     ``out = (accumulate ? out : 0) + scale * move(t)``, one launch of ``uclstm_plane_d4``.  ``out``: ``t``'s shape, with the last
@@ -316,16 +558,54 @@ def plane_d4(t: torch.Tensor, code: int, out: Optional[torch.Tensor] = None, acc
     return out
 
 
+def plane_d4_vec(t: torch.Tensor, code: int, affine, out: Optional[torch.Tensor] = None, accumulate: bool = False, scale: float = 1.0):
+    """``plane_d4`` for frames of channels that turn with the image: ``t [..., Cy, H, W]``, ``affine`` = per output channel
+    ``(source channel, sign, offset)`` as ``VectorNPZDataset.tta_affine`` returns it, and
+    ``out[..., c, :, :] = (accumulate ? out : 0) + scale * (sign * move(t[..., source, :, :]) + offset)``: one launch of
+    ``uclstm_plane_d4_vec``."""
+    from . import _lib as L
+    code = int(code)
+    t = ops._dev(t, torch.float32, "plane_d4_vec input")
+    affine = list(affine)
+    Cy = len(affine)
+    if t.dim() < 3 or t.shape[-3] != Cy or not 1 <= Cy <= VEC_MAX or not 0 <= code <= 7:
+        raise ValueError(f"plane_d4_vec: a tensor [..., {Cy}, H, W] with 1 <= Cy <= {VEC_MAX} and a code in 0..7 are required, "
+                         f"got {tuple(t.shape)}, code {code}")
+    if any(not 0 <= int(src) < Cy or sign not in (1, -1) for src, sign, _ in affine):
+        raise ValueError(f"plane_d4_vec: affine must hold (source channel in [0, {Cy}), sign +-1, offset) per channel, got {affine}")
+    H, W = t.shape[-2:]
+    shape = tuple(t.shape[:-2]) + ((W, H) if code & 4 else (H, W))
+    if out is None:
+        if accumulate:
+            raise ValueError("plane_d4_vec: accumulate=True needs out=")
+        out = torch.empty(shape, dtype=torch.float32, device=t.device)
+    else:
+        ops._dev(out, torch.float32, "plane_d4_vec out")
+        if tuple(out.shape) != shape or out.device != t.device or out.data_ptr() == t.data_ptr():
+            raise ValueError(f"plane_d4_vec: out must be another tensor of shape {shape} on {t.device}, got {tuple(out.shape)} on {out.device}")
+    if t.numel():
+        import ctypes as C
+        cmap = (C.c_int8 * Cy)(*[(int(src) | (0x80 if sign < 0 else 0)) - (256 if sign < 0 else 0) for src, sign, _ in affine])
+        offs = (C.c_float * Cy)(*[float(off) for _, _, off in affine])
+        L.check(L.lib.uclstm_plane_d4_vec(ops._p(t), ops._p(out), t.numel() // (Cy * H * W), Cy, H, W, code, C.addressof(cmap),
+                                          C.addressof(offs), int(bool(accumulate)), float(scale), ops._stream()), "plane_d4_vec")
+    return out
+
+
 _TTA_SETS = {"flips": (0, 1, 2, 3), "d4": tuple(range(8))}
 
 
 @torch.no_grad()
-def predict_tta(model, x: torch.Tensor, codes="flips", state=None) -> torch.Tensor:
+def predict_tta(model, x: torch.Tensor, codes="flips", state=None, dataset=None) -> torch.Tensor:
     """Test-time augmentation: the mean over ``codes`` of ``inverse move(model(move(x)))``, ``[B,T,C,H,W]`` f32.
     ``codes``: ``"flips"`` = (0, 1, 2, 3), ``"d4"`` = all eight, or an iterable of codes.  For each code in the given order: ``x``
     is moved with ``plane_d4``, the model runs under ``no_grad``, its frames are stacked as the epoch loops stack them, and the
     output moved by the INVERSE code is accumulated with weight 1 / len(codes) by the same kernel (left to right in f32).
-    ``model`` is anything that returns ``(frames or tensor, state)``.  Codes with t need square frames."""
+    ``model`` is anything that returns ``(frames or tensor, state)``.  Codes with t need square frames.
+
+    ``dataset``: a ``VectorNPZDataset`` whose target channels the model predicts (normalised).  The inputs move as before; the
+    outputs come back through ``plane_d4_vec`` with ``dataset.tta_affine(d4_inverse(c))``, so a horizontal component changes sign
+    and channel with the frame (codes with t need ``tie_horizontal=True``).  None: scalar outputs, the launches as they were."""
     if isinstance(codes, str):
         if codes not in _TTA_SETS:
             raise ValueError(f"predict_tta: codes must be one of {sorted(_TTA_SETS)} or an iterable of codes, got {codes!r}")
@@ -335,13 +615,18 @@ def predict_tta(model, x: torch.Tensor, codes="flips", state=None) -> torch.Tens
         raise ValueError(f"predict_tta: codes must be a non-empty sequence of values in 0..7, got {codes}")
     if any(c & 4 for c in codes) and x.shape[-1] != x.shape[-2]:
         raise ValueError(f"predict_tta: codes with a transpose need square frames, got {x.shape[-2]} x {x.shape[-1]}")
+    if dataset is not None and not isinstance(dataset, VectorNPZDataset):
+        raise TypeError(f"predict_tta: dataset must be a VectorNPZDataset or None, got {type(dataset).__name__}")
+    affine = None if dataset is None else {c: dataset.tta_affine(d4_inverse(c)) for c in codes}      # raises before any launch
     x = x.contiguous().float()
     acc = None
     for c in codes:
         xc = plane_d4(x, c)
         output, _ = model(xc) if state is None else model(xc, state)
         y = _stack(output).contiguous().float()
-        if acc is None:
+        if affine is not None:
+            acc = plane_d4_vec(y, d4_inverse(c), affine[c], out=acc, accumulate=acc is not None, scale=1.0 / len(codes))
+        elif acc is None:
             acc = plane_d4(y, d4_inverse(c), scale=1.0 / len(codes))
         else:
             plane_d4(y, d4_inverse(c), out=acc, accumulate=True, scale=1.0 / len(codes))
@@ -402,8 +687,14 @@ class DeviceSequenceLoader:
     ``uclstm_dataset_gather_augment`` per batch instead (batches are then ``[b, T_out, C, Ho, Wo]``).  Per epoch
     ``epoch_augment`` draws one table row per POSITION from ``augment_generator`` (two positions that name the same row get
     independent draws); the table is uploaded once next to the row list, and ``last_augment`` keeps the host copy of the current
-    epoch.  A batch is bit-identical to the plain batch moved with ``torch.flip`` / ``transpose`` / slicing.  Scalar targets only
-    (see ``Augment``).  ``augment=None`` is the plain path, launch for launch."""
+    epoch.  A batch is bit-identical to the plain batch moved with ``torch.flip`` / ``transpose`` / slicing.
+    ``augment=None`` is the plain path, launch for launch.
+
+    A ``VectorNPZDataset`` (or Subsets of one) yields ``y [b,T_out,Cy,Ho,Wo]`` through ``uclstm_dataset_gather_vec``, with or
+    without ``augment``: the move also negates and swaps the horizontal components as the dataset's ``axes`` say
+    (``channel_map``, a host table: nothing more is uploaded), and every channel is normalised with its own constants.
+    ``Augment(transpose=True)`` over a dataset with only one horizontal channel is refused at construction.  A scalar dataset
+    takes the entry points it always took."""
 
     def __init__(self, dataset, batch_size: int, shuffle: bool = False, sampler=None, drop_last: bool = False, generator=None,
                  device="cuda", max_resident_bytes: Optional[int] = None, augment: Optional[Augment] = None, augment_generator=None):
@@ -426,6 +717,9 @@ class DeviceSequenceLoader:
         self.augment, self.augment_generator, self.last_augment = augment, augment_generator, None
         if augment is not None:
             augment.output_shape(self.root.T, self.root.H, self.root.W)          # a crop that does not fit fails here, not mid-epoch
+        self.vector = isinstance(self.root, VectorNPZDataset)
+        if self.vector and augment is not None and augment.transpose:
+            self.root.channel_map(4)                                             # an unpaired horizontal channel: ValueError here
         self.x_all, self.y_all = self._resident(self.root, self.device, max_resident_bytes)
 
     @staticmethod
@@ -461,7 +755,8 @@ class DeviceSequenceLoader:
             if not self.drop_last and len(self.sampler) % self.batch_size:
                 raise ValueError(f"batches(out=...): the last batch of {len(self.sampler)} positions in batches of "
                                  f"{self.batch_size} would be short; use drop_last=True")
-            want = ((self.batch_size, T, Cc, H, W), (self.batch_size, T, 1, H, W), (self.batch_size, T, 1, H, W))
+            Cy = self.root.Cy if self.vector else 1
+            want = ((self.batch_size, T, Cc, H, W), (self.batch_size, T, Cy, H, W), (self.batch_size, T, 1, H, W))
             if len(out) != 3:
                 raise ValueError("batches(out=...): expected (x, y, mask)")
             for t, shape, what in zip(out, want, ("out x", "out y", "out mask")):
@@ -486,7 +781,13 @@ class DeviceSequenceLoader:
             aug = pinned_aug.to(self.device, non_blocking=True)
         s = 0
         for b in [len(b) for b in batches]:
-            if self.augment is None:
+            if self.vector:                                     # one entry point with or without augmentation (aug = NULL)
+                if self.augment is None:
+                    T, _, H, W = self.x_all.shape[1:]
+                    yield _gather_vec(self.root, self.x_all, self.y_all, rows[s:s + b], None, b, (T, H, W), 2, out)
+                else:
+                    yield _gather_vec(self.root, self.x_all, self.y_all, rows[s:s + b], aug[s:s + b], b, shape, flags, out)
+            elif self.augment is None:
                 yield _gather_transform(self.root, self.x_all, self.y_all, rows[s:s + b], b, out)
             else:
                 yield _gather_augment(self.root, self.x_all, self.y_all, rows[s:s + b], aug[s:s + b], b, shape, flags, out)
@@ -703,6 +1004,9 @@ class DeviceNPZDataset(NPZSequenceDataset):
             self.X = data["X"].astype(np.float32)
             self.Y = data["Y"].astype(np.float32)
         self.N, self.T, _, self.H, self.W = self.X.shape
+        if self.Y.ndim == 5 and self.Y.shape[2] > 1:
+            raise TypeError(f"DeviceNPZDataset does not take a vector dataset: Y has {self.Y.shape[2]} target channels and this class "
+                            "derives one scalar set of constants; VectorNPZDataset computes per-channel constants on the host")
         need = int(self.X.nbytes) + int(self.Y.nbytes)
         limit = int(0.8 * torch.cuda.mem_get_info(dev)[0]) if max_resident_bytes is None else int(max_resident_bytes)
         if need <= limit:
@@ -1136,9 +1440,34 @@ class _Metrics:
 
     def __init__(self, device):
         self.s = torch.zeros(4, dtype=torch.float64, device=device)
+        self.sv = None                               # [Cy, 4] for a vector dataset: the same sums per target channel
+
+    @torch.no_grad()
+    def _add_vec(self, ds, y, y_pred, mask, use_mask):
+        """One ``uclstm_metric_sums_vec`` (ordered partials in both modes): every channel de-normalised with its own constants."""
+        from . import _lib as L
+        yp = ops._dev(y_pred.contiguous().float(), torch.float32, "y_pred")
+        yt = ops._dev(y.contiguous().float(), torch.float32, "y")
+        Cy, (H, W) = ds.Cy, yp.shape[-2:]
+        if yp.dim() < 3 or yp.shape[-3] != Cy or yt.shape != yp.shape:
+            raise ValueError(f"metrics: y_pred and y must be [..., {Cy}, H, W], got {tuple(yp.shape)} and {tuple(yt.shape)}")
+        n_frames = yp.numel() // (Cy * H * W)
+        m = None
+        if use_mask and mask is not None:
+            m = ops._dev(mask.contiguous().float(), torch.float32, "mask")
+            if m.numel() != n_frames * H * W:
+                raise ValueError(f"metrics: the mask of a vector target has one channel, [..., 1, {H}, {W}]; got {tuple(m.shape)}")
+        if self.sv is None:
+            self.sv = torch.zeros((Cy, 4), dtype=torch.float64, device=yp.device)
+        partials = torch.empty((int(L.lib.uclstm_metric_sums_vec_rows(n_frames, Cy, H * W)), Cy, 4), dtype=torch.float64, device=yp.device)
+        ops._log_reduce("metric_sums_vec")
+        L.check(L.lib.uclstm_metric_sums_vec(ops._p(yp), ops._p(yt), ops._p(m), ops._p(partials), ops._p(self.sv), 1, n_frames, Cy, H * W,
+                                             _TRANSFORM_IDS[ds.y_transform], ds.target_consts(), ops._stream()), "metric_sums_vec")
 
     @torch.no_grad()
     def add(self, dataset_obj, y, y_pred, mask, use_mask):
+        if isinstance(dataset_obj, VectorNPZDataset):
+            return self._add_vec(dataset_obj, y, y_pred, mask, use_mask)
         if y_pred.is_cuda and getattr(dataset_obj, "y_transform", None) == "asinh" and hasattr(dataset_obj, "trans_min"):
             # one fused kernel: de-normalise both, difference, masked running sums (no intermediate tensors)
             from . import _lib as L
@@ -1166,10 +1495,21 @@ class _Metrics:
                                    torch.tensor(float(d.numel()), dtype=torch.float64, device=d.device)))
 
     def result(self):
-        a, q, e, n = (float(v) for v in self.s.cpu())
+        """``(mae, rmse, me)``; for a vector dataset pooled over the channels (the sums of all channels added in channel order)."""
+        a, q, e, n = (float(v) for v in (self.s if self.sv is None else self.sv.sum(dim=0)).cpu())
         if n <= 0:
             return 0.0, 0.0, 0.0
         return a / n, math.sqrt(q / n), e / n
+
+    def per_channel(self):
+        """``{"mae": [Cy], "rmse": [Cy], "me": [Cy]}``; a scalar dataset is one channel."""
+        rows = (self.s.reshape(1, 4) if self.sv is None else self.sv).cpu().tolist()
+        out = {"mae": [], "rmse": [], "me": []}
+        for a, q, e, n in rows:
+            out["mae"].append(a / n if n > 0 else 0.0)
+            out["rmse"].append(math.sqrt(q / n) if n > 0 else 0.0)
+            out["me"].append(e / n if n > 0 else 0.0)
+        return out
 
 
 def quiesce_host_gc() -> None:
@@ -1187,8 +1527,11 @@ def quiesce_host_gc() -> None:
     gc.freeze()
 
 
-def train_one_epoch(model, loader, optimizer, device, dataset_obj, use_mask=True, ddp=None, loss: Optional[LossSpec] = None):
-    """Reference main.py:77-144; returns ``(avg_loss, avg_mae, avg_rmse, avg_me)``.  ``loss``: as in ``train_step``."""
+def train_one_epoch(model, loader, optimizer, device, dataset_obj, use_mask=True, per_channel: bool = False, ddp=None,
+                    loss: Optional[LossSpec] = None):
+    """Reference main.py:77-144; returns ``(avg_loss, avg_mae, avg_rmse, avg_me)``.  ``loss``: as in ``train_step``.
+    For a ``VectorNPZDataset`` the three metrics are pooled over the target channels; ``per_channel=True`` appends
+    ``{"mae": [Cy], "rmse": [Cy], "me": [Cy]}``."""
     spec = check_spec(loss)
     model.train()
     total = torch.zeros((), dtype=torch.float64, device=device)
@@ -1203,13 +1546,17 @@ def train_one_epoch(model, loader, optimizer, device, dataset_obj, use_mask=True
         n += x.size(0)
         met.add(dataset_obj, y, y_pred, mask, use_mask)
     mae, rmse, me = met.result()
-    return float(total) / max(n, 1), mae, rmse, me
+    return (float(total) / max(n, 1), mae, rmse, me) + ((met.per_channel(),) if per_channel else ())
 
 
 @torch.no_grad()
-def evaluate(model, loader, device, dataset_obj, use_mask=True, tta=None, loss: Optional[LossSpec] = None):
+def evaluate(model, loader, device, dataset_obj, use_mask=True, per_channel: bool = False, tta=None, loss: Optional[LossSpec] = None):
     """Reference main.py:150-205.  ``tta``: None, or the ``codes`` of ``predict_tta`` (``"flips"``, ``"d4"``, an iterable): the
-    prediction is then the test-time-augmented mean.  ``loss``: the ``LossSpec`` whose value is averaged (None: the reference's)."""
+    prediction is then the test-time-augmented mean.  ``loss``: the ``LossSpec`` whose value is averaged (None: the reference's).
+    A ``VectorNPZDataset`` as ``dataset_obj``: the averaged outputs come back with their channels turned (``predict_tta(dataset=)``),
+    the three metrics are pooled over the target channels, and ``per_channel=True`` appends
+    ``{"mae": [Cy], "rmse": [Cy], "me": [Cy]}``."""
+    vec = dataset_obj if isinstance(dataset_obj, VectorNPZDataset) else None
     spec = check_spec(loss)
     model.eval()
     total = torch.zeros((), dtype=torch.float64, device=device)
@@ -1217,13 +1564,13 @@ def evaluate(model, loader, device, dataset_obj, use_mask=True, tta=None, loss: 
     met = _Metrics(device)
     for x, y, mask in loader:
         x, y, mask = x.to(device, non_blocking=True), y.to(device, non_blocking=True), mask.to(device, non_blocking=True)
-        y_pred = _stack(model(x)[0]) if tta is None else predict_tta(model, x, tta)
+        y_pred = _stack(model(x)[0]) if tta is None else predict_tta(model, x, tta, dataset=vec)
         loss = compute_loss(y_pred, y, mask, use_mask, spec)
         total += loss.double() * x.size(0)
         n += x.size(0)
         met.add(dataset_obj, y, y_pred, mask, use_mask)
     mae, rmse, me = met.result()
-    return float(total) / max(n, 1), mae, rmse, me
+    return (float(total) / max(n, 1), mae, rmse, me) + ((met.per_channel(),) if per_channel else ())
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1253,6 +1600,7 @@ class EvalReport:
 
     def __init__(self, dataset_obj, hist_bins=100, hist_range=(-7.5, 7.5), err_range=(-3.0, 3.0), scatter_range=(-8.0, 8.0),
                  scatter_bin_width=0.05, points_per_bin=1000, seed=0, device="cuda"):
+        _refuse_vector(dataset_obj, "EvalReport")
         tr = getattr(dataset_obj, "y_transform", None)
         if tr not in _TRANSFORM_IDS:
             raise ValueError(f"EvalReport: unknown y_transform {tr!r}")
@@ -1417,6 +1765,7 @@ def evaluate_report(model, loader, device, dataset_obj, use_mask=True, tta=None,
     its loss and metric kernels add block partials with f64 atomics in arrival order, so two passes can differ in the last
     bits (~1e-13 relative); the report's own sums do not have that freedom.  (In deterministic mode, ``ops.deterministic()``, those
     kernels add their block partials in a fixed order and two passes are identical.)  ``tta`` and ``loss``: as in ``evaluate``."""
+    _refuse_vector(dataset_obj, "evaluate_report")
     spec = check_spec(loss)
     model.eval()
     total = torch.zeros((), dtype=torch.float64, device=device)

@@ -2413,9 +2413,22 @@ def loss_spec_desc(spec) -> "L.LossSpecDesc":
                           int(spec.grad_weight != 0))
 
 
+def _mask_broadcast(y_pred, m) -> int:
+    """Cy when the mask ``m`` has ONE channel (dim -3) where ``y_pred`` has Cy > 1 and all other dims agree; 1 otherwise."""
+    if m is None or y_pred.dim() < 3 or m.dim() != y_pred.dim():
+        return 1
+    Cy = int(y_pred.shape[-3])
+    if Cy > 1 and m.shape[-3] == 1 and m.shape[:-3] == y_pred.shape[:-3] and m.shape[-2:] == y_pred.shape[-2:]:
+        return Cy
+    return 1
+
+
 class LossFn(torch.autograd.Function):
     """``spec``: None = the reference's loss on uclstm_loss_fwd / _bwd; a loss.LossSpec = uclstm_loss_spec_fwd / _bwd (loss.py
-    sends the default spec here as None).  Both are logged as the reduction they are, loss_fwd / loss_fwd_ordered."""
+    sends the default spec here as None).  Both are logged as the reduction they are, loss_fwd / loss_fwd_ordered.
+    A mask with ONE channel over a ``y`` of several (``y [B,T,Cy,H,W]``, ``mask [B,T,1,H,W]``: a vector target under the loaders'
+    mask) is broadcast over the channels as main.py:40-43 does: uclstm_loss_spec_fwd_bc / _fwd_ordered_bc / _bwd_bc, where the
+    reference's loss runs as ``LossSpec.reference()``.  Every other shape takes the entry points above."""
 
     @staticmethod
     def forward(ctx, y_pred, y, mask, use_mask, spec=None):
@@ -2425,7 +2438,14 @@ class LossFn(torch.autograd.Function):
         planes = y_pred.numel() // (H * W)
         m = _dev(mask.contiguous().float(), F32, "mask") if (use_mask and mask is not None) else None
         desc = None if spec is None else loss_spec_desc(spec)
-        ctx.desc = desc
+        # a one-channel mask over a target of Cy > 1 channels is broadcast (main.py:40-43, :64-66): the _bc entry points, on
+        # which the reference's loss runs as its own LossSpec.  Every other shape keeps the entry points it always took.
+        Cy = _mask_broadcast(y_pred, m)
+        if Cy > 1 and desc is None:
+            desc = L.LossSpecDesc(L.LOSS_POINT_L1, 3, 1.0, 4.0, 1)
+        ctx.desc, ctx.mask_div = desc, Cy
+        if Cy > 1:
+            return LossFn._forward_bc(ctx, y_pred, y, m, spec, desc, Cy)
         if _DETERMINISTIC:
             sums = torch.empty((4,), dtype=torch.float64, device=y_pred.device)
             partials = torch.empty((int(L.lib.uclstm_loss_fwd_ordered_rows(planes, H, W)), 4), dtype=torch.float64, device=y_pred.device)
@@ -2444,6 +2464,29 @@ class LossFn(torch.autograd.Function):
             else:
                 L.check(L.lib.uclstm_loss_spec_fwd(C.byref(desc), _p(y_pred), _p(y), _p(m), _p(sums), planes, H, W, _stream()),
                         "loss_spec_fwd")
+        return LossFn._finish(ctx, y_pred, y, m, spec, sums)
+
+    @staticmethod
+    def _forward_bc(ctx, y_pred, y, m, spec, desc, Cy):
+        H, W = y_pred.shape[-2], y_pred.shape[-1]
+        planes = y_pred.numel() // (H * W)
+        if _DETERMINISTIC:
+            sums = torch.empty((4,), dtype=torch.float64, device=y_pred.device)
+            partials = torch.empty((int(L.lib.uclstm_loss_fwd_ordered_rows(planes, H, W)), 4), dtype=torch.float64, device=y_pred.device)
+            _log_reduce("loss_fwd_ordered")
+            L.check(L.lib.uclstm_loss_spec_fwd_ordered_bc(C.byref(desc), _p(y_pred), _p(y), _p(m), _p(partials), _p(sums), 0, planes, H, W,
+                                                          Cy, _stream()), "loss_spec_fwd_ordered_bc")
+        else:
+            sums = torch.zeros((4,), dtype=torch.float64, device=y_pred.device)
+            _log_reduce("loss_fwd")
+            L.check(L.lib.uclstm_loss_spec_fwd_bc(C.byref(desc), _p(y_pred), _p(y), _p(m), _p(sums), planes, H, W, Cy, _stream()),
+                    "loss_spec_fwd_bc")
+        return LossFn._finish(ctx, y_pred, y, m, spec, sums)
+
+    @staticmethod
+    def _finish(ctx, y_pred, y, m, spec, sums):
+        H, W = y_pred.shape[-2], y_pred.shape[-1]
+        planes = y_pred.numel() // (H * W)
         eps, gw = (1e-8, 0.005) if spec is None else (float(spec.eps), float(spec.grad_weight))
         n1 = float(y_pred.numel())
         n2 = float(planes * (H - 1) * (W - 1))
@@ -2469,7 +2512,10 @@ class LossFn(torch.autograd.Function):
         planes = y_pred.numel() // (H * W)
         grad = torch.empty_like(y_pred)
         coefs = torch.stack((c1 * g, c2 * g)).float().contiguous()      # stays on device: no host sync in the step
-        if ctx.desc is None:
+        if ctx.mask_div > 1:
+            L.check(L.lib.uclstm_loss_spec_bwd_bc(C.byref(ctx.desc), _p(y_pred), _p(y), _p(m), _p(coefs), _p(grad), planes, H, W,
+                                                  ctx.mask_div, _stream()), "loss_spec_bwd_bc")
+        elif ctx.desc is None:
             L.check(L.lib.uclstm_loss_bwd(_p(y_pred), _p(y), _p(m), _p(coefs), _p(grad), planes, H, W, _stream()), "loss_bwd")
         else:
             L.check(L.lib.uclstm_loss_spec_bwd(C.byref(ctx.desc), _p(y_pred), _p(y), _p(m), _p(coefs), _p(grad), planes, H, W, _stream()),
