@@ -287,7 +287,7 @@ __device__ __forceinline__ void igemm_fwd_body(const uclstm_igemm_desc& d, const
                 }
                 const int toff = (tap / 3 - 1) * W1 + (tap % 3 - 1);
                 const unsigned char* const Wt = Wring + slot * WSLOT;
-                act16x8 wf[4], xf[4];
+                act16x8 wf[2][4], xf[2][4];
                 int xaddr[4];
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
@@ -295,18 +295,33 @@ __device__ __forceinline__ void igemm_fwd_body(const uclstm_igemm_desc& d, const
                     xaddr[b] = r * 128 + ((lq ^ (r & 7)) << 4);
                 }
                 const int choffw = (lq ^ (l15 & 7)) << 4;
+                // Both 32-deep halves have a fragment set of their own: the eight reads of the second half are slotted one
+                // after each of the first eight MFMAs of the first half, so only the first half's reads (right behind the
+                // barrier) are waited for in full.  Never across the barrier: the sched_barrier below keeps every MFMA of
+                // this step -- and with them the reads they consume -- in front of the next step's s_barrier, behind which
+                // the DMA overwrites this step's ring slot (and, at a chunk boundary, the patch buffer just read).
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) wf[a] = *(const act16x8*)(Wt + (wc * 64 + a * 16 + l15) * 128 + (choffw ^ (h << 6)));
+                    for (int a = 0; a < 4; ++a) wf[h][a] = *(const act16x8*)(Wt + (wc * 64 + a * 16 + l15) * 128 + (choffw ^ (h << 6)));
 #pragma unroll
-                    for (int b = 0; b < 4; ++b) xf[b] = *(const act16x8*)(P + (xaddr[b] ^ (h << 6)));
+                    for (int b = 0; b < 4; ++b) xf[h][b] = *(const act16x8*)(P + (xaddr[b] ^ (h << 6)));
+                }
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
 #pragma unroll
                     for (int a = 0; a < 4; ++a)
 #pragma unroll
                         for (int b = 0; b < 4; ++b)
-                            acc[a][b] = UCLSTM_MFMA_16x16x32(wf[a], xf[b], acc[a][b], 0, 0, 0);
+                            acc[a][b] = UCLSTM_MFMA_16x16x32(wf[h][a], xf[h][b], acc[a][b], 0, 0, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);         // the first half's 8 DS reads
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // 1 MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);     // 1 DS read of the second half
                 }
+                __builtin_amdgcn_sched_group_barrier(0x008, 24, 0);        // the other 24 MFMAs
+                __builtin_amdgcn_sched_barrier(0);                         // nothing of this step moves behind the next barrier
                 slot = slot + 1 >= 3 ? 0 : slot + 1;
             }
         }
@@ -958,9 +973,23 @@ __global__ __launch_bounds__(256, 1) void igemm_fwd_c64_kernel(const uclstm_igem
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // 18 steps (tap, 32-channel half), software-pipelined by hand: the fragments of step s+1 are read while the 16 MFMAs of
-        // step s issue (one wave per SIMD: nobody else hides an LDS round trip), one ds_read slotted after each of the first
-        // eight MFMAs of a step
+        // 18 steps (tap, 32-channel half), software-pipelined by hand: the eight fragment reads of step s+1 go into the other
+        // register set while the 16 MFMAs of step s issue (one wave per SIMD: nobody else hides an LDS round trip), one ds_read
+        // slotted after each of the first eight MFMAs of a step.  The sched_group_barrier groups of a scheduling region are
+        // matched in program order, so the eight reads of the prologue need a group of their own: without it they take the
+        // first eight "1 DS read" groups, every later group then describes the step before its own, and the scheduler folds
+        // the two register sets into one -- three of four pixel fragments read inside the step that consumes them, each
+        // followed by a full lgkmcnt(0) (64 exposed round trips per tile).  With it the emitted step is
+        //     |3| M r |3| M r |3| M r |3| M r M r M r M r M r MMMMMMMM
+        // -- every wait is counted and names reads issued at least eight MFMAs earlier; only step 0 waits for its own reads.
+        // (tools/audit_lds_waits.py prints this string from the code object; tests/test_fwd_read_pipeline.py asserts it.)
+        // Hazards against the ring:
+        //   * the first reads of tile t+1 are LDS loads behind the `vmcnt(0)` + __syncthreads() that open it (a fence the
+        //     compiler does not move loads across), so they see the landed rows;
+        //   * every read of tile t feeds an MFMA of tile t, those MFMAs feed the epilogue's global stores, and the stores stay
+        //     in front of the next tile's `asm volatile(... "memory")` wait: the wave arrives at that barrier with no fragment
+        //     read outstanding (the emitted tail is `|0|` + 17 MFMAs), so the rows prefetched after it overwrite only slots
+        //     whose reads have returned.  No read is consumed only after a barrier.
         const unsigned char* rowp[3];
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) rowp[dy] = Ring + ((v0 + wave + dy) % C64_SLOTS) * C64_ROW;      // virtual row v0 + wave + dy - 1
@@ -974,6 +1003,7 @@ __global__ __launch_bounds__(256, 1) void igemm_fwd_c64_kernel(const uclstm_igem
             for (int b = 0; b < 4; ++b) xf[set][b] = *(const act16x8*)(rowp[dy] + xoff[b][dx][kk]);
         };
         load_step(0, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);                 // the prologue's 8 DS reads
 #pragma unroll
         for (int st = 0; st < 18; ++st) {
             if (st + 1 < 18) load_step(st + 1, (st + 1) & 1);
