@@ -659,8 +659,10 @@ typedef struct {
  * allocated, copied or synchronised.  aug == NULL: no remap (code 0, window at the origin, t0 = 0).
  * Bit for bit: without aug, channel c equals uclstm_dataset_gather_transform on channel c with consts[c]; with aug, the batch
  * equals the plain call on the raw data moved with flip / transpose / channel permutation / negation; with Cy = 1 and an
- * identity chan_map it equals uclstm_dataset_gather_augment.  flags, the clamping of idx and of the table, the conditions of the
- * 16-byte path and the tile mover are those of uclstm_dataset_gather_augment.  f32 only (no _f16 twin).
+ * identity chan_map it equals uclstm_dataset_gather_augment.  Both entry points launch ONE kernel, so flags, the clamping of idx
+ * and of the table, the conditions of the 16-byte path and the tile mover are those of uclstm_dataset_gather_augment; Cy = 1 (from
+ * either entry point) has instantiations of its own, in which the loop over further target channels does not exist.  f32 only (no
+ * _f16 twin).
  * UCLSTM_E_BADARG before any launch for: Cy outside [1, UCLSTM_VEC_MAX], a NULL x_all / y_all / x / y / mask / consts, y_scale <= 0
  * under transforms 1 / 2, trans_max == trans_min, and the limits of uclstm_dataset_gather_augment with Cy in the products
  * (n_out * T_out * Cy * Ho * Wo < 2^31, Cy * Hs * Ws < 2^31). */
@@ -673,7 +675,9 @@ int32_t uclstm_dataset_gather_vec(const float* x_all, const float* y_all, const 
  * NORMALISED vector predictions: src f32 [n_frames][Cy][H][W], dst [n_frames][Cy][H][W] ([W][H] for codes with t),
  *   dst[f][c] = (accumulate ? dst[f][c] : 0) + scale * (s * move(src[f][source channel]) + offset[c]),  s = -1 with bit 7, else 1,
  * evaluated in that order in f32.  chan_map HOST int8 [Cy] (one row of the table above, NULL = identity), offset HOST f32 [Cy]
- * (NULL = zeros); both travel as kernel arguments.  src and dst must not overlap.  UCLSTM_E_BADARG for a NULL src / dst, Cy
+ * (NULL = zeros); both travel as kernel arguments.  The kernel is uclstm_plane_d4's: that entry point is Cy = 1 with the identity
+ * map and the offset -0.f, which leaves every value as it is (+0.f, the NULL here, turns a -0.f into +0.f and nothing else).
+ * src and dst must not overlap.  UCLSTM_E_BADARG for a NULL src / dst, Cy
  * outside [1, UCLSTM_VEC_MAX], code outside [0, 7], sizes <= 0, n_frames * Cy * H * W >= 2^31. */
 int32_t uclstm_plane_d4_vec(const float* src, float* dst, int64_t n_frames, int32_t Cy, int32_t H, int32_t W, int32_t code,
         const int8_t* chan_map /* HOST [Cy], as above */, const float* offset /* HOST [Cy] */, int32_t accumulate, float scale, void* stream);

@@ -25,7 +25,7 @@ DEV = "cuda"
 TRANSFORMS = ["asinh", "signed_log", None]
 # case -> (N, T, C, Cy, H, W, axes)
 SHAPES = {"40": (3, 2, 2, 3, 40, 40, VC.AXES_UVW), "5x7": (5, 1, 2, 2, 5, 7, ("-w", "+h")), "c3": (4, 3, 3, 4, 4, 8, ("+h", None, "-w", None)),
-          "12": (10, 3, 2, 3, 12, 12, VC.AXES_UVW), "8": (3, 4, 2, 2, 8, 8, ("+w", "+h")), "one": (3, 4, 2, 1, 8, 8, (None,))}
+          "12": (10, 3, 2, 3, 12, 12, VC.AXES_UVW), "8": (3, 4, 2, 2, 8, 8, ("+w", "+h")), "one": (3, 4, 2, 1, 8, 8, (None,)), "one_neg": (3, 4, 2, 1, 8, 8, ("-w",))}
 _cache = {}
 
 
@@ -58,22 +58,24 @@ def _idx(idx):
     return torch.tensor(idx, dtype=torch.int64, device=DEV)
 
 
-def _moved_raw(ds, xa, ya, idx, tab, shape):
-    """The raw data of rows ``idx`` moved on the host side of the check: window, flip / transpose, channel map with negation."""
+def _moved_raw(ds, xa, ya, idx, tab, shape, cmap=None):
+    """The raw data of rows ``idx`` moved on the host side of the check: window, flip / transpose, channel map with negation
+    (``cmap(code)``; None: the dataset's ``channel_map``)."""
+    cmap = cmap or ds.channel_map
     To, Ho, Wo = shape
     xs, ys = [], []
     for row, (code, oy, ox, t0) in zip(idx, tab):
         Hc, Wc = (Wo, Ho) if code & 4 else (Ho, Wo)
         xs.append(torch_move(xa[row, t0:t0 + To, :, oy:oy + Hc, ox:ox + Wc], code))
-        ys.append(VC.apply_map(ya[row, t0:t0 + To, :, oy:oy + Hc, ox:ox + Wc], code, ds.channel_map(code)))
+        ys.append(VC.apply_map(ya[row, t0:t0 + To, :, oy:oy + Hc, ox:ox + Wc], code, cmap(code)))
     return torch.stack(xs).contiguous(), torch.stack(ys).contiguous()
 
 
-def _run_and_compare(made_case, idx, tab, shape, flags, what):
+def _run_and_compare(made_case, idx, tab, shape, flags, what, cmap=None):
     """Equality (b): the augmented batch equals the PLAIN vector gather (aug = NULL) of the raw data moved with torch."""
     ds, xa, ya, _ = made_case
     got = E._gather_vec(ds, xa, ya, _idx(idx), _table(tab), len(idx), shape, flags)
-    xr, yr = _moved_raw(ds, xa, ya, idx, tab, shape)
+    xr, yr = _moved_raw(ds, xa, ya, idx, tab, shape, cmap)
     want = E._gather_vec(ds, xr, yr, None, None, len(idx), shape, 2)
     for g, w, name, ch in zip(got, want, ("x", "y", "mask"), (xa.shape[2], ds.Cy, 1)):
         assert tuple(g.shape) == (len(idx), shape[0], ch, shape[1], shape[2]) and g.is_contiguous(), (what, name)
@@ -95,7 +97,7 @@ class _Scalar:
 
 @pytest.mark.parametrize("clip", [True, False])
 @pytest.mark.parametrize("transform", TRANSFORMS, ids=str)
-@pytest.mark.parametrize("case", ["40", "5x7", "c3"])
+@pytest.mark.parametrize("case", ["40", "5x7", "c3", "one_neg"])
 def test_plain_gather_equals_the_scalar_kernel_per_channel(made, case, transform, clip):
     ds, xa, ya, plain = made(case, transform, clip)
     idx = [len(ds) - 1, 0, 1, 1]
@@ -168,6 +170,43 @@ def test_one_scalar_channel_equals_the_scalar_augment_kernel(made, transform, sh
     want = E._gather_augment(_Scalar(ds, 0), xa, ya, _idx(idx), tab, 8, shape, flags)
     for g, w, name in zip(got, want, ("x", "y", "mask")):
         assert torch.equal(g, w), f"{transform} {shape}: {name} differs in {int((g != w).sum())} of {g.numel()} elements"
+
+
+# ... and one channel whose map negates: what only the instantiation for Cy = 1 can get wrong
+@pytest.mark.parametrize("transform", TRANSFORMS, ids=str)
+@pytest.mark.parametrize("shape,flags,oyx", [((4, 8, 8), 3, (0, 0)), ((3, 5, 5), 1, (1, 3))])
+def test_one_channel_that_negates_under_mirrors(made, transform, shape, flags, oyx):
+    """Cy = 1, axes ("-w",): the channel changes sign under h.  With a single horizontal channel ``channel_map`` refuses the codes
+    with t and ``chan_map_table`` holds identity rows for them, so the reference reads the rows the kernel is given."""
+    case = made("one_neg", transform, True)
+    ds = case[0]
+    table = ds.chan_map_table().view(np.uint8)
+
+    def cmap(code):
+        return [(int(table[code, 0]) & 7, bool(table[code, 0] & 0x80))]
+    assert all(cmap(k) == ds.channel_map(k) for k in range(4))
+    assert [cmap(k)[0][1] for k in range(8)] == [False, True, False, True, False, False, False, False]      # not vacuous: codes 1, 3 negate
+    tab = [[k, oyx[0], oyx[1], k % (5 - shape[0])] for k in range(8)]
+    _, y, _ = _run_and_compare(case, [2, 0, 2, 1, 0, 2, 1, 1], tab, shape, flags, f"one_neg {transform} {shape}", cmap)
+    assert not torch.equal(y[0], y[2])                                     # the same row and window under code 0 and code 2
+
+
+def test_both_instantiations_in_one_process_agree_on_x_and_mask(made):
+    """One launch at Cy = 2 and one at Cy = 1 over the same x_all, both without a table: x and mask do not know about Cy, and target
+    channel 0 (identity map, the same constants) does not either."""
+    ds, xa, ya, _ = made("8")
+    N, T, Cc, H, W = xa.shape
+    consts = ds.target_consts()
+    outs = []
+    for Cy, y_all in ((2, ya), (1, ya[:, :, :1].contiguous())):
+        out = tuple(torch.empty(N, T, c, H, W, device=DEV) for c in (Cc, Cy, 1))
+        L.check(L.lib.uclstm_dataset_gather_vec(ops._p(xa), ops._p(y_all), None, None, N, N, T, T, Cc, Cy, H, W, H, W, 2, None,
+                                                ops._p(out[0]), ops._p(out[1]), ops._p(out[2]), 1, float(ds.norm_const), 1, consts,
+                                                ops._stream()), "gather_vec")
+        outs.append(out)
+    (x2, y2, m2), (x1, y1, m1) = outs
+    assert torch.equal(x2, x1) and torch.equal(m2, m1)
+    assert torch.equal(y2[:, :, :1], y1)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -334,7 +373,7 @@ def test_a_scalar_dataset_still_launches_only_the_old_entry_points(tmp_path, mon
 # plane_d4_vec
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("code", range(8))
-@pytest.mark.parametrize("shape", [(3, 3, 5, 7), (2, 2, 33, 40), (2, 4, 36, 40)])
+@pytest.mark.parametrize("shape", [(3, 3, 5, 7), (2, 2, 33, 40), (2, 4, 36, 40), (3, 1, 5, 7), (2, 1, 36, 40)])
 def test_plane_d4_vec_equals_signed_plane_d4_per_channel(shape, code):
     t = torch.randn(shape, generator=_G(sum(shape)), dtype=torch.float32).to(DEV)
     Cy = shape[1]
@@ -364,6 +403,14 @@ def test_plane_d4_vec_equals_signed_plane_d4_per_channel(shape, code):
         U.plane_d4_vec(t, 8, affine)
     with pytest.raises(ValueError):
         U.plane_d4_vec(t, code, affine[:-1] + [(Cy, 1.0, 0.0)])
+
+
+def test_plane_d4_keeps_the_sign_of_a_zero():
+    """uclstm_plane_d4 runs the kernel of uclstm_plane_d4_vec with the offset -0.f: v + -0.f is v for v = -0.f too (+0.f would not be)."""
+    t = torch.tensor([0.0, -0.0, 1.5, -2.0] * 10, device=DEV).reshape(1, 5, 8)
+    for code in (0, 3, 5):
+        got = U.plane_d4(t, code)
+        assert torch.equal(got.view(torch.int32), torch_move(t, code).contiguous().view(torch.int32)), code
 
 
 def test_plane_d4_vec_clamps_the_source_channel():

@@ -116,148 +116,17 @@ __device__ __forceinline__ void store_slot(float* __restrict__ p, const D4Tile& 
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// dataset_gather_transform_kernel with a per-sequence remap: output sequence o reads table row aug[o] = {code, oy, ox, t0}, uniform
-// per block iteration like the sequence index, and clamped like it (code & 7, or & 3 without flag bit 0; the window kept inside the
-// source; on the 16-byte path ox rounded down to a multiple of 4) -- a bad table never becomes a wild read.
-// The mask is taken at the SOURCE pixel: it travels with channel 0.  CT as in the plain kernel (2: all loads before the first store).
-template <int V, int CT>
-__global__ __launch_bounds__(NT) void dataset_gather_augment_kernel(
-        const float* __restrict__ xa, const float* __restrict__ ya, const int64_t* __restrict__ idx, const int32_t* __restrict__ aug,
-        int64_t n_seq, int n_chunks, FastDiv dTiles, FastDiv dTj, FastDiv dT, int T_src, int Crt, int Hs, int Ws, int Ho, int Wo, int flags,
-        float* __restrict__ x, float* __restrict__ y, float* __restrict__ mask, int transform, float inv_norm, float min_vel,
-        float max_vel, int clip, float inv_yscale, float tmin, float inv_trange) {
-    __shared__ float tile[3][TS * TP];
-    const int C = CT > 0 ? CT : Crt;
-    const int T = (int)dT.d, HWs = Hs * Ws, HWo = Ho * Wo;
-    for (int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        const uint32_t f = fdiv((uint32_t)chunk, dTiles);           // output frame = o * T + t
-        const uint32_t tl = (uint32_t)chunk - f * dTiles.d;
-        const uint32_t ti = fdiv(tl, dTj);
-        const uint32_t o = fdiv(f, dT);                             // output sequence
-        int64_t row = idx ? idx[o] : (int64_t)o;
-        row = row < 0 ? 0 : (row >= n_seq ? n_seq - 1 : row);
-        const int32_t* ar = aug + (int64_t)o * 4;
-        const int code = ar[0] & ((flags & 1) ? 7 : 3);             // codes with t only where the host vouches for Ho == Wo
-        const int oy = clampi(ar[1], 0, Hs - Ho);
-        int ox = clampi(ar[2], 0, Ws - Wo);
-        if (V == 4) ox &= ~3;
-        const int t0 = clampi(ar[3], 0, T_src - T);
-        const D4Tile g = d4_tile(code, Ho, Wo, (int)ti, (int)(tl - ti * dTj.d));
-        const int64_t sf = row * T_src + t0 + (int64_t)(f - o * (uint32_t)T);   // source frame
-        const int org = oy * Ws + ox;
-        const float* xs = xa + sf * C * HWs + org;
-        float* xd = x + (int64_t)f * C * HWo;
-        const int64_t od = (int64_t)f * HWo;
-        float v[4], c0[4], m[4];
-        d4_load<V>(ya + sf * HWs + org, Ws, g, v);
-        d4_load<V>(xs, Ws, g, c0);
-        if constexpr (CT > 0) {
-            static_assert(CT <= 2, "one LDS plane per channel plus the target");
-            float cc[CT > 1 ? CT - 1 : 1][4];
-#pragma unroll
-            for (int c = 1; c < CT; ++c) d4_load<V>(xs + (int64_t)c * HWs, Ws, g, cc[c - 1]);
-            if (g.tr) {
-                d4_put<V>(tile[0], v);
-                d4_put<V>(tile[1], c0);
-#pragma unroll
-                for (int c = 1; c < CT; ++c) d4_put<V>(tile[1 + c], cc[c - 1]);
-                __syncthreads();
-                d4_get<V>(tile[0], v);
-                d4_get<V>(tile[1], c0);
-#pragma unroll
-                for (int c = 1; c < CT; ++c) d4_get<V>(tile[1 + c], cc[c - 1]);
-                __syncthreads();                                    // the next iteration writes the tiles again
-            }
-#pragma unroll
-            for (int c = 1; c < CT; ++c) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) cc[c - 1][k] *= inv_norm;
-                store_slot<V>(xd + (int64_t)c * HWo, g, cc[c - 1]);
-            }
-        } else {
-            if (g.tr) {
-                d4_put<V>(tile[0], v);
-                d4_put<V>(tile[1], c0);
-                __syncthreads();
-                d4_get<V>(tile[0], v);
-                d4_get<V>(tile[1], c0);
-            }
-            for (int c = 1; c < C; ++c) {
-                float r[4];
-                d4_load<V>(xs + (int64_t)c * HWs, Ws, g, r);
-                if (g.tr) {
-                    d4_put<V>(tile[2], r);
-                    __syncthreads();
-                    d4_get<V>(tile[2], r);
-                    __syncthreads();
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) r[k] *= inv_norm;
-                store_slot<V>(xd + (int64_t)c * HWo, g, r);
-            }
-            if (g.tr) __syncthreads();
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            m[k] = c0[k] > 1.1f ? 1.f : 0.f;
-            c0[k] *= inv_norm;
-            float w = v[k];
-            if (clip) w = fminf(fmaxf(w, min_vel), max_vel);
-            v[k] = 2.f * (target_fwd(w, transform, inv_yscale) - tmin) * inv_trange - 1.f;
-        }
-        store_slot<V>(xd, g, c0);
-        store_slot<V>(mask + od, g, m);
-        store_slot<V>(y + od, g, v);
-    }
-}
-
-// dst = (accumulate ? dst : 0) + scale * move(src) over n planes of H x W: the same tile mover, one plane per block iteration's tile
-template <int V>
-__global__ __launch_bounds__(NT) void plane_d4_kernel(const float* __restrict__ src, float* __restrict__ dst, int n_chunks,
-                                                      FastDiv dTiles, FastDiv dTj, int H, int W, int code, int accumulate, float scale) {
-    __shared__ float tile[TS * TP];
-    const int HW = H * W;
-    for (int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        const uint32_t p = fdiv((uint32_t)chunk, dTiles);
-        const uint32_t tl = (uint32_t)chunk - p * dTiles.d;
-        const uint32_t ti = fdiv(tl, dTj);
-        const D4Tile g = d4_tile(code, H, W, (int)ti, (int)(tl - ti * dTj.d));
-        float r[4], d[4];
-        d4_load<V>(src + (int64_t)p * HW, W, g, r);
-        float* out = dst + (int64_t)p * HW;
-        if (accumulate) {                                           // uniform; dead lanes read their clamped slot
-            bool live;
-            if constexpr (V == 4) {
-                const f32x4 e = *reinterpret_cast<const f32x4*>(out + d4_out<4>(g, 0, live));
-#pragma unroll
-                for (int k = 0; k < 4; ++k) d[k] = e[k];
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) d[k] = out[d4_out<1>(g, k, live)];
-            }
-        }
-        if (g.tr) {
-            d4_put<V>(tile, r);
-            __syncthreads();
-            d4_get<V>(tile, r);
-            __syncthreads();
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = accumulate ? d[k] + scale * r[k] : scale * r[k];
-        store_slot<V>(out, g, r);
-    }
-}
-
-// ---- vector targets: Cy channels per frame, a move acts on the channels too (sign under mirrors, swap under transposes) ----
-// The two host tables of uclstm_dataset_gather_vec as ONE kernel argument (112 bytes of the kernarg segment: nothing to upload).
-// map[code]: byte c = the entry of output channel c (bits 0-2 source channel, bit 7 negate the raw value).  Every index into the
-// arrays below is a compile-time constant (unrolled loops), so they stay scalar registers.
-struct VecTables {
+// The host tables of a gather as ONE kernel argument (52 bytes of the kernarg segment for CYMAX = 1, 112 for UCLSTM_VEC_MAX:
+// nothing to upload).  map[code]: byte c = the entry of output channel c (bits 0-2 source channel, bit 7 negate the raw value; a
+// move acts on vector channels too: sign under mirrors, swap under transposes).  Every index into the arrays below is a
+// compile-time constant (unrolled loops), so they stay scalar registers.
+template <int CYMAX>
+struct GatherTables {
     uint32_t map[8];
-    float min_vel[UCLSTM_VEC_MAX], max_vel[UCLSTM_VEC_MAX], inv_yscale[UCLSTM_VEC_MAX], tmin[UCLSTM_VEC_MAX], inv_trange[UCLSTM_VEC_MAX];
+    float min_vel[CYMAX], max_vel[CYMAX], inv_yscale[CYMAX], tmin[CYMAX], inv_trange[CYMAX];
 };
 
-// the per-pixel target arithmetic of dataset_gather_augment_kernel; `flip` = 0x80000000 negates the RAW value first
+// the per-pixel target arithmetic of dataset_gather_transform_kernel; `flip` = 0x80000000 negates the RAW value first
 __device__ __forceinline__ float target_px(float raw, uint32_t flip, int clip, float min_vel, float max_vel, int transform,
                                            float inv_yscale, float tmin, float inv_trange) {
     float w = __uint_as_float(__float_as_uint(raw) ^ flip);
@@ -265,21 +134,27 @@ __device__ __forceinline__ float target_px(float raw, uint32_t flip, int clip, f
     return 2.f * (target_fwd(w, transform, inv_yscale) - tmin) * inv_trange - 1.f;
 }
 
-// dataset_gather_augment_kernel for y_all [n_seq][T_src][Cy][Hs][Ws]: target channel 0 travels with the x channels exactly as the
-// one target does there (Cy = 1 is that kernel, load for load); channels 1 .. Cy-1 follow, one plane at a time through tile[0].
+// dataset_gather_transform_kernel with a per-sequence remap, for y_all [n_seq][T_src][Cy][Hs][Ws]: output sequence o reads table
+// row aug[o] = {code, oy, ox, t0}, uniform per block iteration like the sequence index, and clamped like it (code & 7, or & 3
+// without flag bit 0; the window kept inside the source; on the 16-byte path ox rounded down to a multiple of 4) -- a bad table
+// never becomes a wild read.  aug == NULL: code 0 at the origin of the source (the plain gather).
+// The mask is taken at the SOURCE pixel: it travels with channel 0.  CT as in the plain kernel (2: all loads before the first store).
+// CYMAX = 1 is the scalar target (and a one-channel vector dataset, which may still negate): Cy is the constant 1, so the tail
+// loop and the channel clamps fold away.  CYMAX = UCLSTM_VEC_MAX: Cy >= 2 at run time; target channel 0 travels with the x channels
+// exactly as the one target does, channels 1 .. Cy-1 follow, one plane at a time through tile[0].
 // Their loads are NOT hoisted above the first store: with asinh the kernel is bound by the per-pixel arithmetic (three asinhf per
-// 44 bytes where the scalar kernel has one per 28), and a channel's arithmetic then hides the next channel's loads; issuing all
+// 44 bytes where the scalar target has one per 28), and a channel's arithmetic then hides the next channel's loads; issuing all
 // loads first measured 7 % slower at Cy = 3 (profiles/vector_targets_ab.txt).
 // Output channel c reads the plane of source channel (entry & 7), clamped into [0, Cy) like everything else read from a table.
-// aug == NULL: code 0 at the origin of the source (the plain gather).
-template <int V, int CT>
-__global__ __launch_bounds__(NT) void dataset_gather_vec_kernel(
+template <int V, int CT, int CYMAX>
+__global__ __launch_bounds__(NT) void dataset_gather_tiles_kernel(
         const float* __restrict__ xa, const float* __restrict__ ya, const int64_t* __restrict__ idx, const int32_t* __restrict__ aug,
-        int64_t n_seq, int n_chunks, FastDiv dTiles, FastDiv dTj, FastDiv dT, int T_src, int Crt, int Cy, int Hs, int Ws, int Ho, int Wo,
-        int flags, float* __restrict__ x, float* __restrict__ y, float* __restrict__ mask, int transform, float inv_norm, int clip,
-        VecTables tb) {
+        int64_t n_seq, int n_chunks, FastDiv dTiles, FastDiv dTj, FastDiv dT, int T_src, int Crt, int Cyrt, int Hs, int Ws, int Ho,
+        int Wo, int flags, float* __restrict__ x, float* __restrict__ y, float* __restrict__ mask, int transform, float inv_norm,
+        int clip, GatherTables<CYMAX> tb) {
     __shared__ float tile[3][TS * TP];
     const int C = CT > 0 ? CT : Crt;
+    const int Cy = CYMAX > 1 ? Cyrt : 1;
     const int T = (int)dT.d, HWs = Hs * Ws, HWo = Ho * Wo;
     for (int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         const uint32_t f = fdiv((uint32_t)chunk, dTiles);           // output frame = o * T + t
@@ -368,7 +243,7 @@ __global__ __launch_bounds__(NT) void dataset_gather_vec_kernel(
         store_slot<V>(mask + od, g, m);
         store_slot<V>(yd, g, v);
 #pragma unroll
-        for (int c = 1; c < UCLSTM_VEC_MAX; ++c) {
+        for (int c = 1; c < CYMAX; ++c) {
             if (c < Cy) {                                           // uniform
                 const uint32_t e = mrow >> (8 * c);
                 float r[4];
@@ -389,28 +264,30 @@ __global__ __launch_bounds__(NT) void dataset_gather_vec_kernel(
     }
 }
 
-// plane_d4_kernel over frames of Cy channels: plane p = f * Cy + c reads the plane of its source channel, and
-// dst = (accumulate ? dst : 0) + scale * (+-move(src) + off[c]).  map: byte c = the entry of output channel c, as above.
-struct PlaneVecTables {
+// dst = (accumulate ? dst : 0) + scale * (+-move(src) + off[c]) over frames of Cy planes of H x W: the same tile mover, one plane
+// per block iteration's tile.  Plane p = f * Cy + c reads the plane of its source channel; map: byte c = the entry of output
+// channel c, as above.  CYMAX = 1: Cy is the constant 1 and p is the frame (the scalar mover, and a one-channel vector frame).
+template <int CYMAX>
+struct PlaneTables {
     uint32_t map;
-    float off[UCLSTM_VEC_MAX];
+    float off[CYMAX];
 };
-template <int V>
-__global__ __launch_bounds__(NT) void plane_d4_vec_kernel(const float* __restrict__ src, float* __restrict__ dst, int n_chunks,
-                                                          FastDiv dTiles, FastDiv dTj, FastDiv dCy, int H, int W, int code, int accumulate,
-                                                          float scale, PlaneVecTables tb) {
+template <int V, int CYMAX>
+__global__ __launch_bounds__(NT) void plane_d4_kernel(const float* __restrict__ src, float* __restrict__ dst, int n_chunks, FastDiv dTiles,
+                                                      FastDiv dTj, FastDiv dCy, int H, int W, int code, int accumulate, float scale,
+                                                      PlaneTables<CYMAX> tb) {
     __shared__ float tile[TS * TP];
-    const int HW = H * W, Cy = (int)dCy.d;
+    const int HW = H * W, Cy = CYMAX > 1 ? (int)dCy.d : 1;
     for (int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         const uint32_t p = fdiv((uint32_t)chunk, dTiles);
         const uint32_t tl = (uint32_t)chunk - p * dTiles.d;
         const uint32_t ti = fdiv(tl, dTj);
-        const uint32_t f = fdiv(p, dCy);
-        const int c = (int)(p - f * dCy.d);
+        const uint32_t f = CYMAX > 1 ? fdiv(p, dCy) : p;
+        const int c = (int)(p - f * (uint32_t)Cy);
         uint32_t e = tb.map;
         float off = tb.off[0];
 #pragma unroll
-        for (int k = 1; k < UCLSTM_VEC_MAX; ++k) {
+        for (int k = 1; k < CYMAX; ++k) {
             e = c == k ? tb.map >> (8 * k) : e;
             off = c == k ? tb.off[k] : off;
         }
@@ -437,7 +314,7 @@ __global__ __launch_bounds__(NT) void plane_d4_vec_kernel(const float* __restric
             __syncthreads();
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < 4; ++k) {                               // off = -0.f (uclstm_plane_d4) leaves every value as it is, -0.f too
             const float t = scale * (__uint_as_float(__float_as_uint(r[k]) ^ flip) + off);
             r[k] = accumulate ? d[k] + t : t;
         }
@@ -447,56 +324,12 @@ __global__ __launch_bounds__(NT) void plane_d4_vec_kernel(const float* __restric
 
 inline int tiles_of(int n) { return (n + TS - 1) / TS; }
 
-}  // namespace
-
-extern "C" int32_t uclstm_dataset_gather_augment(const float* x_all, const float* y_all, const int64_t* idx, const int32_t* aug,
-                                                 int64_t n_seq, int64_t n_out, int32_t T_src, int32_t T_out, int32_t C, int32_t Hs,
-                                                 int32_t Ws, int32_t Ho, int32_t Wo, int32_t flags, float* x, float* y, float* mask,
-                                                 int32_t transform, float norm_const, float min_vel, float max_vel, int32_t clip,
-                                                 float y_scale, float trans_min, float trans_max, void* stream) {
-    if (!x_all || !y_all || !aug || !x || !y || !mask || n_seq <= 0 || n_out <= 0 || T_src <= 0 || T_out <= 0 || C <= 0 || Hs <= 0 ||
-        Ws <= 0 || Ho <= 0 || Wo <= 0 || Ho > Hs || Wo > Ws || T_out > T_src || flags < 0 || flags > 3 || ((flags & 1) && Ho != Wo) ||
-        transform < 0 || transform > 2 || norm_const == 0.f || trans_max == trans_min || (transform != 0 && !(y_scale > 0.f)) ||
-        (!idx && n_out > n_seq))
-        return UCLSTM_E_BADARG;
-    if ((int64_t)Hs * Ws >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;         // Ho * Wo <= Hs * Ws: offsets inside a frame are ints
-    const int64_t frame_px = (int64_t)T_out * ((int64_t)Ho * Wo);              // < 2^62
-    if (n_out > (((int64_t)1 << 31) - 1) / frame_px) return UCLSTM_E_BADARG;    // n_out * T_out * Ho * Wo >= 2^31
-    // the 16-byte path must be valid for the whole launch: every row, every window start and every pointer on a 16-byte boundary
-    const bool vec = Ws % 4 == 0 && Wo % 4 == 0 && (flags & 2) &&
-                     (((uintptr_t)x_all | (uintptr_t)y_all | (uintptr_t)x | (uintptr_t)y | (uintptr_t)mask) % 16) == 0;
-    const int ntj = tiles_of(Wo), tiles = tiles_of(Ho) * ntj;
-    const int64_t n_chunks = n_out * T_out * tiles;                            // <= n_out * T_out * Ho * Wo < 2^31
-    const int grid = (int)(n_chunks < 2048 ? n_chunks : 2048);
-    const float inv_yscale = transform != 0 ? 1.0f / y_scale : 1.0f;
-#define UCLSTM_AUGMENT_LAUNCH(V, CT)                                                                                                      \
-    UCLSTM_LAUNCH((dataset_gather_augment_kernel<V, CT>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, x_all, y_all, idx, aug, n_seq,    \
-                  (int)n_chunks, make_fastdiv(tiles), make_fastdiv(ntj), make_fastdiv(T_out), T_src, C, Hs, Ws, Ho, Wo, flags, x, y, mask, \
-                  transform, 1.0f / norm_const, min_vel, max_vel, clip, inv_yscale, trans_min, 1.0f / (trans_max - trans_min))
-    if (vec) {
-        if (C == 2) UCLSTM_AUGMENT_LAUNCH(4, 2);
-        else UCLSTM_AUGMENT_LAUNCH(4, 0);
-    } else {
-        if (C == 2) UCLSTM_AUGMENT_LAUNCH(1, 2);
-        else UCLSTM_AUGMENT_LAUNCH(1, 0);
-    }
-#undef UCLSTM_AUGMENT_LAUNCH
-    return UCLSTM_OK;
-}
-
-extern "C" int32_t uclstm_dataset_gather_vec(const float* x_all, const float* y_all, const int64_t* idx, const int32_t* aug, int64_t n_seq,
-                                             int64_t n_out, int32_t T_src, int32_t T_out, int32_t C, int32_t Cy, int32_t Hs, int32_t Ws,
-                                             int32_t Ho, int32_t Wo, int32_t flags, const int8_t* chan_map, float* x, float* y,
-                                             float* mask, int32_t transform, float norm_const, int32_t clip,
-                                             const uclstm_target_consts* consts, void* stream) {
-    if (!x_all || !y_all || !x || !y || !mask || !consts || Cy < 1 || Cy > UCLSTM_VEC_MAX || n_seq <= 0 || n_out <= 0 || T_src <= 0 ||
-        T_out <= 0 || C <= 0 || Hs <= 0 || Ws <= 0 || Ho <= 0 || Wo <= 0 || Ho > Hs || Wo > Ws || T_out > T_src || flags < 0 || flags > 3 ||
-        ((flags & 1) && Ho != Wo) || transform < 0 || transform > 2 || norm_const == 0.f || (!idx && n_out > n_seq))
-        return UCLSTM_E_BADARG;
-    VecTables tb;
-    for (int c = 0; c < UCLSTM_VEC_MAX; ++c) {
+// the kernel tables from the host arrays of an entry point (chan_map NULL: identity; channels past Cy repeat channel 0)
+template <int CYMAX>
+GatherTables<CYMAX> gather_tables(int Cy, const int8_t* chan_map, const uclstm_target_consts* consts, int transform) {
+    GatherTables<CYMAX> tb;
+    for (int c = 0; c < CYMAX; ++c) {
         const uclstm_target_consts& k = consts[c < Cy ? c : 0];
-        if (k.trans_max == k.trans_min || (transform != 0 && !(k.y_scale > 0.f))) return UCLSTM_E_BADARG;
         tb.min_vel[c] = k.min_vel;
         tb.max_vel[c] = k.max_vel;
         tb.inv_yscale[c] = transform != 0 ? 1.0f / k.y_scale : 1.0f;
@@ -507,6 +340,31 @@ extern "C" int32_t uclstm_dataset_gather_vec(const float* x_all, const float* y_
         tb.map[code] = 0;
         for (int c = 0; c < Cy; ++c) tb.map[code] |= (uint32_t)(chan_map ? (uint8_t)chan_map[code * Cy + c] : (uint8_t)c) << (8 * c);
     }
+    return tb;
+}
+template <int CYMAX>
+PlaneTables<CYMAX> plane_tables(int Cy, const int8_t* chan_map, const float* offset) {
+    PlaneTables<CYMAX> tb;
+    tb.map = 0;
+    for (int c = 0; c < CYMAX; ++c) {
+        if (c < Cy) tb.map |= (uint32_t)(chan_map ? (uint8_t)chan_map[c] : (uint8_t)c) << (8 * c);
+        tb.off[c] = (offset && c < Cy) ? offset[c] : 0.f;
+    }
+    return tb;
+}
+
+// What the two gather entry points share: the argument checks, the 2^31 limits, the 16-byte-path condition, the grid and the
+// dispatch.  The caller vouches for 1 <= Cy <= UCLSTM_VEC_MAX and consts [Cy].
+int32_t gather_tiles(const float* x_all, const float* y_all, const int64_t* idx, const int32_t* aug, int64_t n_seq, int64_t n_out,
+                     int32_t T_src, int32_t T_out, int32_t C, int32_t Cy, int32_t Hs, int32_t Ws, int32_t Ho, int32_t Wo, int32_t flags,
+                     const int8_t* chan_map, float* x, float* y, float* mask, int32_t transform, float norm_const, int32_t clip,
+                     const uclstm_target_consts* consts, void* stream) {
+    if (!x_all || !y_all || !x || !y || !mask || n_seq <= 0 || n_out <= 0 || T_src <= 0 || T_out <= 0 || C <= 0 || Hs <= 0 || Ws <= 0 ||
+        Ho <= 0 || Wo <= 0 || Ho > Hs || Wo > Ws || T_out > T_src || flags < 0 || flags > 3 || ((flags & 1) && Ho != Wo) ||
+        transform < 0 || transform > 2 || norm_const == 0.f || (!idx && n_out > n_seq))
+        return UCLSTM_E_BADARG;
+    for (int c = 0; c < Cy; ++c)
+        if (consts[c].trans_max == consts[c].trans_min || (transform != 0 && !(consts[c].y_scale > 0.f))) return UCLSTM_E_BADARG;
     if ((int64_t)Cy * Hs * Ws >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;    // Ho * Wo <= Hs * Ws: offsets inside a frame are ints
     const int64_t frame_px = (int64_t)T_out * Cy * ((int64_t)Ho * Wo);         // < 2^62 + 2
     if (n_out > (((int64_t)1 << 31) - 1) / frame_px) return UCLSTM_E_BADARG;    // n_out * T_out * Cy * Ho * Wo >= 2^31
@@ -516,63 +374,84 @@ extern "C" int32_t uclstm_dataset_gather_vec(const float* x_all, const float* y_
     const int ntj = tiles_of(Wo), tiles = tiles_of(Ho) * ntj;
     const int64_t n_chunks = n_out * T_out * tiles;                            // <= n_out * T_out * Ho * Wo < 2^31
     const int grid = (int)(n_chunks < 2048 ? n_chunks : 2048);
-#define UCLSTM_VEC_LAUNCH(V, CT)                                                                                                        \
-    UCLSTM_LAUNCH((dataset_gather_vec_kernel<V, CT>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, x_all, y_all, idx, aug, n_seq,       \
-                  (int)n_chunks, make_fastdiv(tiles), make_fastdiv(ntj), make_fastdiv(T_out), T_src, C, Cy, Hs, Ws, Ho, Wo, flags, x, y, \
-                  mask, transform, 1.0f / norm_const, clip, tb)
-    if (vec) {
-        if (C == 2) UCLSTM_VEC_LAUNCH(4, 2);
-        else UCLSTM_VEC_LAUNCH(4, 0);
+#define UCLSTM_GATHER_LAUNCH(V, CT, CYMAX)                                                                                              \
+    UCLSTM_LAUNCH((dataset_gather_tiles_kernel<V, CT, CYMAX>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, x_all, y_all, idx, aug,     \
+                  n_seq, (int)n_chunks, make_fastdiv(tiles), make_fastdiv(ntj), make_fastdiv(T_out), T_src, C, Cy, Hs, Ws, Ho, Wo, flags, \
+                  x, y, mask, transform, 1.0f / norm_const, clip, gather_tables<CYMAX>(Cy, chan_map, consts, transform))
+#define UCLSTM_GATHER_CT(V, CYMAX)                  \
+    do {                                            \
+        if (C == 2) UCLSTM_GATHER_LAUNCH(V, 2, CYMAX); \
+        else UCLSTM_GATHER_LAUNCH(V, 0, CYMAX);     \
+    } while (0)
+    if (Cy == 1) {                                                              // the scalar target's own instantiations
+        if (vec) UCLSTM_GATHER_CT(4, 1);
+        else UCLSTM_GATHER_CT(1, 1);
     } else {
-        if (C == 2) UCLSTM_VEC_LAUNCH(1, 2);
-        else UCLSTM_VEC_LAUNCH(1, 0);
+        if (vec) UCLSTM_GATHER_CT(4, UCLSTM_VEC_MAX);
+        else UCLSTM_GATHER_CT(1, UCLSTM_VEC_MAX);
     }
-#undef UCLSTM_VEC_LAUNCH
+#undef UCLSTM_GATHER_CT
+#undef UCLSTM_GATHER_LAUNCH
     return UCLSTM_OK;
 }
 
-extern "C" int32_t uclstm_plane_d4_vec(const float* src, float* dst, int64_t n_frames, int32_t Cy, int32_t H, int32_t W, int32_t code,
-                                       const int8_t* chan_map, const float* offset, int32_t accumulate, float scale, void* stream) {
-    if (!src || !dst || n_frames <= 0 || Cy < 1 || Cy > UCLSTM_VEC_MAX || H <= 0 || W <= 0 || code < 0 || code > 7) return UCLSTM_E_BADARG;
+// the same for the two plane movers; the caller vouches for 1 <= Cy <= UCLSTM_VEC_MAX
+int32_t plane_tiles(const float* src, float* dst, int64_t n_frames, int32_t Cy, int32_t H, int32_t W, int32_t code, const int8_t* chan_map,
+                    const float* offset, int32_t accumulate, float scale, void* stream) {
+    if (!src || !dst || n_frames <= 0 || H <= 0 || W <= 0 || code < 0 || code > 7) return UCLSTM_E_BADARG;
     const int64_t plane_px = (int64_t)H * W;
     if (plane_px >= ((int64_t)1 << 31) / Cy || n_frames > (((int64_t)1 << 31) - 1) / (plane_px * Cy)) return UCLSTM_E_BADARG;
-    PlaneVecTables tb;
-    tb.map = 0;
-    for (int c = 0; c < UCLSTM_VEC_MAX; ++c) {
-        if (c < Cy) tb.map |= (uint32_t)(chan_map ? (uint8_t)chan_map[c] : (uint8_t)c) << (8 * c);
-        tb.off[c] = (offset && c < Cy) ? offset[c] : 0.f;
-    }
     const int Ho = (code & 4) ? W : H, Wo = (code & 4) ? H : W;
     // rows of both planes on 16-byte boundaries; with t the loads also run in groups of 4 along the output's rows (Ho = W)
     const bool vec = W % 4 == 0 && Wo % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) % 16) == 0;
     const int ntj = tiles_of(Wo), tiles = tiles_of(Ho) * ntj;
     const int64_t n_chunks = n_frames * Cy * tiles;
     const int grid = (int)(n_chunks < 2048 ? n_chunks : 2048);
-    if (vec)
-        UCLSTM_LAUNCH((plane_d4_vec_kernel<4>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, src, dst, (int)n_chunks, make_fastdiv(tiles),
-                      make_fastdiv(ntj), make_fastdiv(Cy), H, W, code, accumulate, scale, tb);
-    else
-        UCLSTM_LAUNCH((plane_d4_vec_kernel<1>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, src, dst, (int)n_chunks, make_fastdiv(tiles),
-                      make_fastdiv(ntj), make_fastdiv(Cy), H, W, code, accumulate, scale, tb);
+#define UCLSTM_PLANE_LAUNCH(V, CYMAX)                                                                                                   \
+    UCLSTM_LAUNCH((plane_d4_kernel<V, CYMAX>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, src, dst, (int)n_chunks, make_fastdiv(tiles), \
+                  make_fastdiv(ntj), make_fastdiv(Cy), H, W, code, accumulate, scale, plane_tables<CYMAX>(Cy, chan_map, offset))
+    if (Cy == 1) {
+        if (vec) UCLSTM_PLANE_LAUNCH(4, 1);
+        else UCLSTM_PLANE_LAUNCH(1, 1);
+    } else {
+        if (vec) UCLSTM_PLANE_LAUNCH(4, UCLSTM_VEC_MAX);
+        else UCLSTM_PLANE_LAUNCH(1, UCLSTM_VEC_MAX);
+    }
+#undef UCLSTM_PLANE_LAUNCH
     return UCLSTM_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t uclstm_dataset_gather_augment(const float* x_all, const float* y_all, const int64_t* idx, const int32_t* aug,
+                                                 int64_t n_seq, int64_t n_out, int32_t T_src, int32_t T_out, int32_t C, int32_t Hs,
+                                                 int32_t Ws, int32_t Ho, int32_t Wo, int32_t flags, float* x, float* y, float* mask,
+                                                 int32_t transform, float norm_const, float min_vel, float max_vel, int32_t clip,
+                                                 float y_scale, float trans_min, float trans_max, void* stream) {
+    if (!aug) return UCLSTM_E_BADARG;
+    const uclstm_target_consts k = {min_vel, max_vel, y_scale, trans_min, trans_max};
+    return gather_tiles(x_all, y_all, idx, aug, n_seq, n_out, T_src, T_out, C, 1, Hs, Ws, Ho, Wo, flags, NULL, x, y, mask, transform,
+                        norm_const, clip, &k, stream);
+}
+
+extern "C" int32_t uclstm_dataset_gather_vec(const float* x_all, const float* y_all, const int64_t* idx, const int32_t* aug, int64_t n_seq,
+                                             int64_t n_out, int32_t T_src, int32_t T_out, int32_t C, int32_t Cy, int32_t Hs, int32_t Ws,
+                                             int32_t Ho, int32_t Wo, int32_t flags, const int8_t* chan_map, float* x, float* y,
+                                             float* mask, int32_t transform, float norm_const, int32_t clip,
+                                             const uclstm_target_consts* consts, void* stream) {
+    if (!consts || Cy < 1 || Cy > UCLSTM_VEC_MAX) return UCLSTM_E_BADARG;
+    return gather_tiles(x_all, y_all, idx, aug, n_seq, n_out, T_src, T_out, C, Cy, Hs, Ws, Ho, Wo, flags, chan_map, x, y, mask, transform,
+                        norm_const, clip, consts, stream);
 }
 
 extern "C" int32_t uclstm_plane_d4(const float* src, float* dst, int64_t n_planes, int32_t H, int32_t W, int32_t code,
                                    int32_t accumulate, float scale, void* stream) {
-    if (!src || !dst || n_planes <= 0 || H <= 0 || W <= 0 || code < 0 || code > 7) return UCLSTM_E_BADARG;
-    const int64_t plane_px = (int64_t)H * W;
-    if (plane_px >= ((int64_t)1 << 31) || n_planes > (((int64_t)1 << 31) - 1) / plane_px) return UCLSTM_E_BADARG;
-    const int Ho = (code & 4) ? W : H, Wo = (code & 4) ? H : W;
-    // rows of both planes on 16-byte boundaries; with t the loads also run in groups of 4 along the output's rows (Ho = W)
-    const bool vec = W % 4 == 0 && Wo % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) % 16) == 0;
-    const int ntj = tiles_of(Wo), tiles = tiles_of(Ho) * ntj;
-    const int64_t n_chunks = n_planes * tiles;
-    const int grid = (int)(n_chunks < 2048 ? n_chunks : 2048);
-    if (vec)
-        UCLSTM_LAUNCH((plane_d4_kernel<4>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, src, dst, (int)n_chunks, make_fastdiv(tiles),
-                      make_fastdiv(ntj), H, W, code, accumulate, scale);
-    else
-        UCLSTM_LAUNCH((plane_d4_kernel<1>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, src, dst, (int)n_chunks, make_fastdiv(tiles),
-                      make_fastdiv(ntj), H, W, code, accumulate, scale);
-    return UCLSTM_OK;
+    static const float no_offset = -0.f;                                        // v + -0.f is v for every v, v = -0.f included
+    return plane_tiles(src, dst, n_planes, 1, H, W, code, NULL, &no_offset, accumulate, scale, stream);
+}
+
+extern "C" int32_t uclstm_plane_d4_vec(const float* src, float* dst, int64_t n_frames, int32_t Cy, int32_t H, int32_t W, int32_t code,
+                                       const int8_t* chan_map, const float* offset, int32_t accumulate, float scale, void* stream) {
+    if (Cy < 1 || Cy > UCLSTM_VEC_MAX) return UCLSTM_E_BADARG;
+    return plane_tiles(src, dst, n_frames, Cy, H, W, code, chan_map, offset, accumulate, scale, stream);
 }

@@ -379,18 +379,32 @@ def device_transform(ds, x_raw: torch.Tensor, y_raw: torch.Tensor):
     return x, y, mask
 
 
+def _gather_out(x_all, n_out, shape, Cy, out):
+    """The ``(x, y, mask)`` a gather writes: the caller-owned ``out``, or fresh tensors ``[n_out, T_out, C | Cy | 1, Ho, Wo]`` on the
+    current stream for ``shape = (T_out, Ho, Wo)``."""
+    if out is not None:
+        x, y, mask = out
+        return x, y, mask
+    To, Ho, Wo = shape
+    return tuple(torch.empty((n_out, To, c, Ho, Wo), dtype=torch.float32, device=x_all.device) for c in (x_all.shape[2], Cy, 1))
+
+
+def _aug_table(aug, n_out, who):
+    """The device table of a gather with a remap: int32 ``[>= n_out, 4]`` rows ``{code, oy, ox, t0}``."""
+    from . import _lib as L
+    aug = ops._dev(aug, torch.int32, "aug")
+    if aug.dim() != 2 or aug.shape[1] != 4 or aug.shape[0] < n_out:
+        raise L.UclstmError(f"{who}: aug must be int32 [>= {n_out}, 4], got {tuple(aug.shape)}")
+    return aug
+
+
 def _gather_transform(ds, x_all, y_all, idx, n_out, out=None):
     """One launch of ``uclstm_dataset_gather_transform``: the sequences ``idx[0..n_out)`` (device int64; None = the first
     ``n_out`` in order) of the RAW device arrays ``x_all [N,T,C,H,W]`` / ``y_all [N,T,1,H,W]`` as ``ds.__getitem__`` would yield
     them.  ``out``: caller-owned ``(x, y, mask)`` to write into; fresh tensors on the current stream otherwise."""
     from . import _lib as L
     N, T, Cc, H, W = x_all.shape
-    if out is None:
-        x = torch.empty((n_out, T, Cc, H, W), dtype=torch.float32, device=x_all.device)
-        y = torch.empty((n_out, T, 1, H, W), dtype=torch.float32, device=x_all.device)
-        mask = torch.empty_like(y)
-    else:
-        x, y, mask = out
+    x, y, mask = _gather_out(x_all, n_out, (T, H, W), 1, out)
     L.check(L.lib.uclstm_dataset_gather_transform(
         ops._p(x_all), ops._p(y_all), ops._p(idx), N, n_out, T, Cc, H * W, ops._p(x), ops._p(y), ops._p(mask),
         _TRANSFORM_IDS[ds.y_transform], float(ds.norm_const), float(ds.min_vel), float(ds.max_vel), int(bool(ds.clip_outliers)),
@@ -486,15 +500,8 @@ def _gather_augment(ds, x_all, y_all, idx, aug, n_out, shape, flags, out=None):
     from . import _lib as L
     N, T, Cc, H, W = x_all.shape
     To, Ho, Wo = (int(v) for v in shape)
-    aug = ops._dev(aug, torch.int32, "aug")
-    if aug.dim() != 2 or aug.shape[1] != 4 or aug.shape[0] < n_out:
-        raise L.UclstmError(f"_gather_augment: aug must be int32 [>= {n_out}, 4], got {tuple(aug.shape)}")
-    if out is None:
-        x = torch.empty((n_out, To, Cc, Ho, Wo), dtype=torch.float32, device=x_all.device)
-        y = torch.empty((n_out, To, 1, Ho, Wo), dtype=torch.float32, device=x_all.device)
-        mask = torch.empty_like(y)
-    else:
-        x, y, mask = out
+    aug = _aug_table(aug, n_out, "_gather_augment")
+    x, y, mask = _gather_out(x_all, n_out, (To, Ho, Wo), 1, out)
     L.check(L.lib.uclstm_dataset_gather_augment(
         ops._p(x_all), ops._p(y_all), ops._p(idx), ops._p(aug), N, n_out, T, To, Cc, H, W, Ho, Wo, int(flags),
         ops._p(x), ops._p(y), ops._p(mask), _TRANSFORM_IDS[ds.y_transform], float(ds.norm_const), float(ds.min_vel),
@@ -514,15 +521,8 @@ def _gather_vec(ds, x_all, y_all, idx, aug, n_out, shape, flags, out=None):
     if y_all.dim() != 5 or y_all.shape[2] != Cy or y_all.shape[:2] != x_all.shape[:2] or y_all.shape[3:] != x_all.shape[3:]:
         raise L.UclstmError(f"_gather_vec: y must be [{N},{T},{Cy},{H},{W}] beside x {tuple(x_all.shape)}, got {tuple(y_all.shape)}")
     if aug is not None:
-        aug = ops._dev(aug, torch.int32, "aug")
-        if aug.dim() != 2 or aug.shape[1] != 4 or aug.shape[0] < n_out:
-            raise L.UclstmError(f"_gather_vec: aug must be int32 [>= {n_out}, 4], got {tuple(aug.shape)}")
-    if out is None:
-        x = torch.empty((n_out, To, Cc, Ho, Wo), dtype=torch.float32, device=x_all.device)
-        y = torch.empty((n_out, To, Cy, Ho, Wo), dtype=torch.float32, device=x_all.device)
-        mask = torch.empty((n_out, To, 1, Ho, Wo), dtype=torch.float32, device=x_all.device)
-    else:
-        x, y, mask = out
+        aug = _aug_table(aug, n_out, "_gather_vec")
+    x, y, mask = _gather_out(x_all, n_out, (To, Ho, Wo), Cy, out)
     table = ds.__dict__.get("_chan_map_host")
     if table is None:
         table = ds.__dict__["_chan_map_host"] = np.ascontiguousarray(ds.chan_map_table())
@@ -533,25 +533,34 @@ def _gather_vec(ds, x_all, y_all, idx, aug, n_out, shape, flags, out=None):
     return x, y, mask
 
 
+def _plane_args(who, t, code, fits, need, out, accumulate):
+    """What ``plane_d4`` and ``plane_d4_vec`` check alike: ``t`` (f32, contiguous, on the device, of a shape that ``fits``, which
+    ``need`` puts into words), the code, and ``out``: the moved shape on ``t``'s device and not ``t`` itself, or None = a fresh
+    tensor (refused with ``accumulate``).  Returns ``(t, code, out)``."""
+    code = int(code)
+    t = ops._dev(t, torch.float32, f"{who} input")
+    if not fits(t) or not 0 <= code <= 7:
+        raise ValueError(f"{who}: {need} and a code in 0..7 are required, got {tuple(t.shape)}, code {code}")
+    H, W = t.shape[-2:]
+    shape = tuple(t.shape[:-2]) + ((W, H) if code & 4 else (H, W))
+    if out is None:
+        if accumulate:
+            raise ValueError(f"{who}: accumulate=True needs out=")
+        out = torch.empty(shape, dtype=torch.float32, device=t.device)
+    else:
+        ops._dev(out, torch.float32, f"{who} out")
+        if tuple(out.shape) != shape or out.device != t.device or out.data_ptr() == t.data_ptr():
+            raise ValueError(f"{who}: out must be another tensor of shape {shape} on {t.device}, got {tuple(out.shape)} on {out.device}")
+    return t, code, out
+
+
 def plane_d4(t: torch.Tensor, code: int, out: Optional[torch.Tensor] = None, accumulate: bool = False, scale: float = 1.0):
     """Move the last two dims of the contiguous f32 device tensor ``t`` by ``code`` (0..7, as in ``Augment``):
     ``out = (accumulate ? out : 0) + scale * move(t)``, one launch of ``uclstm_plane_d4``.  ``out``: ``t``'s shape, with the last
     two dims swapped for codes with t; a fresh tensor when None (then ``accumulate`` is refused).  ``out`` must not be ``t``."""
     from . import _lib as L
-    code = int(code)
-    t = ops._dev(t, torch.float32, "plane_d4 input")
-    if t.dim() < 2 or not 0 <= code <= 7:
-        raise ValueError(f"plane_d4: a tensor of at least 2 dims and a code in 0..7 are required, got {tuple(t.shape)}, code {code}")
+    t, code, out = _plane_args("plane_d4", t, code, lambda t: t.dim() >= 2, "a tensor of at least 2 dims", out, accumulate)
     H, W = t.shape[-2:]
-    shape = tuple(t.shape[:-2]) + ((W, H) if code & 4 else (H, W))
-    if out is None:
-        if accumulate:
-            raise ValueError("plane_d4: accumulate=True needs out=")
-        out = torch.empty(shape, dtype=torch.float32, device=t.device)
-    else:
-        ops._dev(out, torch.float32, "plane_d4 out")
-        if tuple(out.shape) != shape or out.device != t.device or out.data_ptr() == t.data_ptr():
-            raise ValueError(f"plane_d4: out must be another tensor of shape {shape} on {t.device}, got {tuple(out.shape)} on {out.device}")
     if t.numel():
         L.check(L.lib.uclstm_plane_d4(ops._p(t), ops._p(out), t.numel() // (H * W), H, W, code, int(bool(accumulate)), float(scale),
                                       ops._stream()), "plane_d4")
@@ -564,25 +573,13 @@ def plane_d4_vec(t: torch.Tensor, code: int, affine, out: Optional[torch.Tensor]
     ``out[..., c, :, :] = (accumulate ? out : 0) + scale * (sign * move(t[..., source, :, :]) + offset)``: one launch of
     ``uclstm_plane_d4_vec``."""
     from . import _lib as L
-    code = int(code)
-    t = ops._dev(t, torch.float32, "plane_d4_vec input")
     affine = list(affine)
     Cy = len(affine)
-    if t.dim() < 3 or t.shape[-3] != Cy or not 1 <= Cy <= VEC_MAX or not 0 <= code <= 7:
-        raise ValueError(f"plane_d4_vec: a tensor [..., {Cy}, H, W] with 1 <= Cy <= {VEC_MAX} and a code in 0..7 are required, "
-                         f"got {tuple(t.shape)}, code {code}")
+    t, code, out = _plane_args("plane_d4_vec", t, code, lambda t: t.dim() >= 3 and t.shape[-3] == Cy and 1 <= Cy <= VEC_MAX,
+                               f"a tensor [..., {Cy}, H, W] with 1 <= Cy <= {VEC_MAX}", out, accumulate)
     if any(not 0 <= int(src) < Cy or sign not in (1, -1) for src, sign, _ in affine):
         raise ValueError(f"plane_d4_vec: affine must hold (source channel in [0, {Cy}), sign +-1, offset) per channel, got {affine}")
     H, W = t.shape[-2:]
-    shape = tuple(t.shape[:-2]) + ((W, H) if code & 4 else (H, W))
-    if out is None:
-        if accumulate:
-            raise ValueError("plane_d4_vec: accumulate=True needs out=")
-        out = torch.empty(shape, dtype=torch.float32, device=t.device)
-    else:
-        ops._dev(out, torch.float32, "plane_d4_vec out")
-        if tuple(out.shape) != shape or out.device != t.device or out.data_ptr() == t.data_ptr():
-            raise ValueError(f"plane_d4_vec: out must be another tensor of shape {shape} on {t.device}, got {tuple(out.shape)} on {out.device}")
     if t.numel():
         import ctypes as C
         cmap = (C.c_int8 * Cy)(*[(int(src) | (0x80 if sign < 0 else 0)) - (256 if sign < 0 else 0) for src, sign, _ in affine])
@@ -720,6 +717,12 @@ class DeviceSequenceLoader:
         self.vector = isinstance(self.root, VectorNPZDataset)
         if self.vector and augment is not None and augment.transpose:
             self.root.channel_map(4)                                             # an unpaired horizontal channel: ValueError here
+        if self.vector:                                     # one entry point with or without augmentation (aug = NULL)
+            self._gather = _gather_vec
+        elif augment is not None:
+            self._gather = _gather_augment
+        else:
+            self._gather = lambda ds, x_all, y_all, idx, aug, n_out, shape, flags, out: _gather_transform(ds, x_all, y_all, idx, n_out, out)
         self.x_all, self.y_all = self._resident(self.root, self.device, max_resident_bytes)
 
     @staticmethod
@@ -772,8 +775,9 @@ class DeviceSequenceLoader:
         # ONE pinned int64 tensor per epoch, copied without blocking; this generator's frame keeps it alive until the epoch ends
         pinned = torch.from_numpy(np.concatenate(batches)).pin_memory()
         rows = pinned.to(self.device, non_blocking=True)
+        T, _, H, W = self.x_all.shape[1:]
+        shape, flags, aug = (T, H, W), 2, None
         if self.augment is not None:
-            T, _, H, W = self.x_all.shape[1:]
             shape = self.augment.output_shape(T, H, W)
             self.last_augment = epoch_augment(len(pinned), T, H, W, self.augment, self.augment_generator)
             flags = int(bool(self.augment.transpose)) | (0 if (self.last_augment[:, 2] % 4).any() else 2)
@@ -781,16 +785,7 @@ class DeviceSequenceLoader:
             aug = pinned_aug.to(self.device, non_blocking=True)
         s = 0
         for b in [len(b) for b in batches]:
-            if self.vector:                                     # one entry point with or without augmentation (aug = NULL)
-                if self.augment is None:
-                    T, _, H, W = self.x_all.shape[1:]
-                    yield _gather_vec(self.root, self.x_all, self.y_all, rows[s:s + b], None, b, (T, H, W), 2, out)
-                else:
-                    yield _gather_vec(self.root, self.x_all, self.y_all, rows[s:s + b], aug[s:s + b], b, shape, flags, out)
-            elif self.augment is None:
-                yield _gather_transform(self.root, self.x_all, self.y_all, rows[s:s + b], b, out)
-            else:
-                yield _gather_augment(self.root, self.x_all, self.y_all, rows[s:s + b], aug[s:s + b], b, shape, flags, out)
+            yield self._gather(self.root, self.x_all, self.y_all, rows[s:s + b], None if aug is None else aug[s:s + b], b, shape, flags, out)
             s += b
         del pinned
 
