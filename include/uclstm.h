@@ -770,6 +770,65 @@ int32_t uclstm_eval_stats(const uclstm_eval_desc* d, void* stream);
  * UCLSTM_E_BADARG. */
 int64_t uclstm_eval_stats_rows(int64_t P, int64_t frames);
 
+/* The same report for VECTOR targets in one launch per batch: y_pred / y are [B][T] frames of [Cy][HW] (the planes of a frame
+ * contiguous, channel stride HW, frames addressed by the batch / time strides in elements as above: the model's transposed
+ * output view is read in place), mask is [B][T][1][HW], broadcast over the channels (may be NULL; a pixel counts when
+ * mask != 0).  Cy = 1 .. UCLSTM_VEC_MAX.  Everything below travels in the descriptor by value; nothing is allocated, copied or
+ * synchronised.
+ * Per channel c, de-normalised with consts[c] (min_vel / max_vel unused) and `transform`, with ranges hist_lo/hi[c],
+ * err_lo/hi[c] and edges dig_lo[c] + i * dig_w[c]; bins, n_edges, K and seed are common:
+ *   table      f64 [rows][Cy][UCLSTM_EVAL_ROW], rows = uclstm_eval_stats_rows(HW, B*T), WRITTEN
+ *   hist       u64 [Cy][3][bins], ACCUMULATED
+ *   dig_count  u64 [Cy][n_edges + 1], ACCUMULATED
+ *   scatter    f32 [Cy][n_edges + 1][K][2], ACCUMULATED (8-byte aligned; NULL when K == 0)
+ * with the meaning of every field that of uclstm_eval_stats.  Bit for bit: channel c's rows, histogram counts and digitize counts
+ * equal what uclstm_eval_stats writes when pointed at channel c in place (bases + c * HW, the same strides, P = HW, the
+ * one-channel mask, consts[c]); the scatter sample obeys the same rule (slots [0, min(dig_count, K)) filled with (gt, pred)
+ * pairs of that channel and bin).
+ * Vector part, only when w_chan >= 0 and h_chan >= 0 (otherwise vtable / vhist / dir_hist may be NULL and are not touched).  In
+ * the image frame, with the de-normalised f32 components a = w_sign * v[w_chan] along +column and b = h_sign * v[h_chan] along
+ * +row, target g and prediction p:  speed s = sqrt(a^2 + b^2), ds = s_p - s_g;  endpoint error epe = sqrt((a_p - a_g)^2 +
+ * (b_p - b_g)^2);  direction error dth = atan2(a_g * b_p - b_g * a_p, a_g * a_p + b_g * b_p) in degrees, in (-180, 180],
+ * positive when the prediction is turned from +column towards +row relative to the target, counted only where s_g >= min_speed
+ * and s_p >= min_speed (min_speed is compared as an f32).  These per-pixel values are computed in F32 (sqrtf, atan2f); every
+ * sum is accumulated in f64.
+ *   vtable     f64 [rows][UCLSTM_EVAL_VROW], WRITTEN: {n, sum|ds|, sum ds^2, sum ds, sum s_g, sum s_p, sum epe, sum epe^2, n_dir,
+ *              sum|dth|, sum dth, sum dth^2, max epe, max s_g, max s_p, 0}; a row without a valid pixel holds n = 0 and
+ *              max = -inf.  No floating-point atomics, a fixed order: bitwise reproducible like `table`.
+ *   vhist      u64 [3][bins], ACCUMULATED: s_g and s_p over [0, speed_hi], epe over [0, epe_hi] (the rule of `hist`)
+ *   dir_hist   u64 [dir_bins], ACCUMULATED: dth over [-180, 180] (the rule of `hist`)
+ * Counters live in LDS when Cy * (3 * bins + 3 * (n_edges + 1)) + 3 * bins + dir_bins words fit 60 KiB, otherwise every count is a
+ * global integer atomic.  f32 only (no _f16 twin). */
+#define UCLSTM_EVAL_VROW        16
+typedef struct {
+    const float* y_pred; int64_t pred_stride_b, pred_stride_t;
+    const float* y;      int64_t y_stride_b, y_stride_t;
+    const float* mask;   int64_t mask_stride_b, mask_stride_t;
+    int32_t B, T, Cy;
+    int32_t transform;                 /* UCLSTM_EVAL_* */
+    int64_t HW;
+    uclstm_target_consts consts[UCLSTM_VEC_MAX];
+    double hist_lo[UCLSTM_VEC_MAX], hist_hi[UCLSTM_VEC_MAX], err_lo[UCLSTM_VEC_MAX], err_hi[UCLSTM_VEC_MAX];
+    double dig_lo[UCLSTM_VEC_MAX], dig_w[UCLSTM_VEC_MAX];
+    int32_t bins, n_edges, K, dir_bins;
+    uint64_t seed;
+    int32_t w_chan, h_chan;            /* channel index, or -1 for none */
+    int32_t w_sign, h_sign;            /* +1 / -1 */
+    double speed_hi, epe_hi, min_speed;
+    double* table;
+    uint64_t* hist;
+    uint64_t* dig_count;
+    float* scatter;
+    double* vtable;
+    uint64_t* vhist;
+    uint64_t* dir_hist;
+} uclstm_eval_vec_desc;
+/* UCLSTM_E_BADARG before any launch for: every condition of uclstm_eval_stats (per channel where the field is per channel), Cy
+ * outside [1, UCLSTM_VEC_MAX], w_chan or h_chan outside [-1, Cy) or equal to each other when >= 0, a sign other than +1 / -1,
+ * speed_hi <= 0, epe_hi <= 0, min_speed < 0 or NaN, dir_bins outside [1, 4096], a NULL vtable / vhist / dir_hist while both
+ * channels are given, B*T*Cy*HW >= 2^31. */
+int32_t uclstm_eval_stats_vec(const uclstm_eval_vec_desc* d, void* stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* Dataset statistics (train/unet.py:222-262, get_data_min_max.py) -- csrc/dataset_stats.hip */
 /* ------------------------------------------------------------------------------------ */

@@ -2,11 +2,16 @@
 statistics computed on the device (unet_convlstm_amd.evaluate_report) and every path given on the command line.
 
     python tools/eval_report.py --checkpoint model.pt --npz data.npz [--batch 8] [--use-mask] [--out report.npz] [--plots DIR]
+    python tools/eval_report.py --checkpoint model.pt --npz wind.npz --axes "+w,-h,none" [--tie-horizontal] [--out report.npz]
     python tools/eval_report.py --bench            # kernel timing against uclstm_metric_sums, see profiles/eval_report.txt
+    python tools/eval_report.py --bench --vector   # uclstm_eval_stats_vec against Cy scalar launches, see profiles/eval_report_vec.txt
 
 The checkpoint is what the reference's training writes: {"config": {...}, "model_state": state_dict}, of model type 'custom'
 (TemporalUNetDualView) or 'resnet18' (PretrainedTemporalUNet: lstm_layers from the config or counted in the keys).  --plots
 draws the reference's five figures from the report when matplotlib can be imported, after everything that is timed.
+--axes: the target is a vector (VectorNPZDataset, one entry per channel: +w, -w, +h, -h or none); the model's head is sized from the
+checkpoint's own head weight and the report is VectorEvalReport's: per channel what the scalar report holds (keys ch<c>_*), and
+speed / endpoint / direction errors when there is a horizontal pair (keys vector_*).  No figures with --axes.
 """
 from __future__ import annotations
 
@@ -34,7 +39,17 @@ def flat(report: dict) -> dict:
     return out
 
 
-def load_model(U, checkpoint_path, device):
+def flat_vector(report: dict) -> dict:
+    """The dict of VectorEvalReport.result as a flat {name: array} mapping: ch<c>_<key> per channel, vector_<key>, axes."""
+    out = {"axes": np.asarray(["none" if a is None else a for a in report["axes"]])}
+    for c, ch in enumerate(report["channels"]):
+        out.update({f"ch{c}_{k}": v for k, v in flat(ch).items()})
+    if report["vector"] is not None:
+        out.update({f"vector_{k}": v for k, v in flat(report["vector"]).items()})
+    return out
+
+
+def load_model(U, checkpoint_path, device, vector=False):
     checkpoint = torch.load(checkpoint_path, map_location="cpu")
     cfg = checkpoint.get("config", {})
     model_type = cfg.get("type", "custom")
@@ -52,7 +67,7 @@ def load_model(U, checkpoint_path, device):
         return model.to(device).eval()
     if model_type != "custom":
         raise SystemExit(f"model type {model_type!r} is not supported ('custom': TemporalUNetDualView, 'resnet18': PretrainedTemporalUNet)")
-    model = U.TemporalUNetDualView(in_channels_per_sat=1, out_channels=1, base_ch=cfg.get("base_ch", 64), lstm_layers=1,
+    model = U.TemporalUNetDualView(in_channels_per_sat=1, out_channels=state["outc.conv.weight"].shape[0] if vector else 1, base_ch=cfg.get("base_ch", 64), lstm_layers=1,
                                    use_skip_lstm=cfg.get("use_skip_lstm", True), use_attention=cfg.get("use_attention", False))
     model.load_state_dict(state)
     return model.to(device).eval()
@@ -102,10 +117,44 @@ def draw(report: dict, out_dir: str) -> bool:
     return True
 
 
+def run_vector(args, U, device) -> None:
+    axes = tuple(None if a.strip().lower() == "none" else a.strip() for a in args.axes.split(","))
+    if args.plots:
+        raise SystemExit("--plots draws the scalar report's figures; there are none for --axes")
+    print(f"[INFO] Loading checkpoint: {args.checkpoint}")
+    model = load_model(U, args.checkpoint, device, vector=True)
+    full_dataset = U.VectorNPZDataset(args.npz, axes, tie_horizontal=args.tie_horizontal)
+    if model.out_channels != full_dataset.Cy:
+        raise SystemExit(f"the checkpoint's head has {model.out_channels} outputs, --axes names {full_dataset.Cy} channels")
+    n_train = int(0.8 * len(full_dataset))                           # the split of training, same seed
+    generator = torch.Generator().manual_seed(42)
+    _, val_ds = torch.utils.data.random_split(full_dataset, [n_train, len(full_dataset) - n_train], generator=generator)
+    print(f"[INFO] Dataset loaded. Evaluating on VALIDATION set only ({len(val_ds)} sequences)")
+    loader = U.DeviceSequenceLoader(val_ds, args.batch)
+    t0 = time.perf_counter()
+    loss, mae, rmse, me, report = U.evaluate_vector_report(model, loader, device, full_dataset, use_mask=args.use_mask)
+    dt = time.perf_counter() - t0
+    print("\n" + "=" * 40)
+    for c, ch in enumerate(report["channels"]):
+        print(f"Channel {c} ({axes[c]}): MAE {ch['mae']:.4f}  RMSE {ch['rmse']:.4f}  Bias {ch['mean_err']:.4f}  Error Std {ch['std_err']:.4f} m/s")
+    v = report["vector"]
+    if v is not None:
+        print(f"Speed MAE:         {v['speed_mae']:.4f} m/s (bias {v['speed_bias']:.4f})")
+        print(f"Endpoint Error:    {v['epe_mean']:.4f} m/s (RMS {v['epe_rmse']:.4f}, max {v['epe_max']:.4f})")
+        print(f"Direction MAE:     {v['dir_mae']:.2f} deg (bias {v['dir_bias']:.2f}, std {v['dir_std']:.2f}, {int(v['n_dir'])} of {int(v['n'])} pixels)")
+    print("=" * 40)
+    print(f"[INFO] loss {loss:.6f}; pooled MAE {mae:.4f} RMSE {rmse:.4f}; {len(val_ds)} sequences in {dt:.3f} s")
+    if args.out:
+        np.savez(args.out, loss=np.float64(loss), **flat_vector(report))
+        print(f"[INFO] report written to {args.out}")
+
+
 def run(args) -> None:
     import unet_convlstm_amd as U
     if not torch.cuda.is_available():
         raise SystemExit("a HIP device is required (this package has no CPU path)")
+    if getattr(args, "axes", None):                                   # callers that build their own namespace predate the option
+        return run_vector(args, U, torch.device("cuda", 0))
     device = torch.device("cuda", 0)
     print(f"[INFO] Loading checkpoint: {args.checkpoint}")
     model = load_model(U, args.checkpoint, device)
@@ -258,6 +307,92 @@ def bench(args) -> None:
           f"8 batches: {1e3 * (time.perf_counter() - t0):.1f} ms (numpy, one host thread)")
 
 
+def bench_vector(args) -> None:
+    """uclstm_eval_stats_vec at Cy = 3 against what it replaces, by the method of bench(): HIP events around every entry, a spin
+    kernel in front of every round, the entries alternated, medians; the whole comparison three times over (legs), so that the
+    spread between legs says what a difference between entries means."""
+    import unet_convlstm_amd as U
+    from unet_convlstm_amd import _lib as L, ops
+
+    Cy, legs = 3, 3
+    ds = object.__new__(U.VectorNPZDataset)                             # the constants only: no file behind it
+    ds.Cy, ds.axes, ds.w_channel, ds.h_channel, ds.y_transform = Cy, ("+w", "-h", None), 0, 1, "asinh"
+    ds.y_scale = np.array([2.0, 2.0, 0.5])
+    ds.min_vel, ds.max_vel = np.array([-7.6, -7.6, -2.0]), np.array([8.8, 8.8, 2.0])
+    ds.trans_min, ds.trans_max = np.arcsinh(ds.min_vel / ds.y_scale), np.arcsinh(ds.max_vel / ds.y_scale)
+
+    class One:                                                          # channel c as a scalar dataset
+        def __init__(self, c):
+            self.y_transform, self.y_scale, self.trans_min, self.trans_max = "asinh", ds.y_scale[c], ds.trans_min[c], ds.trans_max[c]
+
+    dev = torch.device("cuda", 0)
+    print(f"# eval_stats_vec at Cy = {Cy}: median ms per entry over {args.iters} rounds (HIP events, {args.warmup} warm-up rounds, entries alternated "
+          f"in one process), the median of {legs} legs and their [min .. max]; GB/s of vec from its algorithmic bytes (8 * Cy B/pixel, + 4 with a mask)")
+    print("# vec = uclstm_eval_stats_vec with the horizontal pair; vec-nopair = the same launch with w_chan = h_chan = -1 (the per-channel part alone); "
+          "3 x scalar = Cy in-place launches of uclstm_eval_stats (the same per-channel statistics); sums_vec = uclstm_metric_sums_vec on contiguous tensors")
+    print(f"{'shape':>20} {'input':>8} {'mask':>5} {'vec ms':>24} {'GB/s':>6} {'vec-nopair ms':>24} {'3 x scalar ms':>24} {'sums_vec ms':>24} {'vec/3 x scalar':>15}")
+    stream = ops._stream()
+    sv = torch.zeros((Cy, 4), dtype=torch.float64, device=dev)
+    for shape in ((32, 20, Cy, 64, 64), (4, 12, Cy, 256, 256)):
+        B, T, _, H, W = shape
+        for kind in ("uniform", "skewed"):
+            g = torch.Generator().manual_seed(1)
+            y = torch.rand(shape, generator=g) * 2 - 1
+            if kind == "skewed":
+                y[torch.rand(shape, generator=g) < 0.85] = -0.4137
+            yp = (y + 0.15 * torch.randn(shape, generator=g)).clamp(-1.2, 1.2)
+            mask = (torch.rand((B, T, 1, H, W), generator=g) > 0.3).float()
+            y_d, m_d = y.to(dev), mask.to(dev)
+            view = yp.transpose(0, 1).contiguous().to(dev).transpose(0, 1)          # as the model returns it
+            yp_c = view.contiguous()
+            n_frames, n = B * T, B * T * H * W
+            partials = torch.empty((int(L.lib.uclstm_metric_sums_vec_rows(n_frames, Cy, H * W)), Cy, 4), dtype=torch.float64, device=dev)
+            for use_mask in (False, True):
+                m = m_d if use_mask else None
+                rep = U.VectorEvalReport(ds, device=dev)
+                desc, _table, _vtable = rep._describe(view, y_d, m)
+                assert desc.y_pred == view.data_ptr() and not view.is_contiguous()
+                rep_np = U.VectorEvalReport(ds, device=dev)
+                desc_np, _t, _v = rep_np._describe(view, y_d, m)
+                desc_np.w_chan = desc_np.h_chan = -1
+                scalar = []
+                for c in range(Cy):
+                    r = U.EvalReport(One(c), device=dev)
+                    scalar.append((r, r._describe(view[:, :, c:c + 1], y_d[:, :, c:c + 1], m)))
+                    assert scalar[-1][1][0].y_pred == view.data_ptr() + 4 * c * H * W
+
+                def vec():
+                    L.check(L.lib.uclstm_eval_stats_vec(desc, stream), "eval_stats_vec")
+
+                def vec_nopair():
+                    L.check(L.lib.uclstm_eval_stats_vec(desc_np, stream), "eval_stats_vec")
+
+                def three():
+                    for _r, (d, _tab) in scalar:
+                        L.check(L.lib.uclstm_eval_stats(d, stream), "eval_stats")
+
+                def sums_vec():
+                    L.check(L.lib.uclstm_metric_sums_vec(ops._p(yp_c), ops._p(y_d), ops._p(m), ops._p(partials), ops._p(sv), 1, n_frames, Cy, H * W,
+                                                         1, ds.target_consts(), stream), "metric_sums_vec")
+
+                fns = {"vec": vec, "vec-nopair": vec_nopair, "3 x scalar": three, "sums_vec": sums_vec}
+                runs = [_time_alternated(fns, args.warmup, args.iters, lambda: L.check(L.lib.uclstm_stream_spin(500, stream), "spin"))
+                        for _ in range(legs)]
+                expect = legs * (args.warmup + args.iters) * int(m.sum().item() if use_mask else n)
+                got = [int(v) for v in rep._dig.sum(dim=1).tolist()] + [int(r._dig.sum().item()) for r, _ in scalar]
+                if got != [expect] * (2 * Cy) or int(rep._dir.sum().item()) > expect:
+                    raise SystemExit(f"the kernels counted something else than the pixels they were given: {got}, expected {expect}")
+                ms = {k: sorted(r[k] for r in runs) for k in fns}
+                med = {k: v[legs // 2] for k, v in ms.items()}
+
+                def cell(k):
+                    return f"{med[k]:8.4f} [{ms[k][0]:.4f} .. {ms[k][-1]:.4f}]"
+
+                gb = n * (8 * Cy + (4 if use_mask else 0)) / 1e6
+                print(f"{str(list(shape)):>20} {kind:>8} {str(use_mask):>5} {cell('vec'):>24} {gb / med['vec']:6.0f} {cell('vec-nopair'):>24} "
+                      f"{cell('3 x scalar'):>24} {cell('sums_vec'):>24} {med['vec'] / med['3 x scalar']:15.2f}", flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--checkpoint")
@@ -267,13 +402,16 @@ def main() -> None:
     ap.add_argument("--out", default=None, help="write the report as .npz")
     ap.add_argument("--plots", default=None, metavar="DIR", help="draw the five figures of get_metrics.py into DIR (needs matplotlib)")
     ap.add_argument("--bench", action="store_true", help="time the kernel against uclstm_metric_sums instead of evaluating a checkpoint")
+    ap.add_argument("--axes", default=None, metavar="A,B,..", help='vector target: one of +w, -w, +h, -h, none per channel, e.g. "+w,-h,none"')
+    ap.add_argument("--tie-horizontal", action="store_true", help="with --axes: the two horizontal channels share one set of constants")
+    ap.add_argument("--vector", action="store_true", help="with --bench: time uclstm_eval_stats_vec (profiles/eval_report_vec.txt)")
     ap.add_argument("--iters", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=5)
     args = ap.parse_args()
     if args.bench:
         if args.iters < 50:
             ap.error("--bench needs --iters >= 50")
-        bench(args)
+        (bench_vector if args.vector else bench)(args)
         return
     if not args.checkpoint or not args.npz:
         ap.error("--checkpoint and --npz are required")

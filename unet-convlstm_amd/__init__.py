@@ -18,7 +18,7 @@ from .optim import FusedAdamW
 from .engine import train_one_epoch, evaluate, train_step, GraphedTrainStep, quiesce_host_gc, SyntheticSequences, NPZSequenceDataset, device_transform, EvalReport, evaluate_report, DeviceSequenceLoader, epoch_rows, Augment, epoch_augment, plane_d4, predict_tta, d4_inverse
 from .engine import (DeviceSpriteLoader, render_sprites_host, epoch_sprites, check_sprite_table, load_idx_images,
                      procedural_glyphs)
-from .engine import VectorNPZDataset, plane_d4_vec
+from .engine import VectorNPZDataset, plane_d4_vec, VectorEvalReport, evaluate_vector_report
 from .engine import DeviceNPZDataset, device_order_statistics, device_percentile, device_extremes, percentile_ranks, percentile_lerp
 from .ddp import FlatDDP
 from .streaming import StreamingPredictor, PretrainedStreamingPredictor
@@ -29,7 +29,7 @@ from .ops import sync_batchnorm, set_sync_batchnorm, get_sync_batchnorm
 __all__ = ["ConvLSTMCell", "ConvLSTM", "DoubleConv", "Down", "Up", "OutConv", "SpatialAttention",
            "TemporalUNetDualView", "UNet", "PretrainedTemporalUNet", "compute_loss", "LossSpec", "FusedAdamW", "train_one_epoch", "evaluate",
            "train_step", "GraphedTrainStep", "quiesce_host_gc", "SyntheticSequences", "NPZSequenceDataset", "device_transform", "EvalReport", "evaluate_report", "DeviceSequenceLoader", "epoch_rows", "Augment", "epoch_augment", "plane_d4", "predict_tta", "d4_inverse", "DeviceSpriteLoader", "render_sprites_host", "epoch_sprites", "check_sprite_table",
-           "load_idx_images", "procedural_glyphs", "VectorNPZDataset", "plane_d4_vec", "DeviceNPZDataset", "device_order_statistics", "device_percentile", "device_extremes",
+           "load_idx_images", "procedural_glyphs", "VectorNPZDataset", "plane_d4_vec", "VectorEvalReport", "evaluate_vector_report", "DeviceNPZDataset", "device_order_statistics", "device_percentile", "device_extremes",
            "percentile_ranks", "percentile_lerp", "FlatDDP", "StreamingPredictor", "PretrainedStreamingPredictor", "UclstmError", "ops",
            "compute_dtype", "set_compute_dtype", "get_compute_dtype", "deterministic", "set_deterministic", "is_deterministic",
            "sync_batchnorm", "set_sync_batchnorm", "get_sync_batchnorm"]

@@ -118,12 +118,30 @@ class TargetConsts(C.Structure):
     _fields_ = [("min_vel", C.c_float), ("max_vel", C.c_float), ("y_scale", C.c_float), ("trans_min", C.c_float), ("trans_max", C.c_float)]
 
 
+class EvalVecDesc(C.Structure):
+    """uclstm_eval_vec_desc: the report of uclstm_eval_stats for frames of Cy target channels, per-channel fields as arrays of VEC_MAX."""
+    _fields_ = [("y_pred", C.c_void_p), ("pred_stride_b", C.c_int64), ("pred_stride_t", C.c_int64),
+                ("y", C.c_void_p), ("y_stride_b", C.c_int64), ("y_stride_t", C.c_int64),
+                ("mask", C.c_void_p), ("mask_stride_b", C.c_int64), ("mask_stride_t", C.c_int64),
+                ("B", C.c_int32), ("T", C.c_int32), ("Cy", C.c_int32), ("transform", C.c_int32), ("HW", C.c_int64),
+                ("consts", TargetConsts * 4),
+                ("hist_lo", C.c_double * 4), ("hist_hi", C.c_double * 4), ("err_lo", C.c_double * 4), ("err_hi", C.c_double * 4),
+                ("dig_lo", C.c_double * 4), ("dig_w", C.c_double * 4),
+                ("bins", C.c_int32), ("n_edges", C.c_int32), ("K", C.c_int32), ("dir_bins", C.c_int32),
+                ("seed", C.c_uint64),
+                ("w_chan", C.c_int32), ("h_chan", C.c_int32), ("w_sign", C.c_int32), ("h_sign", C.c_int32),
+                ("speed_hi", C.c_double), ("epe_hi", C.c_double), ("min_speed", C.c_double),
+                ("table", C.c_void_p), ("hist", C.c_void_p), ("dig_count", C.c_void_p), ("scatter", C.c_void_p),
+                ("vtable", C.c_void_p), ("vhist", C.c_void_p), ("dir_hist", C.c_void_p)]
+
+
 LOSS_POINT_L1, LOSS_POINT_L2, LOSS_POINT_HUBER = 0, 1, 2
 VEC_MAX = 4                  # UCLSTM_VEC_MAX: target channels of the vector data path
 SELECT_MAX_SLOTS, SELECT_BINS, SELECT_SIGNED, SELECT_ABS = 8, 2048, 0, 1
 SELECT_WS_COUNT, SELECT_WS_NAN, SELECT_WS_FLAGS, SELECT_WS_PREFIX, SELECT_WS_RANK, SELECT_WS_LEADER, SELECT_WS_HIST = 0, 1, 2, 8, 16, 24, 32
 EXTREMES_MIN_KEY, EXTREMES_MAX_KEY, EXTREMES_NAN, EXTREMES_NONZERO, EXTREMES_COUNT, EXTREMES_WORDS = 0, 1, 2, 3, 4, 8
 EVAL_ROW = 16
+EVAL_VROW = 16               # UCLSTM_EVAL_VROW: doubles per row of the vector table
 EVAL_NONE, EVAL_ASINH, EVAL_SIGNED_LOG = 0, 1, 2
 
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -236,6 +254,7 @@ _PROTOS = {
     "uclstm_metric_sums_vec": [_P, _P, _P, _P, _P, _I, _L, _I, _I, _I, C.POINTER(TargetConsts), _P],
     "uclstm_eval_stats": [C.POINTER(EvalDesc), _P],
     "uclstm_eval_stats_rows": [_L, _L],
+    "uclstm_eval_stats_vec": [C.POINTER(EvalVecDesc), _P],
     "uclstm_select_workspace_bytes": [],
     "uclstm_select_begin": [C.POINTER(SelectState), _P, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _I, _P],
     "uclstm_select_accumulate": [C.POINTER(SelectState), _I, _P, _L, _P],

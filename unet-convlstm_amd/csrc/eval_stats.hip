@@ -353,3 +353,382 @@ extern "C" int32_t uclstm_eval_stats(const uclstm_eval_desc* d, void* stream) {
     }
     return UCLSTM_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Vector targets: frames of Cy planes [Cy][HW], one mask plane for all channels.  One launch does, per channel, exactly what
+// eval_stats_kernel does when pointed at that channel in place (same chunk, same pixel ownership, same reduction order, the
+// device helpers above), and keeps the de-normalised horizontal pair in registers for the quantities that need two channels
+// of one pixel: speed, endpoint error, direction error.  Traffic: 8 * Cy B (+ 4 B with a mask) per pixel, read once.
+//
+// Registers: the channels are a fully unrolled loop; a channel's values, bins and ranks die with its iteration, because its
+// scatter tickets are reserved and used inside it (two block barriers per channel).  Only the mask bits and the four f32
+// components of the horizontal pair live across the loop.  Resource usage, timing and the variants tried (loading a channel
+// ahead, an occupancy floor): profiles/eval_report_vec.txt.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int VROW = UCLSTM_EVAL_VROW;
+
+struct VecArgs {
+    Args ch[UCLSTM_VEC_MAX];                     // channel c as uclstm_eval_stats sees it in place: yp / y + c * HW, P = HW, its constants,
+                                                 // ranges and slices of hist / dig / scatter; table + c * ROW (a row is [Cy][ROW])
+    int w_chan, h_chan;                          // the horizontal pair, both >= 0 or the vector part does not exist
+    float w_sign, h_sign;
+    double s_hi, s_step, s_norm;                 // speed histograms over [0, s_hi]
+    double p_hi, p_step, p_norm;                 // endpoint error over [0, p_hi]
+    double t_step, t_norm;                       // direction error over [-180, 180]
+    int dir_bins;
+    float min_speed;
+    double* vtable;
+    unsigned long long* vhist;                   // [3][bins]
+    unsigned long long* dir_hist;                // [dir_bins]
+};
+
+template <bool VEC>
+__device__ __forceinline__ void load_chunk(const float* p, int left, float (&v)[PPT]) {
+    if (VEC) {
+#pragma unroll
+        for (int q = 0; q < PPT / 4; ++q) {
+            const int o = (q * NT + (int)threadIdx.x) * 4;
+            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (o < left) x = *(const float4*)(p + o);
+            v[4 * q + 0] = x.x, v[4 * q + 1] = x.y, v[4 * q + 2] = x.z, v[4 * q + 3] = x.w;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < PPT; ++q) {
+            const int o = q * NT + (int)threadIdx.x;
+            v[q] = o < left ? p[o] : 0.f;
+        }
+    }
+}
+
+template <int CY, bool VEC, bool LDS>
+__global__ __launch_bounds__(NT) void eval_stats_vec_kernel(const VecArgs va) {
+    // LDS: per channel hist gt | pred | err [bins], digitize [nd], bases lo | hi [nd]; then speed gt | pred | epe [bins], dir [dir_bins]
+    extern __shared__ uint32_t sm[];
+    __shared__ double red_s[CY][4][8];
+    __shared__ float red_m[CY][4][6];
+    __shared__ double red_v[4][12];
+    __shared__ float red_x[4][3];
+    const int bins = va.ch[0].bins, nd = va.ch[0].n_edges + 1, K = va.ch[0].K;
+    const int per = 3 * bins + 3 * nd;
+    uint32_t* vh = sm + CY * per;
+    uint32_t* dh = vh + 3 * bins;
+    const bool pair = va.w_chan >= 0 && va.h_chan >= 0;
+    if (LDS) {
+        for (int i = threadIdx.x; i < CY * per + 3 * bins + va.dir_bins; i += NT) sm[i] = 0u;
+        __syncthreads();
+    }
+
+    const Args& a0 = va.ch[0];
+    const uint32_t frame = fdiv(blockIdx.x, a0.dCpf);
+    const int chunk = (int)(blockIdx.x - frame * a0.dCpf.d);
+    const uint32_t b = fdiv(frame, a0.dT);
+    const uint32_t t = frame - b * a0.dT.d;
+    const int p0 = chunk * CHUNK;
+    const int64_t off_p = (int64_t)b * a0.yp_sb + (int64_t)t * a0.yp_st + p0;
+    const int64_t off_y = (int64_t)b * a0.y_sb + (int64_t)t * a0.y_st + p0;
+    const int left = a0.P - p0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float inf = __builtin_inff();
+
+    bool ok[PPT];
+    {
+        float m[PPT];
+        if (a0.mask) load_chunk<VEC>(a0.mask + (int64_t)b * a0.m_sb + (int64_t)t * a0.m_st + p0, left, m);
+#pragma unroll
+        for (int q = 0; q < PPT; ++q) {
+            const int o = VEC ? ((q / 4) * NT + (int)threadIdx.x) * 4 : q * NT + (int)threadIdx.x;      // a quad is inside or outside
+            ok[q] = o < left && (a0.mask ? m[q] != 0.f : true);
+        }
+    }
+
+    float ga[PPT], gb[PPT], pa[PPT], pb[PPT];    // the pair in the image frame: a along +column, b along +row
+#pragma unroll
+    for (int q = 0; q < PPT; ++q) ga[q] = gb[q] = pa[q] = pb[q] = 0.f;
+
+#pragma unroll
+    for (int c = 0; c < CY; ++c) {
+        const Args& a = va.ch[c];
+        uint32_t* h_gt = sm + c * per;
+        uint32_t* h_pr = h_gt + bins;
+        uint32_t* h_er = h_gt + 2 * bins;
+        uint32_t* dg = h_gt + 3 * bins;
+        uint32_t* base_lo = dg + nd;
+        uint32_t* base_hi = base_lo + nd;
+        float vp[PPT], vy[PPT];
+        load_chunk<VEC>(a.yp + off_p, left, vp);
+        load_chunk<VEC>(a.y + off_y, left, vy);
+
+        double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // as eval_stats_kernel, statement for statement
+        float mn_g = inf, mx_g = -inf, mn_p = inf, mx_p = -inf, mn_d = inf, mx_d = -inf;
+        int dbin[PPT];
+        uint32_t rank[PPT];
+        uint64_t ticket[PPT];                    // !LDS only
+#pragma unroll
+        for (int q = 0; q < PPT; ++q) {
+            const float pr = denorm(vp[q], a), gt = denorm(vy[q], a);
+            const float df = pr - gt;
+            vp[q] = pr, vy[q] = gt;
+            const bool v = ok[q];
+            if (v) {
+                const double d = (double)df, g = (double)gt, p = (double)pr;
+                s[0] += 1.0, s[1] += fabs(d), s[2] += d * d, s[3] += d;
+                s[4] += g, s[5] += g * g, s[6] += p, s[7] += p * p;
+                mn_g = fminf(mn_g, gt), mx_g = fmaxf(mx_g, gt);
+                mn_p = fminf(mn_p, pr), mx_p = fmaxf(mx_p, pr);
+                mn_d = fminf(mn_d, df), mx_d = fmaxf(mx_d, df);
+            }
+            const int bg = v ? hist_bin(gt, a.h_lo, a.h_hi, a.h_step, a.h_norm, bins) : -1;
+            const int bp = v ? hist_bin(pr, a.h_lo, a.h_hi, a.h_step, a.h_norm, bins) : -1;
+            const int be = v ? hist_bin(df, a.e_lo, a.e_hi, a.e_step, a.e_norm, bins) : -1;
+            dbin[q] = v ? digitize_bin(gt, a) : -1;
+            if (LDS) {
+                count_in_lds<false, 2>(h_gt, bg, bg >= 0);
+                count_in_lds<false, 1>(h_pr, bp, bp >= 0);
+                count_in_lds<false, 1>(h_er, be, be >= 0);
+                rank[q] = count_in_lds<true, 2>(dg, dbin[q], v);
+            } else {
+                if (bg >= 0) atomicAdd(a.hist + bg, 1ull);
+                if (bp >= 0) atomicAdd(a.hist + bins + bp, 1ull);
+                if (be >= 0) atomicAdd(a.hist + 2 * bins + be, 1ull);
+                ticket[q] = v ? atomicAdd(a.dig + dbin[q], 1ull) : 0ull;
+            }
+        }
+        if (c == va.w_chan) {
+#pragma unroll
+            for (int q = 0; q < PPT; ++q) ga[q] = va.w_sign * vy[q], pa[q] = va.w_sign * vp[q];
+        }
+        if (c == va.h_chan) {
+#pragma unroll
+            for (int q = 0; q < PPT; ++q) gb[q] = va.h_sign * vy[q], pb[q] = va.h_sign * vp[q];
+        }
+
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            mn_g = fminf(mn_g, __shfl_xor(mn_g, o, 64)), mx_g = fmaxf(mx_g, __shfl_xor(mx_g, o, 64));
+            mn_p = fminf(mn_p, __shfl_xor(mn_p, o, 64)), mx_p = fmaxf(mx_p, __shfl_xor(mx_p, o, 64));
+            mn_d = fminf(mn_d, __shfl_xor(mn_d, o, 64)), mx_d = fmaxf(mx_d, __shfl_xor(mx_d, o, 64));
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) red_s[c][wave][k] = s[k];
+            red_m[c][wave][0] = mn_g, red_m[c][wave][1] = mx_g, red_m[c][wave][2] = mn_p;
+            red_m[c][wave][3] = mx_p, red_m[c][wave][4] = mn_d, red_m[c][wave][5] = mx_d;
+        }
+        __syncthreads();                         // also: every LDS counter of this channel is final
+        if (threadIdx.x < ROW) {
+            const int k = threadIdx.x;
+            double v = 0.0;
+            if (k < 8) {
+                v = ((red_s[c][0][k] + red_s[c][1][k]) + red_s[c][2][k]) + red_s[c][3][k];
+            } else if (k < 14) {
+                const int j = k - 8;
+                const float m0 = red_m[c][0][j], m1 = red_m[c][1][j], m2 = red_m[c][2][j], m3 = red_m[c][3][j];
+                v = (double)((j & 1) ? fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)) : fminf(fminf(m0, m1), fminf(m2, m3)));
+            }
+            a.table[(int64_t)blockIdx.x * (CY * ROW) + k] = v;
+        }
+
+        if (LDS) {
+            for (int i = threadIdx.x; i < 3 * bins; i += NT) {
+                const uint32_t n = h_gt[i];
+                if (n) atomicAdd(a.hist + i, (unsigned long long)n);
+            }
+            for (int i = threadIdx.x; i < nd; i += NT) {
+                const uint32_t n = dg[i];
+                if (!n) continue;
+                if (K > 0) {
+                    const unsigned long long base = atomicAdd(a.dig + i, (unsigned long long)n);
+                    base_lo[i] = (uint32_t)base;
+                    base_hi[i] = (uint32_t)(base >> 32);
+                } else {
+                    atomicAdd(a.dig + i, (unsigned long long)n);
+                }
+            }
+            if (K > 0) {
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < PPT; ++q) {
+                    const int bin = dbin[q];
+                    if (bin < 0) continue;
+                    const uint64_t base = ((uint64_t)base_hi[bin] << 32) | base_lo[bin];
+                    scatter_store(a, bin, base + rank[q], vy[q], vp[q]);
+                }
+            }
+        } else if (K > 0) {
+#pragma unroll
+            for (int q = 0; q < PPT; ++q)
+                if (dbin[q] >= 0) scatter_store(a, dbin[q], ticket[q], vy[q], vp[q]);
+        }
+    }
+
+    if (!pair) return;                           // the same in every thread
+
+    // n, |ds|, ds^2, ds, s_g, s_p, epe, epe^2, n_dir, |dth|, dth, dth^2 in f64 from f32 per-pixel values; max epe, s_g, s_p
+    double s[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    float mx_e = -inf, mx_g = -inf, mx_p = -inf;
+#pragma unroll
+    for (int q = 0; q < PPT; ++q) {
+        const bool v = ok[q];
+        const float sg = sqrtf(ga[q] * ga[q] + gb[q] * gb[q]), sp = sqrtf(pa[q] * pa[q] + pb[q] * pb[q]);
+        const float da = pa[q] - ga[q], db = pb[q] - gb[q];
+        const float epe = sqrtf(da * da + db * db), ds = sp - sg;
+        float th = atan2f(ga[q] * pb[q] - gb[q] * pa[q], ga[q] * pa[q] + gb[q] * pb[q]) * 57.29577951308232f;
+        th = (th <= -180.f) ? 180.f : fminf(th, 180.f);          // (-180, 180]
+        const bool vd = v && sg >= va.min_speed && sp >= va.min_speed;
+        if (v) {
+            const double d = (double)ds, e = (double)epe;
+            s[0] += 1.0, s[1] += fabs(d), s[2] += d * d, s[3] += d;
+            s[4] += (double)sg, s[5] += (double)sp, s[6] += e, s[7] += e * e;
+            mx_e = fmaxf(mx_e, epe), mx_g = fmaxf(mx_g, sg), mx_p = fmaxf(mx_p, sp);
+        }
+        if (vd) {
+            const double x = (double)th;
+            s[8] += 1.0, s[9] += fabs(x), s[10] += x, s[11] += x * x;
+        }
+        const int bg = v ? hist_bin(sg, 0.0, va.s_hi, va.s_step, va.s_norm, bins) : -1;
+        const int bp = v ? hist_bin(sp, 0.0, va.s_hi, va.s_step, va.s_norm, bins) : -1;
+        const int be = v ? hist_bin(epe, 0.0, va.p_hi, va.p_step, va.p_norm, bins) : -1;
+        const int bt = vd ? hist_bin(th, -180.0, 180.0, va.t_step, va.t_norm, va.dir_bins) : -1;
+        if (LDS) {
+            count_in_lds<false, 2>(vh, bg, bg >= 0);
+            count_in_lds<false, 1>(vh + bins, bp, bp >= 0);
+            count_in_lds<false, 1>(vh + 2 * bins, be, be >= 0);
+            count_in_lds<false, 1>(dh, bt, bt >= 0);
+        } else {
+            if (bg >= 0) atomicAdd(va.vhist + bg, 1ull);
+            if (bp >= 0) atomicAdd(va.vhist + bins + bp, 1ull);
+            if (be >= 0) atomicAdd(va.vhist + 2 * bins + be, 1ull);
+            if (bt >= 0) atomicAdd(va.dir_hist + bt, 1ull);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        mx_e = fmaxf(mx_e, __shfl_xor(mx_e, o, 64));
+        mx_g = fmaxf(mx_g, __shfl_xor(mx_g, o, 64));
+        mx_p = fmaxf(mx_p, __shfl_xor(mx_p, o, 64));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) red_v[wave][k] = s[k];
+        red_x[wave][0] = mx_e, red_x[wave][1] = mx_g, red_x[wave][2] = mx_p;
+    }
+    __syncthreads();
+    if (threadIdx.x < VROW) {
+        const int k = threadIdx.x;
+        double v = 0.0;
+        if (k < 12) v = ((red_v[0][k] + red_v[1][k]) + red_v[2][k]) + red_v[3][k];
+        else if (k < 15) v = (double)fmaxf(fmaxf(red_x[0][k - 12], red_x[1][k - 12]), fmaxf(red_x[2][k - 12], red_x[3][k - 12]));
+        va.vtable[(int64_t)blockIdx.x * VROW + k] = v;
+    }
+    if (LDS) {
+        for (int i = threadIdx.x; i < 3 * bins; i += NT) {
+            const uint32_t n = vh[i];
+            if (n) atomicAdd(va.vhist + i, (unsigned long long)n);
+        }
+        for (int i = threadIdx.x; i < va.dir_bins; i += NT) {
+            const uint32_t n = dh[i];
+            if (n) atomicAdd(va.dir_hist + i, (unsigned long long)n);
+        }
+    }
+}
+
+template <int CY>
+int32_t launch_vec(const VecArgs& va, bool vec, bool in_lds, size_t lds, unsigned rows, hipStream_t s) {
+    const dim3 grid(rows), block(NT);
+    if (in_lds) {
+        if (vec) UCLSTM_LAUNCH((eval_stats_vec_kernel<CY, true, true>), grid, block, lds, s, va);
+        else UCLSTM_LAUNCH((eval_stats_vec_kernel<CY, false, true>), grid, block, lds, s, va);
+    } else {
+        if (vec) UCLSTM_LAUNCH((eval_stats_vec_kernel<CY, true, false>), grid, block, 0, s, va);
+        else UCLSTM_LAUNCH((eval_stats_vec_kernel<CY, false, false>), grid, block, 0, s, va);
+    }
+    return UCLSTM_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t uclstm_eval_stats_vec(const uclstm_eval_vec_desc* d, void* stream) {
+    if (!d || !d->y_pred || !d->y || !d->table || !d->hist || !d->dig_count) return UCLSTM_E_BADARG;
+    if (d->Cy < 1 || d->Cy > UCLSTM_VEC_MAX || d->HW <= 0 || d->B <= 0 || d->T <= 0) return UCLSTM_E_BADARG;
+    if (d->bins < 1 || d->bins > 4096 || d->n_edges < 2 || d->n_edges > 65536) return UCLSTM_E_BADARG;
+    if (d->K < 0 || (d->K > 0 && (!d->scatter || ((uintptr_t)d->scatter % 8)))) return UCLSTM_E_BADARG;
+    if (d->transform != UCLSTM_EVAL_NONE && d->transform != UCLSTM_EVAL_ASINH && d->transform != UCLSTM_EVAL_SIGNED_LOG)
+        return UCLSTM_E_BADARG;
+    for (int c = 0; c < d->Cy; ++c) {
+        if (!(d->hist_hi[c] > d->hist_lo[c]) || !(d->err_hi[c] > d->err_lo[c])) return UCLSTM_E_BADARG;
+        if (!(d->dig_w[c] > 0.0) || !(d->dig_lo[c] == d->dig_lo[c])) return UCLSTM_E_BADARG;
+        if (d->transform != UCLSTM_EVAL_NONE && d->consts[c].y_scale == 0.f) return UCLSTM_E_BADARG;
+    }
+    if (d->pred_stride_b < 0 || d->pred_stride_t < 0 || d->y_stride_b < 0 || d->y_stride_t < 0 ||
+        (d->mask && (d->mask_stride_b < 0 || d->mask_stride_t < 0)))
+        return UCLSTM_E_BADARG;
+    if (d->w_chan < -1 || d->w_chan >= d->Cy || d->h_chan < -1 || d->h_chan >= d->Cy) return UCLSTM_E_BADARG;
+    if (d->w_chan >= 0 && d->w_chan == d->h_chan) return UCLSTM_E_BADARG;
+    if ((d->w_sign != 1 && d->w_sign != -1) || (d->h_sign != 1 && d->h_sign != -1)) return UCLSTM_E_BADARG;
+    if (!(d->speed_hi > 0.0) || !(d->epe_hi > 0.0) || !(d->min_speed >= 0.0)) return UCLSTM_E_BADARG;
+    if (d->dir_bins < 1 || d->dir_bins > 4096) return UCLSTM_E_BADARG;
+    const bool pair = d->w_chan >= 0 && d->h_chan >= 0;
+    if (pair && (!d->vtable || !d->vhist || !d->dir_hist)) return UCLSTM_E_BADARG;
+    const int64_t lim = (int64_t)1 << 31;
+    if (d->HW >= lim) return UCLSTM_E_BADARG;
+    const int64_t frames = (int64_t)d->B * d->T;
+    if (frames >= lim || frames * d->Cy >= lim || frames * d->Cy * d->HW >= lim) return UCLSTM_E_BADARG;
+    const int64_t cpf = (d->HW + CHUNK - 1) / CHUNK;
+    const int64_t rows = frames * cpf;
+    if (rows * NT >= ((int64_t)1 << 32)) return UCLSTM_E_BADARG;        // one block per row, in grid.x
+
+    const int Cy = d->Cy, nd = d->n_edges + 1;
+    VecArgs va = {};
+    for (int c = 0; c < Cy; ++c) {
+        Args& a = va.ch[c];
+        a.yp = d->y_pred + (int64_t)c * d->HW, a.y = d->y + (int64_t)c * d->HW, a.mask = d->mask;
+        a.yp_sb = d->pred_stride_b, a.yp_st = d->pred_stride_t, a.y_sb = d->y_stride_b, a.y_st = d->y_stride_t;
+        a.m_sb = d->mask ? d->mask_stride_b : 0, a.m_st = d->mask ? d->mask_stride_t : 0;
+        a.dT = make_fastdiv((uint32_t)d->T), a.dCpf = make_fastdiv((uint32_t)cpf);
+        a.P = (int)d->HW;
+        a.transform = d->transform;
+        a.yscale = d->consts[c].y_scale, a.tmin = d->consts[c].trans_min, a.trange = d->consts[c].trans_max - d->consts[c].trans_min;
+        a.table = d->table + c * ROW;
+        a.bins = d->bins;
+        const double hw = d->hist_hi[c] - d->hist_lo[c], ew = d->err_hi[c] - d->err_lo[c];
+        a.h_lo = d->hist_lo[c], a.h_hi = d->hist_hi[c], a.h_step = hw / d->bins, a.h_norm = d->bins / hw;
+        a.e_lo = d->err_lo[c], a.e_hi = d->err_hi[c], a.e_step = ew / d->bins, a.e_norm = d->bins / ew;
+        a.hist = (unsigned long long*)d->hist + (int64_t)c * 3 * d->bins;
+        a.d_lo = d->dig_lo[c], a.d_w = d->dig_w[c], a.d_inv_w = 1.0 / d->dig_w[c];
+        a.d_last = d->dig_lo[c] + (double)(d->n_edges - 1) * d->dig_w[c];
+        a.n_edges = d->n_edges;
+        a.dig = (unsigned long long*)d->dig_count + (int64_t)c * nd;
+        a.K = d->K, a.seed = d->seed, a.scatter = d->scatter ? (float2*)d->scatter + (int64_t)c * nd * d->K : nullptr;
+    }
+    va.w_chan = pair ? d->w_chan : -1, va.h_chan = pair ? d->h_chan : -1;
+    va.w_sign = (float)d->w_sign, va.h_sign = (float)d->h_sign;
+    va.s_hi = d->speed_hi, va.s_step = d->speed_hi / d->bins, va.s_norm = d->bins / d->speed_hi;
+    va.p_hi = d->epe_hi, va.p_step = d->epe_hi / d->bins, va.p_norm = d->bins / d->epe_hi;
+    va.t_step = 360.0 / d->dir_bins, va.t_norm = d->dir_bins / 360.0;
+    va.dir_bins = d->dir_bins, va.min_speed = (float)d->min_speed;
+    va.vtable = d->vtable, va.vhist = (unsigned long long*)d->vhist, va.dir_hist = (unsigned long long*)d->dir_hist;
+
+    auto quad = [](const float* p, int64_t sb, int64_t st) { return !p || (((uintptr_t)p % 16) == 0 && sb % 4 == 0 && st % 4 == 0); };
+    const bool vec = d->HW % 4 == 0 && quad(d->y_pred, d->pred_stride_b, d->pred_stride_t) && quad(d->y, d->y_stride_b, d->y_stride_t) &&
+                     quad(d->mask, va.ch[0].m_sb, va.ch[0].m_st);
+    const size_t lds = ((size_t)Cy * (3 * (size_t)d->bins + 3 * (size_t)nd) + 3 * (size_t)d->bins + (size_t)d->dir_bins) * sizeof(uint32_t);
+    const bool in_lds = lds <= LDS_BUDGET;
+    hipStream_t s = (hipStream_t)stream;
+    switch (Cy) {
+        case 1: return launch_vec<1>(va, vec, in_lds, lds, (unsigned)rows, s);
+        case 2: return launch_vec<2>(va, vec, in_lds, lds, (unsigned)rows, s);
+        case 3: return launch_vec<3>(va, vec, in_lds, lds, (unsigned)rows, s);
+        default: return launch_vec<4>(va, vec, in_lds, lds, (unsigned)rows, s);
+    }
+}

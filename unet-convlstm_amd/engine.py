@@ -353,7 +353,8 @@ class VectorNPZDataset(NPZSequenceDataset):
 def _refuse_vector(ds, what: str):
     if isinstance(ds, VectorNPZDataset):
         raise TypeError(f"{what} does not take a vector dataset (VectorNPZDataset): it de-normalises with one scalar set of "
-                        "constants; use evaluate(..., per_channel=True) for per-component metrics")
+                        "constants; use VectorEvalReport / evaluate_vector_report, or evaluate(..., per_channel=True) for "
+                        "per-component metrics")
 
 
 def device_transform(ds, x_raw: torch.Tensor, y_raw: torch.Tensor):
@@ -1770,6 +1771,215 @@ def evaluate_report(model, loader, device, dataset_obj, use_mask=True, tta=None,
     for x, y, mask in loader:
         x, y, mask = x.to(device, non_blocking=True), y.to(device, non_blocking=True), mask.to(device, non_blocking=True)
         y_pred = _stack(model(x)[0]) if tta is None else predict_tta(model, x, tta)
+        loss = compute_loss(y_pred, y, mask, use_mask, spec)
+        total += loss.double() * x.size(0)
+        n += x.size(0)
+        met.add(dataset_obj, y, y_pred, mask, use_mask)
+        rep.add(y, y_pred, mask, use_mask)
+    mae, rmse, me = met.result()
+    return float(total) / max(n, 1), mae, rmse, me, rep.result()
+
+
+def _range_per_channel(v, Cy: int, what: str):
+    """One ``(lo, hi)`` pair, or one pair per channel -> ``Cy`` pairs of floats."""
+    pairs = [v] * Cy if np.ndim(v) == 1 else list(v)
+    if len(pairs) != Cy or any(len(p) != 2 for p in pairs):
+        raise ValueError(f"VectorEvalReport: {what} must be one (lo, hi) pair or one pair per channel ({Cy})")
+    return [(float(lo), float(hi)) for lo, hi in pairs]
+
+
+class VectorEvalReport:
+    """``EvalReport`` for a ``VectorNPZDataset``: ONE kernel per batch (``uclstm_eval_stats_vec``) gives every target channel the
+    statistics of ``EvalReport`` -- channel ``c``'s rows and counts are, bit for bit, those of ``uclstm_eval_stats`` on that channel
+    in place -- and, when the dataset has a w- and an h-channel, what a wind model is judged by, which needs both components of
+    one pixel: speed error, vector (endpoint) error and direction error.
+
+    Vector quantities are in the IMAGE frame: ``a = s_w * v[w_channel]`` along +column, ``b = s_h * v[h_channel]`` along +row
+    (the signs of ``axes``); speed ``sqrt(a^2 + b^2)``, endpoint error ``|p - g|``, direction error the angle from the target to
+    the prediction in degrees in (-180, 180], positive from +column towards +row, counted only where both speeds are
+    ``>= min_speed``.  Per-pixel values are f32, sums f64 and bitwise reproducible.
+
+    ``hist_range``, ``err_range``, ``scatter_range``: one pair, or one pair per channel (``scatter_bin_width`` is common, and the
+    ranges must give the same number of edges).  ``speed_range`` defaults to ``(0, max |hist_range|)`` over the two horizontal
+    channels, ``epe_range`` to ``(0, max |err_range|)`` over them.  ``add`` takes what ``EvalReport.add`` takes (the mask is
+    ``[B,T,1,H,W]``) and reads it in place under the same conditions; ``result`` synchronises once."""
+
+    ROW, VROW = EvalReport.ROW, 16
+    VSUMS = ("n", "sum_abs_ds", "sum_ds_sq", "sum_ds", "sum_speed_gt", "sum_speed_pred", "sum_epe", "sum_epe_sq", "n_dir", "sum_abs_dir",
+             "sum_dir", "sum_dir_sq", "max_epe", "max_speed_gt", "max_speed_pred", "reserved")     # the last axis of vector per_sequence
+
+    def __init__(self, dataset_obj, hist_bins=100, hist_range=(-7.5, 7.5), err_range=(-3.0, 3.0), scatter_range=(-8.0, 8.0),
+                 scatter_bin_width=0.05, points_per_bin=1000, speed_range=None, epe_range=None, dir_bins=72, min_speed=0.5, seed=0,
+                 device="cuda"):
+        if not isinstance(dataset_obj, VectorNPZDataset):
+            raise TypeError("VectorEvalReport takes a VectorNPZDataset; use EvalReport for a scalar dataset")
+        ds = self.ds = dataset_obj
+        if ds.y_transform not in _TRANSFORM_IDS:
+            raise ValueError(f"VectorEvalReport: unknown y_transform {ds.y_transform!r}")
+        Cy = self.Cy = ds.Cy
+        self.transform = _TRANSFORM_IDS[ds.y_transform]
+        self.hist_bins = int(hist_bins)
+        self.hist_range = _range_per_channel(hist_range, Cy, "hist_range")
+        self.err_range = _range_per_channel(err_range, Cy, "err_range")
+        self.points_per_bin, self.seed = int(points_per_bin), int(seed)
+        self.scatter_edges = [EvalReport.make_scatter_edges(r, scatter_bin_width) for r in _range_per_channel(scatter_range, Cy, "scatter_range")]
+        n_edges = len(self.scatter_edges[0])
+        if any(len(e) != n_edges for e in self.scatter_edges):
+            raise ValueError("VectorEvalReport: every channel's scatter_range must give the same number of edges")
+        self.pair = (ds.w_channel, ds.h_channel) if ds.w_channel is not None and ds.h_channel is not None else None
+        hor = self.pair if self.pair else range(Cy)
+        self.speed_range = (0.0, max(abs(v) for c in hor for v in self.hist_range[c])) if speed_range is None else tuple(map(float, speed_range))
+        self.epe_range = (0.0, max(abs(v) for c in hor for v in self.err_range[c])) if epe_range is None else tuple(map(float, epe_range))
+        self.dir_bins, self.min_speed = int(dir_bins), float(min_speed)
+        if not (1 <= self.hist_bins <= 4096) or not (2 <= n_edges <= 65536) or self.points_per_bin < 0:
+            raise ValueError("VectorEvalReport: hist_bins in [1, 4096], 2..65536 scatter edges and points_per_bin >= 0 are required")
+        if self.speed_range[0] != 0.0 or self.epe_range[0] != 0.0 or not self.speed_range[1] > 0 or not self.epe_range[1] > 0:
+            raise ValueError("VectorEvalReport: speed_range and epe_range are (0, hi) with hi > 0")
+        if not (1 <= self.dir_bins <= 4096) or not self.min_speed >= 0:
+            raise ValueError("VectorEvalReport: dir_bins in [1, 4096] and min_speed >= 0 are required")
+        self.device = torch.device(device)
+        self._hist = self._dig = self._scatter = self._vhist = self._dir = None     # device buffers, allocated by the first add()
+        self._tables = []                                      # per add(): (table [rows, Cy, ROW], vtable [rows, VROW] | None, B, T)
+        self.last_pointers = None
+        self.last_copies = 0
+
+    def _describe(self, yp, yt, m):
+        """The descriptor of one launch over validated tensors, and the tables it writes (buffers are allocated on first use)."""
+        from . import _lib as L
+        ds, Cy = self.ds, self.Cy
+        B, T = yt.shape[:2]
+        HW = yt.shape[3] * yt.shape[4]
+        dev = yt.device
+        nd = len(self.scatter_edges[0]) + 1
+        if self._hist is None:
+            self._hist = torch.zeros((Cy, 3, self.hist_bins), dtype=torch.int64, device=dev)
+            self._dig = torch.zeros((Cy, nd), dtype=torch.int64, device=dev)
+            self._scatter = torch.zeros((Cy, nd, max(self.points_per_bin, 1), 2), dtype=torch.float32, device=dev)
+            if self.pair:
+                self._vhist = torch.zeros((3, self.hist_bins), dtype=torch.int64, device=dev)
+                self._dir = torch.zeros(self.dir_bins, dtype=torch.int64, device=dev)
+        rows = int(L.lib.uclstm_eval_stats_rows(HW, B * T))
+        if rows <= 0:
+            raise L.UclstmError(f"VectorEvalReport.add: bad plane / frame count ({HW}, {B * T})")
+        table = torch.empty((rows, Cy, self.ROW), dtype=torch.float64, device=dev)
+        vtable = torch.empty((rows, self.VROW), dtype=torch.float64, device=dev) if self.pair else None
+        d = L.EvalVecDesc()
+        d.y_pred, d.pred_stride_b, d.pred_stride_t = yp.data_ptr(), yp.stride(0), yp.stride(1)
+        d.y, d.y_stride_b, d.y_stride_t = yt.data_ptr(), yt.stride(0), yt.stride(1)
+        if m is not None:
+            d.mask, d.mask_stride_b, d.mask_stride_t = m.data_ptr(), m.stride(0), m.stride(1)
+        d.B, d.T, d.Cy, d.transform, d.HW = B, T, Cy, self.transform, HW
+        for c, k in enumerate(ds.target_consts()):
+            d.consts[c] = k
+            (d.hist_lo[c], d.hist_hi[c]), (d.err_lo[c], d.err_hi[c]) = self.hist_range[c], self.err_range[c]
+            e = self.scatter_edges[c]
+            d.dig_lo[c], d.dig_w[c] = float(e[0]), float(e[1] - e[0])
+        d.bins, d.n_edges, d.K, d.dir_bins = self.hist_bins, nd - 1, self.points_per_bin, self.dir_bins
+        d.seed = self.seed & 0xFFFFFFFFFFFFFFFF
+        d.w_chan, d.h_chan = self.pair if self.pair else (-1, -1)
+        d.w_sign, d.h_sign = ((-1 if ds.axes[c][0] == "-" else 1) for c in self.pair) if self.pair else (1, 1)
+        d.speed_hi, d.epe_hi, d.min_speed = self.speed_range[1], self.epe_range[1], self.min_speed
+        d.table, d.hist, d.dig_count = table.data_ptr(), self._hist.data_ptr(), self._dig.data_ptr()
+        d.scatter = self._scatter.data_ptr() if self.points_per_bin > 0 else None
+        if self.pair:
+            d.vtable, d.vhist, d.dir_hist = vtable.data_ptr(), self._vhist.data_ptr(), self._dir.data_ptr()
+        return d, table, vtable
+
+    @torch.no_grad()
+    def add(self, y, y_pred, mask=None, use_mask=False):
+        from . import _lib as L
+        yp, yt = EvalReport._planes(y_pred, "y_pred"), EvalReport._planes(y, "y")
+        m = EvalReport._planes(mask, "mask") if (use_mask and mask is not None) else None
+        self.last_copies = int(yp is not y_pred) + int(yt is not y) + int(m is not None and m is not mask)
+        B, T, _, H, W = yt.shape
+        if yp.shape != yt.shape or yt.shape[2] != self.Cy or (m is not None and m.shape != (B, T, 1, H, W)):
+            raise L.UclstmError(f"VectorEvalReport.add: y_pred and y must be [B,T,{self.Cy},H,W] and the mask [B,T,1,H,W]: y_pred "
+                                f"{tuple(yp.shape)}, y {tuple(yt.shape)}" + ("" if m is None else f", mask {tuple(m.shape)}"))
+        if self._tables and self._tables[0][3] != T:
+            raise L.UclstmError(f"VectorEvalReport.add: sequences of {T} frames after sequences of {self._tables[0][3]}")
+        d, table, vtable = self._describe(yp, yt, m)
+        L.check(L.lib.uclstm_eval_stats_vec(d, ops._stream()), "eval_stats_vec")
+        self.last_pointers = (yp.data_ptr(), yt.data_ptr(), None if m is None else m.data_ptr())
+        self._tables.append((table, vtable, B, T))
+
+    def result(self) -> dict:
+        """One synchronisation: ``{"channels": [EvalReport.reduce of channel c, ...], "vector": reduce_vector(...) | None, "axes"}``."""
+        if not self._tables:
+            raise ops.L.UclstmError("VectorEvalReport.result: nothing was added")
+        n = len(self._tables)
+        srcs = [t for t, _, _, _ in self._tables] + [self._hist, self._dig, self._scatter]
+        if self.pair:
+            srcs += [v for _, v, _, _ in self._tables] + [self._vhist, self._dir]
+        host = [torch.empty(s.shape, dtype=s.dtype, pin_memory=True) for s in srcs]
+        for h, s in zip(host, srcs):
+            h.copy_(s, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        shapes = [(B, T) for _, _, B, T in self._tables]
+        tables = [h.numpy().reshape(B, T, -1, self.Cy, self.ROW) for h, (B, T) in zip(host, shapes)]
+        hist, dig, scatter = (h.numpy() for h in host[n:n + 3])
+        channels = [EvalReport.reduce([t[:, :, :, c] for t in tables], hist[c], dig[c], scatter[c], hist_range=self.hist_range[c],
+                                      err_range=self.err_range[c], scatter_edges=self.scatter_edges[c], points_per_bin=self.points_per_bin)
+                    for c in range(self.Cy)]
+        vector = None
+        if self.pair:
+            vt = [h.numpy().reshape(B, T, -1, self.VROW) for h, (B, T) in zip(host[n + 3:], shapes)]
+            vector = self.reduce_vector(vt, host[-2].numpy(), host[-1].numpy(), speed_range=self.speed_range, epe_range=self.epe_range)
+        return {"channels": channels, "vector": vector, "axes": self.ds.axes}
+
+    @staticmethod
+    def reduce_vector(vtables, vhist, dir_hist, *, speed_range, epe_range) -> dict:
+        """Raw vector tables -> report, on numpy arrays alone.  ``vtables``: one f64 ``[B, T, chunks, VROW]`` array per ``add`` (rows
+        as ``uclstm_eval_stats_vec`` writes them); ``vhist`` ``[3, bins]``, ``dir_hist`` ``[dir_bins]``.  Rows are combined as in
+        ``EvalReport.reduce``: chunks of a frame, then sequences, then time steps.  ``dir_std`` is the population one."""
+        tabs = [np.asarray(t, dtype=np.float64) for t in vtables]
+        frames = np.concatenate([np.concatenate([t[..., :12].sum(axis=2), t[..., 12:15].max(axis=2), t[..., 15:].sum(axis=2)], axis=-1)
+                                 for t in tabs], axis=0)                                                   # [N, T, VROW]
+        per_t = frames[..., :12].sum(axis=0)
+        g = per_t.sum(axis=0)
+        n, nd = float(g[0]), float(g[8])
+
+        def ratio(a, b):
+            return np.divide(a, b, out=np.zeros_like(a), where=b > 0)
+
+        def over(x, m, root=False):
+            v = float(x / m) if m > 0 else 0.0
+            return math.sqrt(v) if root else v
+
+        mx = frames[..., 12:15].max(axis=(0, 1))
+        dir_bias = over(g[10], nd)
+        vhist, dir_hist = np.asarray(vhist).astype(np.int64), np.asarray(dir_hist).astype(np.int64)
+        return {
+            "n": n,
+            "speed_mae": over(g[1], n), "speed_rmse": over(g[2], n, root=True), "speed_bias": over(g[3], n),
+            "gt_speed_mean": over(g[4], n), "pred_speed_mean": over(g[5], n),
+            "epe_mean": over(g[6], n), "epe_rmse": over(g[7], n, root=True), "epe_max": float(mx[0]) if n > 0 else 0.0,
+            "n_dir": nd,
+            "dir_mae": over(g[9], nd), "dir_bias": dir_bias, "dir_std": math.sqrt(max(over(g[11], nd) - dir_bias * dir_bias, 0.0)),
+            "per_timestep": {"n": per_t[:, 0].copy(), "speed_mae": ratio(per_t[:, 1], per_t[:, 0]), "epe_mean": ratio(per_t[:, 6], per_t[:, 0]),
+                             "dir_mae": ratio(per_t[:, 9], per_t[:, 8])},
+            "per_sequence": frames,
+            "hist_speed_gt": vhist[0], "hist_speed_pred": vhist[1], "hist_epe": vhist[2], "hist_dir": dir_hist,
+            "speed_edges": np.linspace(speed_range[0], speed_range[1], vhist.shape[1] + 1),
+            "epe_edges": np.linspace(epe_range[0], epe_range[1], vhist.shape[1] + 1),
+            "dir_edges": np.linspace(-180.0, 180.0, dir_hist.shape[0] + 1),
+        }
+
+
+@torch.no_grad()
+def evaluate_vector_report(model, loader, device, dataset_obj, use_mask=True, tta=None, loss: Optional[LossSpec] = None, **report_kwargs):
+    """``evaluate()``'s loop for a ``VectorNPZDataset`` with a ``VectorEvalReport`` fed from the same ``y_pred``: returns
+    ``(avg_loss, mae, rmse, me, report)``.  The first four are ``evaluate``'s (pooled over the target channels, computed from the same
+    launches as the report); ``report`` is the dict of ``VectorEvalReport.result``.  With ``tta`` the averaged outputs come back with
+    their channels turned (``predict_tta(dataset=)``)."""
+    rep = VectorEvalReport(dataset_obj, device=device, **report_kwargs)
+    spec = check_spec(loss)
+    model.eval()
+    total = torch.zeros((), dtype=torch.float64, device=device)
+    n = 0
+    met = _Metrics(device)
+    for x, y, mask in loader:
+        x, y, mask = x.to(device, non_blocking=True), y.to(device, non_blocking=True), mask.to(device, non_blocking=True)
+        y_pred = _stack(model(x)[0]) if tta is None else predict_tta(model, x, tta, dataset=dataset_obj)
         loss = compute_loss(y_pred, y, mask, use_mask, spec)
         total += loss.double() * x.size(0)
         n += x.size(0)
