@@ -228,6 +228,39 @@ def test_skewed_targets_give_numpy_counts(share):
     assert r["gt_bin_count"].sum() == gt.size == r["n"]
 
 
+def test_counters_that_just_fit_the_lds_budget_give_numpy_counts():
+    """4096 bins and 1022 edges: 3 * 4096 + 3 * 1023 = 15 357 of the 15 360 counters that 60 KiB hold, the largest configuration
+    whose counters stay in LDS, all of it the one channel's region.  No transform and [-1, 1] -> [-1, 1], so the device's f32 values
+    are numpy's bit for bit (_identity_dataset), and ranges whose edges are exact in binary (steps 2^-11, 2^-14 and 2^-9), so a
+    value on an edge falls to the same side in both: the counts are np.histogram's and np.digitize's on the f64 of those f32
+    values, compared with ==."""
+    ds = _identity_dataset()
+    shape = (2, 3, 1, 47, 47)
+    y, yp = _skewed(shape, 8)                                        # 85 % of the targets share one value: count_in_lds's leader adds
+    kw = dict(hist_bins=4096, hist_range=(-1.0, 1.0), err_range=(-0.125, 0.125), scatter_range=(-1.0, -1.0 + 1021 / 512),
+              scatter_bin_width=1 / 512)
+    rep = U.EvalReport(ds, points_per_bin=4, device=DEV, **kw)
+    edges = rep.scatter_edges
+    assert len(edges) == 1022 and 3 * 4096 + 3 * (len(edges) + 1) == 15357 <= 15 * 1024
+    rep.add(torch.from_numpy(y).to(DEV), _as_model_output(torch.from_numpy(yp)))
+    r = rep.result()
+    g32, p32 = ds.denormalize(y), ds.denormalize(yp)
+    assert g32.dtype == np.float32 and p32.dtype == np.float32
+    gt, pr, d = g32.astype(np.float64).ravel(), p32.astype(np.float64).ravel(), (p32 - g32).astype(np.float64).ravel()
+    want = np.bincount(np.digitize(gt, edges), minlength=len(edges) + 1)
+    assert want.max() >= 0.84 * gt.size
+    for name, got, x, rng_ in (("gt", r["hist_gt"], gt, kw["hist_range"]), ("pred", r["hist_pred"], pr, kw["hist_range"]),
+                               ("err", r["hist_err"], d, kw["err_range"])):
+        ref = np.histogram(x, 4096, rng_)[0]
+        print(f"[eval_report budget] {name}: bins that differ {int((got != ref).sum())}, counted {int(got.sum())} of {x.size}, "
+              f"non-empty bins {int((ref > 0).sum())}")
+        assert np.array_equal(got, ref), (name, np.nonzero(got != ref)[0])
+    assert 0 < r["hist_pred"].sum() < pr.size and 0 < r["hist_err"].sum() < d.size                   # the drop rule is exercised
+    print(f"[eval_report budget] digitize: bins that differ {int((r['gt_bin_count'] != want).sum())}, non-empty bins {int((want > 0).sum())}")
+    assert np.array_equal(r["gt_bin_count"], want)
+    assert np.array_equal(np.bincount(r["scatter_bin"], minlength=len(want)), np.minimum(want, 4))
+
+
 def test_counters_beyond_the_lds_budget_use_the_global_path():
     """4096 bins and 20001 edges do not fit the per-block LDS counters: same figures through per-pixel integer atomics."""
     ds = _dataset("asinh", y_scale=2.0)

@@ -141,6 +141,65 @@ def test_every_channel_equals_the_scalar_kernel_in_place(case, y_transform, use_
     assert all(ch["n"] == n for ch in r["channels"]) and (r["vector"] is None or r["vector"]["n"] == n)
 
 
+# 4096 bins and 1000 edges (-8 + i / 64: exact in binary): 3 * 4096 + 3 * 1001 = 15 291 counters fit the 15 360 of the scalar entry's
+# LDS budget; the vector entry adds its speed and direction counters at every Cy, 15 291 + 3 * 4096 + 72, and counts in global memory.
+ONE_CHANNEL = dict(hist_bins=4096, scatter_range=(-8.0, -8.0 + 999 / 64), scatter_bin_width=1 / 64)
+
+
+@pytest.mark.parametrize("shape", [(2, 3, 1, 47, 47), (2, 2, 1, 64, 64)], ids=["47x47_scalar_loads", "64x64_quads"])
+@pytest.mark.parametrize("use_mask", [True, False])
+def test_one_channel_on_global_counters_equals_the_scalar_entry_on_lds_counters(shape, use_mask):
+    """One tensor through uclstm_eval_stats (LDS counters) and, as Cy = 1, through uclstm_eval_stats_vec (global counters): the two
+    entries run the LDS and the global instantiation of one kernel, and everything that does not depend on block arrival is equal."""
+    ds = vector_dataset((None,), "asinh")
+    y, yp, mask = _inputs(shape, 11)
+    y_d, view, m_d = torch.from_numpy(y).to(DEV), _as_model_output(torch.from_numpy(yp)), torch.from_numpy(mask).to(DEV)
+    K = 8
+    vec = U.VectorEvalReport(ds, points_per_bin=K, seed=5, device=DEV, **ONE_CHANNEL)
+    sca = U.EvalReport(_One(ds, 0), points_per_bin=K, seed=5, device=DEV, **ONE_CHANNEL)
+    words = 3 * 4096 + 3 * (len(sca.scatter_edges) + 1)
+    assert len(vec.scatter_edges[0]) == len(sca.scatter_edges) == 1000 and vec.pair is None
+    assert words == 15291 <= 15 * 1024 < words + 3 * 4096 + vec.dir_bins
+    assert (shape[3] * shape[4] % 4 == 0) == (shape[3] == 64)                  # the 16-byte loader at 64 x 64 only
+    vec.add(y_d, view, m_d, use_mask)
+    sca.add(y_d, view, m_d, use_mask)
+    assert vec.last_copies == 0 == sca.last_copies and vec.last_pointers == sca.last_pointers
+    assert _bits(vec._tables[0][0][:, 0]) == _bits(sca._tables[0][0]), "table rows"
+    assert torch.equal(vec._hist[0], sca._hist) and torch.equal(vec._dig[0], sca._dig), "counts"
+    rv, rs = vec.result(), sca.result()
+    assert rv["vector"] is None and len(rv["channels"]) == 1
+    n = int((mask != 0).sum()) if use_mask else int(np.prod(shape))
+    for r in (rv["channels"][0], rs):
+        cnt = r["gt_bin_count"]
+        assert cnt.sum() == n == r["n"]
+        assert np.array_equal(np.bincount(r["scatter_bin"], minlength=len(cnt)), np.minimum(cnt, K)), "scatter fill"
+
+
+def test_the_two_entry_points_share_no_state():
+    """Scalar entry, vector entry with a pair, scalar entry again, in one process on tensors of one shape: the scalar entry reads
+    [2,3,2,40,40] as one plane of 3200 elements, the vector entry as Cy = 2; the second scalar result is the first, bit for bit."""
+    shape = (2, 3, 2, 40, 40)
+    ds = vector_dataset(("+w", "-h"), "asinh")
+    y, yp, _ = _inputs(shape, 13)
+    y_d, view = torch.from_numpy(y).to(DEV), _as_model_output(torch.from_numpy(yp))
+
+    def scalar():
+        rep = U.EvalReport(_One(ds, 0), points_per_bin=8, seed=5, device=DEV)
+        rep.add(y_d, view)
+        assert rep.last_copies == 0 and rep._tables[0][0].shape[0] == 2 * 3 * 2                     # two chunks per frame
+        return rep, rep.result()
+
+    (rep_a, a) = scalar()
+    vec = U.VectorEvalReport(ds, points_per_bin=8, seed=5, min_speed=MIN_SPEED, device=DEV)
+    vec.add(y_d, view)
+    v = vec.result()
+    assert v["vector"] is not None and v["vector"]["n"] == 2 * 3 * 40 * 40 and len(v["channels"]) == 2
+    (rep_b, b) = scalar()
+    assert _bits(rep_a._tables[0][0]) == _bits(rep_b._tables[0][0])
+    assert torch.equal(rep_a._hist, rep_b._hist) and torch.equal(rep_a._dig, rep_b._dig)
+    _same(a, b, "scalar report")
+
+
 # ---------------------------------------------------------------------------------------------
 # inputs in polar form, and the f64 oracle
 # ---------------------------------------------------------------------------------------------

@@ -125,6 +125,31 @@ def test_each_report_refuses_the_other_kind_of_dataset():
         U.evaluate_report(None, [], "cpu", vec)
 
 
+def test_the_three_evaluation_functions_keep_their_parameter_lists():
+    """One loop serves all three; what a caller passes, and in which order a wrong dataset is refused, is unchanged."""
+    head = ["model", "loader", "device", "dataset_obj", "use_mask"]
+    assert list(inspect.signature(U.evaluate).parameters) == head + ["per_channel", "tta", "loss"]
+    assert list(inspect.signature(U.evaluate_report).parameters) == head + ["tta", "loss", "report_kwargs"]
+    assert list(inspect.signature(U.evaluate_vector_report).parameters) == head + ["tta", "loss", "report_kwargs"]
+    for fn in (U.evaluate, U.evaluate_report, U.evaluate_vector_report):
+        sig = inspect.signature(fn).parameters
+        assert sig["use_mask"].default is True and sig["tta"].default is None and sig["loss"].default is None
+        assert all(sig[k].default is inspect.Parameter.empty for k in head[:4])
+    assert inspect.signature(U.evaluate).parameters["per_channel"].default is False
+    for fn in (U.evaluate_report, U.evaluate_vector_report):
+        assert inspect.signature(fn).parameters["report_kwargs"].kind is inspect.Parameter.VAR_KEYWORD
+    # the wrong dataset is refused before the loss is looked at (a bad `loss` alone is a TypeError that names it)
+    vec = vector_dataset(("+w", "-h", None))
+    with pytest.raises(TypeError, match="vector"):
+        U.evaluate_report(None, [], "cpu", vec, loss="l2")
+    with pytest.raises(TypeError, match="EvalReport"):
+        U.evaluate_vector_report(None, [], "cpu", _Scalar(), loss="l2")
+    with pytest.raises(TypeError, match="LossSpec"):
+        U.evaluate_report(None, [], "cpu", _Scalar(), loss="l2")
+    with pytest.raises(TypeError, match="LossSpec"):
+        U.evaluate_vector_report(None, [], "cpu", vec, loss="l2")
+
+
 def test_cpu_tensors_raise():
     rep = U.VectorEvalReport(vector_dataset(("+w", "-h", None)))
     y = torch.zeros(1, 2, 3, 4, 4)

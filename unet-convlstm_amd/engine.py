@@ -1546,14 +1546,10 @@ def train_one_epoch(model, loader, optimizer, device, dataset_obj, use_mask=True
 
 
 @torch.no_grad()
-def evaluate(model, loader, device, dataset_obj, use_mask=True, per_channel: bool = False, tta=None, loss: Optional[LossSpec] = None):
-    """Reference main.py:150-205.  ``tta``: None, or the ``codes`` of ``predict_tta`` (``"flips"``, ``"d4"``, an iterable): the
-    prediction is then the test-time-augmented mean.  ``loss``: the ``LossSpec`` whose value is averaged (None: the reference's).
-    A ``VectorNPZDataset`` as ``dataset_obj``: the averaged outputs come back with their channels turned (``predict_tta(dataset=)``),
-    the three metrics are pooled over the target channels, and ``per_channel=True`` appends
-    ``{"mae": [Cy], "rmse": [Cy], "me": [Cy]}``."""
+def _evaluate(model, loader, device, dataset_obj, use_mask, tta, spec, report=None):
+    """The loop of ``evaluate``, ``evaluate_report`` and ``evaluate_vector_report``: ``(avg_loss, _Metrics)``; every batch's
+    ``y_pred`` also goes to ``report.add`` when there is a report."""
     vec = dataset_obj if isinstance(dataset_obj, VectorNPZDataset) else None
-    spec = check_spec(loss)
     model.eval()
     total = torch.zeros((), dtype=torch.float64, device=device)
     n = 0
@@ -1565,8 +1561,20 @@ def evaluate(model, loader, device, dataset_obj, use_mask=True, per_channel: boo
         total += loss.double() * x.size(0)
         n += x.size(0)
         met.add(dataset_obj, y, y_pred, mask, use_mask)
-    mae, rmse, me = met.result()
-    return (float(total) / max(n, 1), mae, rmse, me) + ((met.per_channel(),) if per_channel else ())
+        if report is not None:
+            report.add(y, y_pred, mask, use_mask)
+    return float(total) / max(n, 1), met
+
+
+@torch.no_grad()
+def evaluate(model, loader, device, dataset_obj, use_mask=True, per_channel: bool = False, tta=None, loss: Optional[LossSpec] = None):
+    """Reference main.py:150-205.  ``tta``: None, or the ``codes`` of ``predict_tta`` (``"flips"``, ``"d4"``, an iterable): the
+    prediction is then the test-time-augmented mean.  ``loss``: the ``LossSpec`` whose value is averaged (None: the reference's).
+    A ``VectorNPZDataset`` as ``dataset_obj``: the averaged outputs come back with their channels turned (``predict_tta(dataset=)``),
+    the three metrics are pooled over the target channels, and ``per_channel=True`` appends
+    ``{"mae": [Cy], "rmse": [Cy], "me": [Cy]}``."""
+    avg, met = _evaluate(model, loader, device, dataset_obj, use_mask, tta, check_spec(loss))
+    return (avg,) + met.result() + ((met.per_channel(),) if per_channel else ())
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1575,7 +1583,73 @@ def evaluate(model, loader, device, dataset_obj, use_mask=True, per_channel: boo
 _TRANSFORM_IDS = {None: 0, "none": 0, "asinh": 1, "signed_log": 2}
 
 
-class EvalReport:
+class _ReportBase:
+    """What ``EvalReport`` and ``VectorEvalReport`` do alike around their one launch per ``add``.  ``_tables`` holds one tuple per
+    ``add`` whose last entry is ``T``."""
+
+    @staticmethod
+    def _planes(t: torch.Tensor, what: str) -> torch.Tensor:
+        """f32 ``[B,T,C,H,W]`` device tensor whose frames are contiguous planes; anything else is converted / copied once."""
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ops.L.UclstmError(f"EvalReport.add: {what}: a HIP device tensor is required (this package has no CPU path)")
+        if t.dim() != 5:
+            raise ops.L.UclstmError(f"EvalReport.add: {what}: expected [B,T,C,H,W], got {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            t = t.float()
+        want, ok = 1, t.stride(0) >= 0 and t.stride(1) >= 0
+        for dim in (4, 3, 2):
+            ok = ok and (t.size(dim) == 1 or t.stride(dim) == want)
+            want *= t.size(dim)
+        return t if ok else t.contiguous()
+
+    def _begin(self, device):
+        self.device = torch.device(device)
+        self._tables = []
+        self.last_pointers = None                              # (y_pred, y, mask) addresses handed to the library by the last add()
+        self.last_copies = 0                                   # how many of the last add()'s tensors were converted or copied first
+
+    def _inputs(self, y, y_pred, mask, use_mask):
+        """``(y_pred, y, mask | None)`` as the kernel reads them; ``last_copies`` counts those that were converted or copied."""
+        yp, yt = self._planes(y_pred, "y_pred"), self._planes(y, "y")
+        m = self._planes(mask, "mask") if (use_mask and mask is not None) else None
+        self.last_copies = int(yp is not y_pred) + int(yt is not y) + int(m is not None and m is not mask)
+        return yp, yt, m
+
+    def _rows(self, P, frames) -> int:
+        rows = int(ops.L.lib.uclstm_eval_stats_rows(P, frames))
+        if rows <= 0:
+            raise ops.L.UclstmError(f"{type(self).__name__}.add: bad plane / frame count ({P}, {frames})")
+        return rows
+
+    @staticmethod
+    def _point(d, yp, yt, m):
+        """The pointer and stride fields that ``EvalDesc`` and ``EvalVecDesc`` share."""
+        d.y_pred, d.pred_stride_b, d.pred_stride_t = yp.data_ptr(), yp.stride(0), yp.stride(1)
+        d.y, d.y_stride_b, d.y_stride_t = yt.data_ptr(), yt.stride(0), yt.stride(1)
+        if m is not None:
+            d.mask, d.mask_stride_b, d.mask_stride_t = m.data_ptr(), m.stride(0), m.stride(1)
+
+    def _launch(self, entry, name, yp, yt, m):
+        """``_describe``, one launch and the bookkeeping of an ``add``: ``T`` is the same in every ``add``."""
+        T = yt.shape[1]
+        if self._tables and self._tables[0][-1] != T:
+            raise ops.L.UclstmError(f"{type(self).__name__}.add: sequences of {T} frames after sequences of {self._tables[0][-1]}")
+        d, *written = self._describe(yp, yt, m)
+        ops.L.check(entry(d, ops._stream()), name)
+        self.last_pointers = (yp.data_ptr(), yt.data_ptr(), None if m is None else m.data_ptr())
+        self._tables.append((*written, yt.shape[0], T))
+
+    @staticmethod
+    def _read_back(srcs):
+        """Every buffer copied to pinned host memory on the current stream, one synchronisation: numpy arrays in the order of ``srcs``."""
+        host = [torch.empty(s.shape, dtype=s.dtype, pin_memory=True) for s in srcs]
+        for h, s in zip(host, srcs):
+            h.copy_(s, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return [h.numpy() for h in host]
+
+
+class EvalReport(_ReportBase):
     """The statistics of the reference's evaluation scripts, accumulated on the device by ONE kernel per batch
     (``uclstm_eval_stats``): global MAE / RMSE / bias / error std (train/get_metrics.py:188-191), MAE per time step
     (``:281-297``), the three 100-bin histograms (``:317-358``), the ``np.digitize`` count of the target and the balanced
@@ -1610,31 +1684,13 @@ class EvalReport:
         self.scatter_edges = self.make_scatter_edges(scatter_range, scatter_bin_width)
         if not (1 <= self.hist_bins <= 4096) or not (2 <= len(self.scatter_edges) <= 65536) or self.points_per_bin < 0:
             raise ValueError("EvalReport: hist_bins in [1, 4096], 2..65536 scatter edges and points_per_bin >= 0 are required")
-        self.device = torch.device(device)
         self._hist = self._dig = self._scatter = None          # device buffers, allocated by the first add()
-        self._tables = []                                      # per add(): (f64 [rows, ROW] device tensor, B, T)
-        self.last_pointers = None                              # (y_pred, y, mask) addresses handed to the library by the last add()
-        self.last_copies = 0                                   # how many of the last add()'s tensors were converted or copied first
+        self._begin(device)                                    # _tables, per add(): (f64 [rows, ROW] device tensor, B, T)
 
     @staticmethod
     def make_scatter_edges(scatter_range, width) -> np.ndarray:
         """get_metrics.py:210: ``np.arange(lo, hi + width, width)`` in f64 (321 edges for the defaults)."""
         return np.arange(float(scatter_range[0]), float(scatter_range[1]) + float(width), float(width), dtype=np.float64)
-
-    @staticmethod
-    def _planes(t: torch.Tensor, what: str) -> torch.Tensor:
-        """f32 ``[B,T,C,H,W]`` device tensor whose frames are contiguous planes; anything else is converted / copied once."""
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ops.L.UclstmError(f"EvalReport.add: {what}: a HIP device tensor is required (this package has no CPU path)")
-        if t.dim() != 5:
-            raise ops.L.UclstmError(f"EvalReport.add: {what}: expected [B,T,C,H,W], got {tuple(t.shape)}")
-        if t.dtype != torch.float32:
-            t = t.float()
-        want, ok = 1, t.stride(0) >= 0 and t.stride(1) >= 0
-        for dim in (4, 3, 2):
-            ok = ok and (t.size(dim) == 1 or t.stride(dim) == want)
-            want *= t.size(dim)
-        return t if ok else t.contiguous()
 
     def _describe(self, yp, yt, m):
         """The descriptor of one launch over validated tensors, and the table it writes (buffers are allocated on first use)."""
@@ -1647,15 +1703,9 @@ class EvalReport:
             self._hist = torch.zeros((3, self.hist_bins), dtype=torch.int64, device=dev)
             self._dig = torch.zeros(nd, dtype=torch.int64, device=dev)
             self._scatter = torch.zeros((nd, max(self.points_per_bin, 1), 2), dtype=torch.float32, device=dev)
-        rows = int(L.lib.uclstm_eval_stats_rows(P, B * T))
-        if rows <= 0:
-            raise L.UclstmError(f"EvalReport.add: bad plane / frame count ({P}, {B * T})")
-        table = torch.empty((rows, self.ROW), dtype=torch.float64, device=dev)
+        table = torch.empty((self._rows(P, B * T), self.ROW), dtype=torch.float64, device=dev)
         d = L.EvalDesc()
-        d.y_pred, d.pred_stride_b, d.pred_stride_t = yp.data_ptr(), yp.stride(0), yp.stride(1)
-        d.y, d.y_stride_b, d.y_stride_t = yt.data_ptr(), yt.stride(0), yt.stride(1)
-        if m is not None:
-            d.mask, d.mask_stride_b, d.mask_stride_t = m.data_ptr(), m.stride(0), m.stride(1)
+        self._point(d, yp, yt, m)
         d.B, d.T, d.P = B, T, P
         d.transform, d.y_scale, d.trans_min, d.trans_max = self.transform, self.y_scale, self.trans_min, self.trans_max
         d.table = table.data_ptr()
@@ -1670,31 +1720,18 @@ class EvalReport:
     @torch.no_grad()
     def add(self, y, y_pred, mask=None, use_mask=False):
         from . import _lib as L
-        yp, yt = self._planes(y_pred, "y_pred"), self._planes(y, "y")
-        m = self._planes(mask, "mask") if (use_mask and mask is not None) else None
-        self.last_copies = int(yp is not y_pred) + int(yt is not y) + int(m is not None and m is not mask)
+        yp, yt, m = self._inputs(y, y_pred, mask, use_mask)
         if yp.shape != yt.shape or (m is not None and m.shape != yt.shape):
             raise L.UclstmError(f"EvalReport.add: shapes differ: y_pred {tuple(yp.shape)}, y {tuple(yt.shape)}"
                                 + ("" if m is None else f", mask {tuple(m.shape)}"))
-        B, T = yt.shape[:2]
-        if self._tables and self._tables[0][2] != T:
-            raise L.UclstmError(f"EvalReport.add: sequences of {T} frames after sequences of {self._tables[0][2]}")
-        d, table = self._describe(yp, yt, m)
-        L.check(L.lib.uclstm_eval_stats(d, ops._stream()), "eval_stats")
-        self.last_pointers = (yp.data_ptr(), yt.data_ptr(), None if m is None else m.data_ptr())
-        self._tables.append((table, B, T))
+        self._launch(L.lib.uclstm_eval_stats, "eval_stats", yp, yt, m)
 
     def result(self) -> dict:
         """One synchronisation: every buffer is copied to pinned host memory on the current stream, then reduced on the host."""
         if not self._tables:
             raise ops.L.UclstmError("EvalReport.result: nothing was added")
-        srcs = [t for t, _, _ in self._tables] + [self._hist, self._dig, self._scatter]
-        host = [torch.empty(s.shape, dtype=s.dtype, pin_memory=True) for s in srcs]
-        for h, s in zip(host, srcs):
-            h.copy_(s, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        tables = [h.numpy().reshape(B, T, -1, self.ROW) for h, (_, B, T) in zip(host, self._tables)]
-        hist, dig, scatter = (h.numpy() for h in host[len(tables):])
+        *tables, hist, dig, scatter = self._read_back([t for t, _, _ in self._tables] + [self._hist, self._dig, self._scatter])
+        tables = [h.reshape(B, T, -1, self.ROW) for h, (_, B, T) in zip(tables, self._tables)]
         return self.reduce(tables, hist, dig, scatter, hist_range=self.hist_range, err_range=self.err_range,
                            scatter_edges=self.scatter_edges, points_per_bin=self.points_per_bin)
 
@@ -1763,21 +1800,9 @@ def evaluate_report(model, loader, device, dataset_obj, use_mask=True, tta=None,
     kernels add their block partials in a fixed order and two passes are identical.)  ``tta`` and ``loss``: as in ``evaluate``."""
     _refuse_vector(dataset_obj, "evaluate_report")
     spec = check_spec(loss)
-    model.eval()
-    total = torch.zeros((), dtype=torch.float64, device=device)
-    n = 0
-    met = _Metrics(device)
     rep = EvalReport(dataset_obj, device=device, **report_kwargs)
-    for x, y, mask in loader:
-        x, y, mask = x.to(device, non_blocking=True), y.to(device, non_blocking=True), mask.to(device, non_blocking=True)
-        y_pred = _stack(model(x)[0]) if tta is None else predict_tta(model, x, tta)
-        loss = compute_loss(y_pred, y, mask, use_mask, spec)
-        total += loss.double() * x.size(0)
-        n += x.size(0)
-        met.add(dataset_obj, y, y_pred, mask, use_mask)
-        rep.add(y, y_pred, mask, use_mask)
-    mae, rmse, me = met.result()
-    return float(total) / max(n, 1), mae, rmse, me, rep.result()
+    avg, met = _evaluate(model, loader, device, dataset_obj, use_mask, tta, spec, rep)
+    return (avg,) + met.result() + (rep.result(),)
 
 
 def _range_per_channel(v, Cy: int, what: str):
@@ -1788,7 +1813,7 @@ def _range_per_channel(v, Cy: int, what: str):
     return [(float(lo), float(hi)) for lo, hi in pairs]
 
 
-class VectorEvalReport:
+class VectorEvalReport(_ReportBase):
     """``EvalReport`` for a ``VectorNPZDataset``: ONE kernel per batch (``uclstm_eval_stats_vec``) gives every target channel the
     statistics of ``EvalReport`` -- channel ``c``'s rows and counts are, bit for bit, those of ``uclstm_eval_stats`` on that channel
     in place -- and, when the dataset has a w- and an h-channel, what a wind model is judged by, which needs both components of
@@ -1837,11 +1862,8 @@ class VectorEvalReport:
             raise ValueError("VectorEvalReport: speed_range and epe_range are (0, hi) with hi > 0")
         if not (1 <= self.dir_bins <= 4096) or not self.min_speed >= 0:
             raise ValueError("VectorEvalReport: dir_bins in [1, 4096] and min_speed >= 0 are required")
-        self.device = torch.device(device)
         self._hist = self._dig = self._scatter = self._vhist = self._dir = None     # device buffers, allocated by the first add()
-        self._tables = []                                      # per add(): (table [rows, Cy, ROW], vtable [rows, VROW] | None, B, T)
-        self.last_pointers = None
-        self.last_copies = 0
+        self._begin(device)                                    # _tables, per add(): (table [rows, Cy, ROW], vtable [rows, VROW] | None, B, T)
 
     def _describe(self, yp, yt, m):
         """The descriptor of one launch over validated tensors, and the tables it writes (buffers are allocated on first use)."""
@@ -1858,16 +1880,11 @@ class VectorEvalReport:
             if self.pair:
                 self._vhist = torch.zeros((3, self.hist_bins), dtype=torch.int64, device=dev)
                 self._dir = torch.zeros(self.dir_bins, dtype=torch.int64, device=dev)
-        rows = int(L.lib.uclstm_eval_stats_rows(HW, B * T))
-        if rows <= 0:
-            raise L.UclstmError(f"VectorEvalReport.add: bad plane / frame count ({HW}, {B * T})")
+        rows = self._rows(HW, B * T)
         table = torch.empty((rows, Cy, self.ROW), dtype=torch.float64, device=dev)
         vtable = torch.empty((rows, self.VROW), dtype=torch.float64, device=dev) if self.pair else None
         d = L.EvalVecDesc()
-        d.y_pred, d.pred_stride_b, d.pred_stride_t = yp.data_ptr(), yp.stride(0), yp.stride(1)
-        d.y, d.y_stride_b, d.y_stride_t = yt.data_ptr(), yt.stride(0), yt.stride(1)
-        if m is not None:
-            d.mask, d.mask_stride_b, d.mask_stride_t = m.data_ptr(), m.stride(0), m.stride(1)
+        self._point(d, yp, yt, m)
         d.B, d.T, d.Cy, d.transform, d.HW = B, T, Cy, self.transform, HW
         for c, k in enumerate(ds.target_consts()):
             d.consts[c] = k
@@ -1888,19 +1905,12 @@ class VectorEvalReport:
     @torch.no_grad()
     def add(self, y, y_pred, mask=None, use_mask=False):
         from . import _lib as L
-        yp, yt = EvalReport._planes(y_pred, "y_pred"), EvalReport._planes(y, "y")
-        m = EvalReport._planes(mask, "mask") if (use_mask and mask is not None) else None
-        self.last_copies = int(yp is not y_pred) + int(yt is not y) + int(m is not None and m is not mask)
+        yp, yt, m = self._inputs(y, y_pred, mask, use_mask)
         B, T, _, H, W = yt.shape
         if yp.shape != yt.shape or yt.shape[2] != self.Cy or (m is not None and m.shape != (B, T, 1, H, W)):
             raise L.UclstmError(f"VectorEvalReport.add: y_pred and y must be [B,T,{self.Cy},H,W] and the mask [B,T,1,H,W]: y_pred "
                                 f"{tuple(yp.shape)}, y {tuple(yt.shape)}" + ("" if m is None else f", mask {tuple(m.shape)}"))
-        if self._tables and self._tables[0][3] != T:
-            raise L.UclstmError(f"VectorEvalReport.add: sequences of {T} frames after sequences of {self._tables[0][3]}")
-        d, table, vtable = self._describe(yp, yt, m)
-        L.check(L.lib.uclstm_eval_stats_vec(d, ops._stream()), "eval_stats_vec")
-        self.last_pointers = (yp.data_ptr(), yt.data_ptr(), None if m is None else m.data_ptr())
-        self._tables.append((table, vtable, B, T))
+        self._launch(L.lib.uclstm_eval_stats_vec, "eval_stats_vec", yp, yt, m)
 
     def result(self) -> dict:
         """One synchronisation: ``{"channels": [EvalReport.reduce of channel c, ...], "vector": reduce_vector(...) | None, "axes"}``."""
@@ -1910,20 +1920,17 @@ class VectorEvalReport:
         srcs = [t for t, _, _, _ in self._tables] + [self._hist, self._dig, self._scatter]
         if self.pair:
             srcs += [v for _, v, _, _ in self._tables] + [self._vhist, self._dir]
-        host = [torch.empty(s.shape, dtype=s.dtype, pin_memory=True) for s in srcs]
-        for h, s in zip(host, srcs):
-            h.copy_(s, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
+        host = self._read_back(srcs)
         shapes = [(B, T) for _, _, B, T in self._tables]
-        tables = [h.numpy().reshape(B, T, -1, self.Cy, self.ROW) for h, (B, T) in zip(host, shapes)]
-        hist, dig, scatter = (h.numpy() for h in host[n:n + 3])
+        tables = [h.reshape(B, T, -1, self.Cy, self.ROW) for h, (B, T) in zip(host, shapes)]
+        hist, dig, scatter = host[n:n + 3]
         channels = [EvalReport.reduce([t[:, :, :, c] for t in tables], hist[c], dig[c], scatter[c], hist_range=self.hist_range[c],
                                       err_range=self.err_range[c], scatter_edges=self.scatter_edges[c], points_per_bin=self.points_per_bin)
                     for c in range(self.Cy)]
         vector = None
         if self.pair:
-            vt = [h.numpy().reshape(B, T, -1, self.VROW) for h, (B, T) in zip(host[n + 3:], shapes)]
-            vector = self.reduce_vector(vt, host[-2].numpy(), host[-1].numpy(), speed_range=self.speed_range, epe_range=self.epe_range)
+            vt = [h.reshape(B, T, -1, self.VROW) for h, (B, T) in zip(host[n + 3:], shapes)]
+            vector = self.reduce_vector(vt, host[-2], host[-1], speed_range=self.speed_range, epe_range=self.epe_range)
         return {"channels": channels, "vector": vector, "axes": self.ds.axes}
 
     @staticmethod
@@ -1972,18 +1979,5 @@ def evaluate_vector_report(model, loader, device, dataset_obj, use_mask=True, tt
     launches as the report); ``report`` is the dict of ``VectorEvalReport.result``.  With ``tta`` the averaged outputs come back with
     their channels turned (``predict_tta(dataset=)``)."""
     rep = VectorEvalReport(dataset_obj, device=device, **report_kwargs)
-    spec = check_spec(loss)
-    model.eval()
-    total = torch.zeros((), dtype=torch.float64, device=device)
-    n = 0
-    met = _Metrics(device)
-    for x, y, mask in loader:
-        x, y, mask = x.to(device, non_blocking=True), y.to(device, non_blocking=True), mask.to(device, non_blocking=True)
-        y_pred = _stack(model(x)[0]) if tta is None else predict_tta(model, x, tta, dataset=dataset_obj)
-        loss = compute_loss(y_pred, y, mask, use_mask, spec)
-        total += loss.double() * x.size(0)
-        n += x.size(0)
-        met.add(dataset_obj, y, y_pred, mask, use_mask)
-        rep.add(y, y_pred, mask, use_mask)
-    mae, rmse, me = met.result()
-    return float(total) / max(n, 1), mae, rmse, me, rep.result()
+    avg, met = _evaluate(model, loader, device, dataset_obj, use_mask, tta, check_spec(loss), rep)
+    return (avg,) + met.result() + (rep.result(),)
