@@ -189,6 +189,13 @@ int32_t uclstm_igemm_wgrad_splits(const uclstm_wgrad_desc* d);
  * 1 = 64 x 256 / 64 x 192 tile (C_out <= 64), 0 = generic addressing (non-power-of-two images,
  * ConvTranspose, offset sources, kernels wider than 3x3).  Used by bench.py to price each kernel separately. */
 int32_t uclstm_igemm_wgrad_shape(const uclstm_wgrad_desc* d);
+/* The valid-pixel walk of one tap (host only, nothing is launched): a 256 x 256 tile of a 3x3 / pad 1 launch whose tiles each
+ * belong to one tap reduces over the output pixels whose source pixel (y + tap / ktap - pad, x + tap % ktap - pad) lies inside
+ * the image, image by image and row by row -- n_img * hv * wv entries instead of n_img * H * W.  Fills pixels[k] with the pixel
+ * index (img * H * W + y * W + x) of entry i0 + k for k in [0, n), -1 past the end, through the same inline function the kernels
+ * stage with (csrc/wgrad_walk.h), and returns the number of entries of the whole walk (>= 0) or UCLSTM_E_BADARG.  Reads n_img,
+ * H, W, ktap and pad of the descriptor only.  UCLSTM_WGRAD_VALID=0 (read once per process) makes those launches walk every pixel. */
+int64_t uclstm_igemm_wgrad_walk(const uclstm_wgrad_desc* d, int32_t tap, int64_t i0, int32_t n, int32_t* pixels);
 
 /* ------------------------------------------------------------------------------------ */
 /* Weight panels                                                                        */

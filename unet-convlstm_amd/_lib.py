@@ -159,6 +159,7 @@ _PROTOS = {
     "uclstm_igemm_wgrad": [C.POINTER(WgradDesc), _P],
     "uclstm_igemm_wgrad_splits": [C.POINTER(WgradDesc)],
     "uclstm_igemm_wgrad_shape": [C.POINTER(WgradDesc)],
+    "uclstm_igemm_wgrad_walk": [C.POINTER(WgradDesc), _I, _L, _I, C.POINTER(C.c_int32)],
     "uclstm_pack_weights": [C.POINTER(PackDesc), _P, _P, _P],
     "uclstm_pack_job_init": [C.POINTER(PackJob), C.POINTER(PackDesc), _P, _P, _I],
     "uclstm_pack_weights_batched": [_P, _I, _I, _I, _P],
@@ -268,7 +269,7 @@ _PROTOS = {
     "uclstm_source_hash": [],
     "uclstm_last_error_string": [],
 }
-_RESTYPES = {"uclstm_build_arch": C.c_char_p, "uclstm_source_hash": C.c_char_p, "uclstm_last_error_string": C.c_char_p, "uclstm_bn_bwd_reduce_rows": C.c_int64, "uclstm_bn_pool_bwd_rows": C.c_int64,
+_RESTYPES = {"uclstm_igemm_wgrad_walk": C.c_int64, "uclstm_build_arch": C.c_char_p, "uclstm_source_hash": C.c_char_p, "uclstm_last_error_string": C.c_char_p, "uclstm_bn_bwd_reduce_rows": C.c_int64, "uclstm_bn_pool_bwd_rows": C.c_int64,
              "uclstm_eval_stats_rows": C.c_int64, "uclstm_colsum_ordered_rows": C.c_int64, "uclstm_outconv_bwd_ordered_rows": C.c_int64, "uclstm_head3x3_bwd_ordered_rows": C.c_int64,
              "uclstm_loss_fwd_ordered_rows": C.c_int64, "uclstm_sumsq_ordered_rows": C.c_int64, "uclstm_metric_sums_ordered_rows": C.c_int64, "uclstm_metric_sums_vec_rows": C.c_int64,
              "uclstm_bn_add_relu_bwd_rows": C.c_int64, "uclstm_select_workspace_bytes": C.c_int64}

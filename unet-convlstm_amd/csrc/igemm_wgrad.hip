@@ -17,6 +17,7 @@
 // gradient): operand offsets are linear in the pixel index, only the tap-validity needs (y, x).  The tile is added to
 // dWp with f32 atomics staged through LDS (256 contiguous bytes per wave instruction).
 #include "common.h"
+#include "wgrad_walk.h"
 #include <cstdlib>
 
 namespace {
@@ -38,6 +39,8 @@ struct WDerived {
     long chunk;          // pixels per split (multiple of 64)
     int kt_per_tap;      // K-column tiles per tap when a tap is a whole number of tiles, else 0 (no tap-minor order)
     FastDiv dHW, dW, dPerTap;
+    // valid-pixel walk of the 256 x 256 kernels (wgrad_walk.h): divisors of the rectangle [ddy != 0][ddx != 0] of a 3x3 / pad 1 tap
+    WalkDiv dWv[2], dNv[2][2];
 };
 
 typedef __attribute__((address_space(3))) short4v* lds_s4p;
@@ -490,7 +493,42 @@ constexpr int P3_HALF = 2 * PLANE;            // 16 KiB
 constexpr int P3_BUF = 4 * P3_HALF;           // 64 KiB
 constexpr int P3_SMEM = 2 * P3_BUF;           // 128 KiB
 
-template <int NSRC, int P3_LEAD>
+// VW (both 256 x 256 kernels): the valid-pixel walk.  Every tile of a launch with kt_per_tap > 0 belongs to ONE tap, and the pixels
+// whose tap falls outside the image contribute zeros: such a tile stages row i of the tap's walk (wgrad_walk.h) instead of pixel i,
+// i.e. n_img * hv * wv rows instead of n_img * H * W -- (10/12)^2 = 69 % of the K-tiles on a 4 x 4 image.  dY is read at the
+// walk's pixel and X at that pixel + the tap shift, which is inside the image by construction, so the tap-validity compare is
+// gone; rows past the end of the block's range carry the out-of-range offset (zero fill).  The per-lane offset is no longer loop
+// invariant (one walk entry per staged row; the scalar offset stays 0), everything after the DMA -- LDS layout, slot ring, DMA
+// count per half, vmcnt counts, barriers -- is that of the dense walk.  Pixel range sp of `splits` owns K-tiles
+// [sp * per, (sp + 1) * per) of the tap's own walk, per = ceil(tap K-tiles / splits) (the centre tap: exactly the dense ranges);
+// a range that owns none still stores its tile of zeros in slab mode.  Tiles of a group of nine are handed out longest first
+// (centre, edges, corners).  Host side: `vw` in wgrad_run; UCLSTM_WGRAD_VALID=0 selects the dense instantiation (VW = false: the code below as
+// it was, same registers).  The walk is SMALL (wgrad_walk.h): H, W powers of two on this path, fewer than 2^24 pixels.
+struct WalkTile {
+    ValidWalk w;           // total lowered to the end of this block's range
+    uint32_t i0;           // first walk entry of the block
+    int KT;                // its 64-row K-tiles
+    int kt;                // its K-column tile
+    int ddy, ddx;
+};
+__device__ __forceinline__ WalkTile walk_tile(const uclstm_wgrad_desc& d, const WDerived& dv, int kts, int sp) {
+    WalkTile t;
+    const int cg = kts / 9;
+    const int tap = (int)((0x862075314ull >> (4 * (kts - cg * 9))) & 15);      // centre, four edges, four corners
+    t.kt = tap * dv.kt_per_tap + cg;
+    const int ty = tap / 3;
+    t.ddy = ty - 1;
+    t.ddx = tap - 3 * ty - 1;
+    const int iy = t.ddy != 0, ix = t.ddx != 0;
+    t.w = make_valid_walk(d.n_img, d.H, d.W, t.ddy, t.ddx, dv.dNv[iy][ix], dv.dWv[ix]);
+    int kb;
+    valid_walk_range(t.w.total, d.splits, sp, kb, t.KT);
+    t.i0 = (uint32_t)kb * TP;
+    t.w.total = min(t.w.total, (uint32_t)(kb + t.KT) * TP);
+    return t;
+}
+
+template <int NSRC, int P3_LEAD, bool VW>
 __global__ __launch_bounds__(512, 1) void igemm_wgrad_p3_kernel(const uclstm_wgrad_desc d, const WDerived dv, const P2 p2) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -509,18 +547,23 @@ __global__ __launch_bounds__(512, 1) void igemm_wgrad_p3_kernel(const uclstm_wgr
     int nt, kts;
     grouped_tile(rr, dv.n_nt, dv.n_kt, 4, nt, kts);
     int kt = kts;
-    if (dv.kt_per_tap > 0) {
+    if (!VW && dv.kt_per_tap > 0) {
         const int ntaps = d.ktap * d.ktap;
         const int cg = kts / ntaps;
         kt = (kts - cg * ntaps) * dv.kt_per_tap + cg;
+    }
+    WalkTile wt{};
+    if constexpr (VW) {
+        wt = walk_tile(d, dv, kts, sp);
+        kt = wt.kt;
     }
     const int n0 = nt * 256;
     const int kbase = kt * 256;
 
     const long m_begin = (long)sp * dv.chunk;
     const long m_end = min(dv.M, m_begin + dv.chunk);
-    const int KT = m_begin < dv.M ? (int)((m_end - m_begin) / TP) : 0;      // block-uniform; 0: nothing to do (but every
-    if (KT == 0) return;                                                      // wave of the block leaves together)
+    const int KT = VW ? wt.KT : (m_begin < dv.M ? (int)((m_end - m_begin) / TP) : 0);      // block-uniform; 0: nothing to do (but
+    if (KT == 0 && !(VW && d.slab > 0)) return;       // every wave of the block leaves together); VW slabs: a tile of zeros is due
     const int total_halves = 4 * KT;
 
     const uclstm_seg G = d.seg[0];
@@ -536,6 +579,7 @@ __global__ __launch_bounds__(512, 1) void igemm_wgrad_p3_kernel(const uclstm_wgr
     const int cp = lane & 7;
     const int sc = 2 * ((cp >> 1) ^ ((lrow >> 1) & 3)) + (cp & 1);      // source 16-byte chunk stored at this position
     const int r = 8 * wave + lrow;                                       // pixel row of the stage
+    const int rv = VW ? 0 : r;                                           // VW: the row's pixel comes from the walk, per K-tile
     const int Wm = d.W - 1, Hm = d.H - 1;
     const int kseg = dv.kseg0 + dv.kseg1;
     uint32_t yvoff[4], xvoff[4], kxj[4], kyj[4];
@@ -544,7 +588,7 @@ __global__ __launch_bounds__(512, 1) void igemm_wgrad_p3_kernel(const uclstm_wgr
     for (int pl = 0; pl < 4; ++pl) {
         const int ny = n0 + pl * 64 + sc * 8;
         const bool yok = ny < d.N && ny >= G.n_begin && ny < G.n_end;
-        yvoff[pl] = yok ? (uint32_t)(2 * (r * G.C + G.c_off + (ny - G.n_begin))) : OOB;
+        yvoff[pl] = yok ? (uint32_t)(2 * (rv * G.C + G.c_off + (ny - G.n_begin))) : OOB;
         const int k0 = kbase + pl * 64;
         const int xtap = (int)fdiv((uint32_t)k0, dv.dPerTap);
         const int kr = k0 - xtap * kseg;
@@ -558,7 +602,7 @@ __global__ __launch_bounds__(512, 1) void igemm_wgrad_p3_kernel(const uclstm_wgr
         const int badx = ddx < 0 ? 0 : (ddx > 0 ? Wm : -1);
         const int bady = ddy < 0 ? 0 : (ddy > 0 ? Hm : -1);
         xsrc[pl] = xs_;
-        xvoff[pl] = xok ? (uint32_t)(2 * (r * S.C + (ddy * S.Ws + ddx) * S.C + xc) + (int)p2.xbias[xs_]) : OOB;
+        xvoff[pl] = xok ? (uint32_t)(2 * (rv * S.C + (ddy * S.Ws + ddx) * S.C + xc) + (int)p2.xbias[xs_]) : OOB;
         if (badx < 0) kxj[pl] = 0xffffffffu;
         else if (d.W >= 64) kxj[pl] = (uint32_t)(badx - r);
         else kxj[pl] = ((r & Wm) == badx) ? 0u : 0xffffffffu;
@@ -570,6 +614,25 @@ __global__ __launch_bounds__(512, 1) void igemm_wgrad_p3_kernel(const uclstm_wgr
     // half-tile `slot` of K-tile `kt_`: 0 dY planes 0-1, 1 X planes 0-1, 2 X planes 2-3, 3 dY planes 2-3
     auto issue_half = [&](int kt_, int slot) {
         unsigned char* dst = smem + (kt_ & 1) * P3_BUF + slot * P3_HALF + wave * 1024;
+        if constexpr (VW) {
+            // offset = walk pixel * pixel pitch + the lane's column part; the saturating add keeps either out-of-range mark
+            const uint32_t pix = valid_walk_pixel<true>(wt.w, wt.i0 + (uint32_t)kt_ * TP + (uint32_t)r);
+            const uint32_t none = pix == WALK_NONE ? OOB : 0u;      // OR-ed in: no branch around the multiplies
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                lds_ptr dp = (lds_ptr)(dst + i * PLANE);
+                if (slot == 0 || slot == 3) {
+                    const uint32_t pb = walk_mul<true>(pix, ystep) | none;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsy, dp, 16, __builtin_elementwise_add_sat(pb, yvoff[(slot == 0 ? 0 : 2) + i]), 0, 0, 0);
+                } else {
+                    const int pl = (slot == 1 ? 0 : 2) + i;
+                    const bool s1 = NSRC > 1 && xsrc[pl] != 0;
+                    const uint32_t pb = walk_mul<true>(pix, s1 ? x1step : x0step) | none;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(s1 ? rsx1 : rsx0, dp, 16, __builtin_elementwise_add_sat(pb, xvoff[pl]), 0, 0, 0);
+                }
+            }
+            return;
+        }
         const uint32_t mb = mb0 + (uint32_t)kt_ * TP;
         if (slot == 0 || slot == 3) {
             const uint32_t ysoff = mb * ystep;
@@ -760,7 +823,7 @@ __device__ __forceinline__ void p3w_wait_halves() {
     else asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
 }
 
-template <int NSRC, int LEAD>
+template <int NSRC, int LEAD, bool VW>
 __global__ __launch_bounds__(256, 1) void igemm_wgrad_p3w_kernel(const uclstm_wgrad_desc d, const WDerived dv, const P2 p2) {
 #if defined(__HIP_DEVICE_COMPILE__)
     static_assert(LEAD == 8 || LEAD == 9, "eight half-tile slots: a half is re-staged one (9) or two (8) phases after its reads");
@@ -780,18 +843,23 @@ __global__ __launch_bounds__(256, 1) void igemm_wgrad_p3w_kernel(const uclstm_wg
     int nt, kts;
     grouped_tile(rr, dv.n_nt, dv.n_kt, 4, nt, kts);
     int kt = kts;
-    if (dv.kt_per_tap > 0) {
+    if (!VW && dv.kt_per_tap > 0) {
         const int ntaps = d.ktap * d.ktap;
         const int cg = kts / ntaps;
         kt = (kts - cg * ntaps) * dv.kt_per_tap + cg;
+    }
+    WalkTile wt{};
+    if constexpr (VW) {
+        wt = walk_tile(d, dv, kts, sp);
+        kt = wt.kt;
     }
     const int n0 = nt * 256;
     const int kbase = kt * 256;
 
     const long m_begin = (long)sp * dv.chunk;
     const long m_end = min(dv.M, m_begin + dv.chunk);
-    const int KT = m_begin < dv.M ? (int)((m_end - m_begin) / TP) : 0;      // block-uniform
-    if (KT == 0) return;
+    const int KT = VW ? wt.KT : (m_begin < dv.M ? (int)((m_end - m_begin) / TP) : 0);      // block-uniform
+    if (KT == 0 && !(VW && d.slab > 0)) return;       // VW slabs: a range without rows of this tap still stores its tile of zeros
     const int total_halves = 4 * KT;
 
     const uclstm_seg G = d.seg[0];
@@ -809,6 +877,7 @@ __global__ __launch_bounds__(256, 1) void igemm_wgrad_p3w_kernel(const uclstm_wg
     const int cp = lane & 7;
     const int sc = 2 * ((cp >> 1) ^ ((lrow >> 1) & 3)) + (cp & 1);      // source 16-byte chunk stored at this position
     const int r = 8 * wave + lrow;                                       // pixel row (0..31) inside the row half
+    const int rv = VW ? 0 : r;                                           // VW: the row's pixel comes from the walk, per K-tile
     const int Wm = d.W - 1, Hm = d.H - 1;
     const int kseg = dv.kseg0 + dv.kseg1;
     uint32_t yvoff[4], xvoff[4], kxj[4], kyj[4];
@@ -817,7 +886,7 @@ __global__ __launch_bounds__(256, 1) void igemm_wgrad_p3w_kernel(const uclstm_wg
     for (int pl = 0; pl < 4; ++pl) {
         const int ny = n0 + pl * 64 + sc * 8;
         const bool yok = ny < d.N && ny >= G.n_begin && ny < G.n_end;
-        yvoff[pl] = yok ? (uint32_t)(2 * (r * G.C + G.c_off + (ny - G.n_begin))) : OOB;
+        yvoff[pl] = yok ? (uint32_t)(2 * (rv * G.C + G.c_off + (ny - G.n_begin))) : OOB;
         const int k0 = kbase + pl * 64;
         const int xtap = (int)fdiv((uint32_t)k0, dv.dPerTap);
         const int kr = k0 - xtap * kseg;
@@ -831,7 +900,7 @@ __global__ __launch_bounds__(256, 1) void igemm_wgrad_p3w_kernel(const uclstm_wg
         const int badx = ddx < 0 ? 0 : (ddx > 0 ? Wm : -1);
         const int bady = ddy < 0 ? 0 : (ddy > 0 ? Hm : -1);
         xsrc[pl] = xs_;
-        xvoff[pl] = xok ? (uint32_t)(2 * (r * S.C + (ddy * S.Ws + ddx) * S.C + xc) + (int)p2.xbias[xs_]) : OOB;
+        xvoff[pl] = xok ? (uint32_t)(2 * (rv * S.C + (ddy * S.Ws + ddx) * S.C + xc) + (int)p2.xbias[xs_]) : OOB;
         if (badx < 0) kxj[pl] = 0xffffffffu;
         else if (d.W >= 64) kxj[pl] = (uint32_t)(badx - r);
         else kxj[pl] = ((r & Wm) == badx) ? 0u : 0xffffffffu;
@@ -843,8 +912,72 @@ __global__ __launch_bounds__(256, 1) void igemm_wgrad_p3w_kernel(const uclstm_wg
     // half-tile in LDS slot `slot` of K-tile `kt_`: 0 dY planes 0-1, 1 X planes 0-1, 2 X planes 2-3, 3 dY planes 2-3
     // `valid` (wave-uniform) is false for halves past the end of the pixel range: they are issued all the same, out of range
     // (zero fill into a slot nobody reads any more), so that the loop has no branches and one vmcnt count holds in every phase
+    // VW: pixel-pitch multiples of the two walk entries (row halves) of the K-tile whose halves are being issued, per operand
+    // (OOB past the end of the block's range, which makes `valid` redundant).  The halves of K-tile T go out in four consecutive
+    // phases, slot 0 first: the walk of K-tile T runs in the phase before, in WALK_STEPS steps of a few instructions, one step
+    // after each of that phase's last MFMAs (no other wave shares the SIMD: whatever is not issued in the shadow of an MFMA
+    // lengthens the phase).  Step s of row half hh = step 7 hh + s; every step ends in its slow instruction (the multiply of a
+    // division is quarter rate) or hands one value to the next through an empty asm, which keeps the compiler from moving the
+    // arithmetic back in front of the phase's DMA issue.
+    constexpr int WALK_STEPS = 14;
+    uint32_t pby[2] = {OOB, OOB}, pbx0[2] = {OOB, OOB}, pbx1[2] = {OOB, OOB};
+    uint32_t wq[2] = {0, 0}, wimg[2] = {0, 0}, wj[2] = {0, 0}, wpix[2] = {0, 0};
+    auto walk_step = [&](int kt_, int step) {
+        const int hh = step / 7, st = step - 7 * hh;
+        const ValidWalk& w = wt.w;
+        const uint32_t i = wt.i0 + (uint32_t)kt_ * TP + 32u * hh + (uint32_t)r;
+        if (st == 0) {
+            wq[hh] = walk_div_hi(i, w.dNv);
+            asm volatile("" : "+v"(wq[hh]));
+        } else if (st == 1) {
+            wimg[hh] = wq[hh] >> w.dNv.shift;
+            wj[hh] = walk_in_image<true>(w, i, wimg[hh]);
+            asm volatile("" : "+v"(wj[hh]));
+        } else if (st == 2) {
+            wq[hh] = walk_div_hi(wj[hh], w.dWv);
+            asm volatile("" : "+v"(wq[hh]));
+        } else if (st == 3) {
+            const uint32_t yy = wq[hh] >> w.dWv.shift;
+            wpix[hh] = walk_compose<true>(w, i, wimg[hh], yy, walk_in_row<true>(w, wj[hh], yy));
+            asm volatile("" : "+v"(wpix[hh]));
+        } else {
+            const uint32_t none = wpix[hh] == WALK_NONE ? OOB : 0u;      // OR-ed in: no branch around the multiply
+            if (st == 4) {
+                pby[hh] = walk_mul<true>(wpix[hh], ystep) | none;
+                asm volatile("" : "+v"(pby[hh]));
+            } else if (st == 5) {
+                pbx0[hh] = walk_mul<true>(wpix[hh], x0step) | none;
+                asm volatile("" : "+v"(pbx0[hh]));
+            } else if (NSRC > 1) {
+                pbx1[hh] = walk_mul<true>(wpix[hh], x1step) | none;
+                asm volatile("" : "+v"(pbx1[hh]));
+            }
+        }
+    };
+    auto walk_ktile = [&](int kt_) {
+#pragma unroll
+        for (int step = 0; step < WALK_STEPS; ++step) walk_step(kt_, step);
+    };
     auto issue_half = [&](int kt_, int slot, bool valid) {
         unsigned char* dst = smem + (kt_ & 1) * P3_BUF + slot * P3_HALF + wave * 1024;
+        if constexpr (VW) {
+            // offset = walk pixel * pixel pitch + the lane's column part; the saturating add keeps either out-of-range mark
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    lds_ptr dp = (lds_ptr)(dst + i * PLANE + hh * 4096);
+                    if (slot == 0 || slot == 3) {
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsy, dp, 16, __builtin_elementwise_add_sat(pby[hh], yvoff[(slot == 0 ? 0 : 2) + i]), 0, 0, 0);
+                    } else {
+                        const int pl = (slot == 1 ? 0 : 2) + i;
+                        const bool s1 = NSRC > 1 && xsrc[pl] != 0;          // wave-uniform: a select, not a branch
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(s1 ? rsx1 : rsx0, dp, 16, __builtin_elementwise_add_sat(s1 ? pbx1[hh] : pbx0[hh], xvoff[pl]),
+                                                                 0, 0, 0);
+                    }
+                }
+            return;
+        }
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
             const uint32_t mb = mb0 + (uint32_t)kt_ * TP + 32u * hh;
@@ -909,7 +1042,11 @@ __global__ __launch_bounds__(256, 1) void igemm_wgrad_p3w_kernel(const uclstm_wg
     // prologue: all eight slots issued, halves 0-2 landed, halves 0 and 1 read (they belong to "phases -2 and -1") and those
     // reads retired by every wave before anything is staged over them (half 8 here with LEAD 9, else in phase 0)
 #pragma unroll
-    for (int q = 0; q < 8; ++q) issue_half(q >> 2, q & 3, q < total_halves);
+    for (int q = 0; q < 8; ++q) {
+        if (VW && (q & 3) == 0) walk_ktile(q >> 2);
+        issue_half(q >> 2, q & 3, q < total_halves);
+    }
+    if constexpr (VW) walk_ktile(2);
     p3w_wait_halves<5>();
     __builtin_amdgcn_s_barrier();
     read_half(0, 0, 0);
@@ -936,20 +1073,43 @@ __global__ __launch_bounds__(256, 1) void igemm_wgrad_p3w_kernel(const uclstm_wg
             // half g + 2 (past the end: a stale slot, never used)
             if (q < 2) read_half(par, q + 2, 1);
             else read_half(par ^ 1, q - 2, 2);
+            // VW: the phase before slot 0 of K-tile kt_ + 3 goes out walks that K-tile (a constant once the phases are unrolled)
+            const bool walk_phase = VW && q == (LEAD == 9 ? 2 : 3);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
+            for (int ks = 0; ks < 2; ++ks) {
+                if (walk_phase && ks == 1) {
+                    // the second sixteen MFMAs (same order as below), a walk step after each: regions of their own
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            acc[mh][i][nh][j] = UCLSTM_MFMA_16x16x32(af[mh][i][ks], bfr[nh][j][ks], acc[mh][i][nh][j], 0, 0, 0);
+                            if (4 * i + j < WALK_STEPS) walk_step(kt_ + 3, 4 * i + j);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    break;
+                }
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         acc[mh][i][nh][j] = UCLSTM_MFMA_16x16x32(af[mh][i][ks], bfr[nh][j][ks], acc[mh][i][nh][j], 0, 0, 0);
-            // the 16 fragment reads go out between the first MFMAs, so that they have retired long before the barrier
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
-            __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
+            // the 16 fragment reads go out between the first MFMAs, so that they have retired long before the barrier
+            if (!walk_phase) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                }
+                __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
+            }
             __builtin_amdgcn_sched_barrier(0);
             // half g + 3 has landed: halves g + 4 .. g + LEAD of this wave stay in flight
             p3w_wait_halves<LEAD - 3>();
@@ -1001,7 +1161,11 @@ __global__ __launch_bounds__(256, 1) void igemm_wgrad_p3w_kernel(const uclstm_wg
 //    but little interference -- few slabs and a grid that does not have to cover every CU (a 128-KiB block excludes every
 //    64-KiB GEMM block from its CU).  Same-box sweeps of the STEP time: the stand-alone plan gave 16.49 k frames/s, 0.35x its
 //    split counts 16.74 k.  Rule: the fewest splits that still give UCLSTM_P3_MIN_BLOCKS (default 128) blocks.
-int auto_splits256(int64_t tiles, int64_t stages, bool slabs, int64_t panel_elems, bool overlapped) {
+// tap_stages (valid-pixel walk, else null): the 64-row K-tiles of each of the nine taps.  A block of tap t then runs
+// ceil(tap_stages[t] / used) stages instead of `per`; the nine taps alternate in block order, so every round of 256 blocks holds
+// them in equal shares and a CU that drew a short tile starts on the next round early: a round is priced at the MEAN block.
+// The overlapped rule counts blocks, not stages, and stays as it is (the longest block, the centre tap's, is the dense one).
+int auto_splits256(int64_t tiles, int64_t stages, bool slabs, int64_t panel_elems, bool overlapped, const int64_t* tap_stages) {
     const int64_t smax = stages / 8 > 1 ? stages / 8 : 1;
     if (overlapped) {
         static const int min_blocks = [] { const char* e = getenv("UCLSTM_P3_MIN_BLOCKS"); return e ? atoi(e) : 128; }();
@@ -1017,7 +1181,12 @@ int auto_splits256(int64_t tiles, int64_t stages, bool slabs, int64_t panel_elem
         const int64_t per = (stages + s - 1) / s;
         const int64_t used = (stages + per - 1) / per;
         const int64_t rounds = (tiles * used + 255) / 256;
-        const int64_t cost = rounds * (per + fixed) + (int64_t)(slab_cost * (double)used);
+        int64_t cost = rounds * (per + fixed) + (int64_t)(slab_cost * (double)used);
+        if (tap_stages) {
+            int64_t sum = 0;
+            for (int t = 0; t < 9; ++t) sum += (tap_stages[t] + used - 1) / used;
+            cost = (int64_t)((double)rounds * ((double)sum / 9.0 + (double)fixed) + slab_cost * (double)used);
+        }
         if (best_cost < 0 || cost < best_cost) {
             best_cost = cost;
             best = (int)s;
@@ -1380,10 +1549,25 @@ int32_t wgrad_run(const uclstm_wgrad_desc* dp, void* stream, int query) {
     dv.n_kt = (d.Ktot + tc - 1) / tc;
     dv.n_nt = (d.N + tn - 1) / tn;
     dv.kt_per_tap = (fast && ((dv.kseg0 + dv.kseg1) % tc) == 0) ? (dv.kseg0 + dv.kseg1) / tc : 0;
+    // valid-pixel walk: 256 x 256 launches whose tiles all belong to one tap of a 3x3 / pad 1 gradient (UCLSTM_WGRAD_VALID=0: dense)
+    static const bool no_vw = [] { const char* e = getenv("UCLSTM_WGRAD_VALID"); return e && e[0] == '0'; }();
+    const bool vw = big && !no_vw && dv.kt_per_tap > 0 && d.ktap == 3 && d.pad == 1 && dv.M < ((long)1 << 24) - 4096;      // SMALL walks
+    for (int iy = 0; iy < 2; ++iy)
+        for (int ix = 0; ix < 2; ++ix) {
+            const int hv = d.H - iy > 0 ? d.H - iy : 0, wv = d.W - ix > 0 ? d.W - ix : 0;
+            dv.dWv[ix] = make_walkdiv((uint32_t)wv);
+            dv.dNv[iy][ix] = make_walkdiv((uint32_t)(hv * wv));
+        }
     uclstm_wgrad_desc dd = d;
     const bool slabs = d.slab > 0;
+    int64_t tap_stages[9];
+    for (int t = 0; t < 9; ++t) {
+        const int hv = d.H - (t / 3 != 1) > 0 ? d.H - (t / 3 != 1) : 0, wv = d.W - (t % 3 != 1) > 0 ? d.W - (t % 3 != 1) : 0;
+        tap_stages[t] = ((int64_t)d.n_img * hv * wv + TP - 1) / TP;
+    }
     if (dd.splits <= 0)
-        dd.splits = big ? auto_splits256((int64_t)dv.n_kt * dv.n_nt, (dv.M + TP - 1) / TP, slabs, (int64_t)d.N * d.Ktot, d.overlapped != 0)
+        dd.splits = big ? auto_splits256((int64_t)dv.n_kt * dv.n_nt, (dv.M + TP - 1) / TP, slabs, (int64_t)d.N * d.Ktot, d.overlapped != 0,
+                                         vw ? tap_stages : nullptr)
                         : auto_splits((int64_t)dv.n_kt * dv.n_nt, (dv.M + TP - 1) / TP, slabs, (int64_t)d.N * d.Ktot);
     long chunk = (dv.M + dd.splits - 1) / dd.splits;
     chunk = (chunk + TP - 1) / TP * TP;
@@ -1396,42 +1580,38 @@ int32_t wgrad_run(const uclstm_wgrad_desc* dp, void* stream, int query) {
     hipStream_t st = (hipStream_t)stream;
 
     if (big) {
-        static bool attr3 = false;
         // seven half-tiles ahead (five in flight across a barrier) is the default: +11 % on the 4096 x 18432 gradient over six
         // (same box A/B); UCLSTM_P3_LEAD=6 selects the shallower ring
         static const bool lead7 = [] { const char* e = getenv("UCLSTM_P3_LEAD"); return !(e && e[0] == '6'); }();
-        if (!attr3) {
-            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3_kernel<1, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
-            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3_kernel<2, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
-            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3_kernel<1, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
-            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3_kernel<2, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
-            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3w_kernel<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
-            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3w_kernel<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
-            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3w_kernel<1, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
-            (void)hipFuncSetAttribute((const void*)igemm_wgrad_p3w_kernel<2, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
-            attr3 = true;
-        }
         // four waves x 128 x 128 is the default; UCLSTM_P3_WAVES=8 selects the 8-wave kernel (same tile, same plan, bit-identical
         // slabs).  The deeper DMA ring of either kernel is its default, UCLSTM_P3_LEAD=6 the shallower one (8 of the 4-wave kernel)
         static const bool waves8 = [] { const char* e = getenv("UCLSTM_P3_WAVES"); return e && e[0] == '8'; }();
-        if (!waves8) {
-            if (lead7) {
-                if (d.nsrc == 1) UCLSTM_LAUNCH((igemm_wgrad_p3w_kernel<1, 9>), dim3((unsigned)nblk), dim3(256), P3_SMEM, st, dd, dv, p2);
-                else UCLSTM_LAUNCH((igemm_wgrad_p3w_kernel<2, 9>), dim3((unsigned)nblk), dim3(256), P3_SMEM, st, dd, dv, p2);
-            } else {
-                if (d.nsrc == 1) UCLSTM_LAUNCH((igemm_wgrad_p3w_kernel<1, 8>), dim3((unsigned)nblk), dim3(256), P3_SMEM, st, dd, dv, p2);
-                else UCLSTM_LAUNCH((igemm_wgrad_p3w_kernel<2, 8>), dim3((unsigned)nblk), dim3(256), P3_SMEM, st, dd, dv, p2);
-            }
-            return UCLSTM_OK;
-        }
-        if (lead7) {
-            if (d.nsrc == 1) UCLSTM_LAUNCH((igemm_wgrad_p3_kernel<1, 7>), dim3((unsigned)nblk), dim3(512), P3_SMEM, st, dd, dv, p2);
-            else UCLSTM_LAUNCH((igemm_wgrad_p3_kernel<2, 7>), dim3((unsigned)nblk), dim3(512), P3_SMEM, st, dd, dv, p2);
-        } else {
-            if (d.nsrc == 1) UCLSTM_LAUNCH((igemm_wgrad_p3_kernel<1, 6>), dim3((unsigned)nblk), dim3(512), P3_SMEM, st, dd, dv, p2);
-            else UCLSTM_LAUNCH((igemm_wgrad_p3_kernel<2, 6>), dim3((unsigned)nblk), dim3(512), P3_SMEM, st, dd, dv, p2);
-        }
-        return UCLSTM_OK;
+        const dim3 grid((unsigned)nblk);
+#define P3_GO(KERNEL, THREADS)                                                                                              \
+    {                                                                                                                       \
+        static bool attr_ = false;                                                                                          \
+        if (!attr_) {                                                                                                       \
+            (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);            \
+            attr_ = true;                                                                                                   \
+        }                                                                                                                   \
+        UCLSTM_LAUNCH((KERNEL), grid, dim3(THREADS), P3_SMEM, st, dd, dv, p2);                                               \
+        return UCLSTM_OK;                                                                                                   \
+    }
+#define P3_PICK(NAME, DEEP, SHALLOW, THREADS)                                                                               \
+    {                                                                                                                       \
+        if (lead7 && d.nsrc == 1 && vw) P3_GO((NAME<1, DEEP, true>), THREADS)                                                \
+        if (lead7 && d.nsrc == 1) P3_GO((NAME<1, DEEP, false>), THREADS)                                                     \
+        if (lead7 && vw) P3_GO((NAME<2, DEEP, true>), THREADS)                                                               \
+        if (lead7) P3_GO((NAME<2, DEEP, false>), THREADS)                                                                    \
+        if (d.nsrc == 1 && vw) P3_GO((NAME<1, SHALLOW, true>), THREADS)                                                      \
+        if (d.nsrc == 1) P3_GO((NAME<1, SHALLOW, false>), THREADS)                                                           \
+        if (vw) P3_GO((NAME<2, SHALLOW, true>), THREADS)                                                                     \
+        P3_GO((NAME<2, SHALLOW, false>), THREADS)                                                                            \
+    }
+        if (!waves8) P3_PICK(igemm_wgrad_p3w_kernel, 9, 8, 256)
+        P3_PICK(igemm_wgrad_p3_kernel, 7, 6, 512)
+#undef P3_PICK
+#undef P3_GO
     }
     if (fast) {
         if (wn == 1) return d.nsrc == 1 ? launch_p2<1, 1>(dd, dv, p2, nblk, st) : launch_p2<1, 2>(dd, dv, p2, nblk, st);
@@ -1459,4 +1639,22 @@ extern "C" int32_t uclstm_igemm_wgrad_splits(const uclstm_wgrad_desc* d) { retur
 #endif
 #ifndef UCLSTM_ACT_F16
 extern "C" int32_t uclstm_igemm_wgrad_shape(const uclstm_wgrad_desc* d) { return wgrad_run(d, nullptr, 2); }
+#endif
+#ifndef UCLSTM_ACT_F16
+extern "C" int64_t uclstm_igemm_wgrad_walk(const uclstm_wgrad_desc* d, int32_t tap, int64_t i0, int32_t n, int32_t* pixels) {
+    if (!d || d->n_img <= 0 || d->H <= 0 || d->W <= 0 || d->ktap < 1 || d->ktap > 7 || d->pad < 0 || d->pad > 3) return UCLSTM_E_BADARG;
+    if (tap < 0 || tap >= d->ktap * d->ktap || i0 < 0 || n < 0 || (n > 0 && !pixels)) return UCLSTM_E_BADARG;
+    if ((int64_t)d->n_img * d->H * d->W >= ((int64_t)1 << 31) - 4096 || i0 + n >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    const int ty = tap / d->ktap;
+    const int ddy = ty - d->pad, ddx = tap - ty * d->ktap - d->pad;
+    const int ay = ddy < 0 ? -ddy : ddy, ax = ddx < 0 ? -ddx : ddx;
+    const int hv = d->H > ay ? d->H - ay : 0, wv = d->W > ax ? d->W - ax : 0;
+    const ValidWalk w = make_valid_walk(d->n_img, d->H, d->W, ddy, ddx, make_walkdiv((uint32_t)(hv * wv)), make_walkdiv((uint32_t)wv));
+    const bool small = valid_walk_small(w, d->n_img);      // what the kernels run
+    for (int32_t k = 0; k < n; ++k) {
+        const uint32_t p = small ? valid_walk_pixel<true>(w, (uint32_t)(i0 + k)) : valid_walk_pixel<false>(w, (uint32_t)(i0 + k));
+        pixels[k] = p == WALK_NONE ? -1 : (int32_t)p;
+    }
+    return (int64_t)w.total;
+}
 #endif
