@@ -548,9 +548,28 @@ int32_t uclstm_loss_spec_fwd_ordered_bc(const uclstm_loss_spec* spec, const floa
                                         int32_t mask_div, void* stream);
 int32_t uclstm_loss_spec_bwd_bc(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
                                 const float* coefs, float* grad, int64_t planes, int32_t H, int32_t W, int32_t mask_div, void* stream);
+/* The same three with a WEIGHT PER PLANE (loss.WeightedLossSpec: per-frame and per-channel weights).  plane_w is a DEVICE
+ * f32[period]; plane p of y_pred / y / grad has the weight q = plane_w[p % period] (for y [B,T,Cy,H,W]: period = T*Cy and
+ * plane_w[t*Cy + c] = frame weight t x channel weight c).  Every term of the four sums carries it,
+ *   sums = sum(rho*w*m*q), sum(w*m*q), sum(gd*mc*q), sum(mc*q),
+ * one more f32 multiplication per term, and since every neighbour of the gradient term lies in the element's own plane
+ *   grad = q * (coefs[0] * rho'(d) * w * m + coefs[1] * d(sum gd*mc)/dy_pred).
+ * mask_div as for the _bc entry points; 1 = a mask plane per plane, or no mask (mask may be NULL only then).  Same grids and the
+ * same partition of the elements as the plain entry points: a table of ones returns their bits (ordered form and bwd).
+ * UCLSTM_E_BADARG as above (but for the NULL mask at mask_div == 1), and for a NULL plane_w, period < 1, planes % period != 0 or a
+ * NULL mask with mask_div > 1.  f32 planes only: no _f16 twin. */
+int32_t uclstm_loss_spec_fwd_pw(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                const float* plane_w, int32_t period, double* sums, int64_t planes, int32_t H, int32_t W,
+                                int32_t mask_div, void* stream);
+int32_t uclstm_loss_spec_fwd_ordered_pw(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                        const float* plane_w, int32_t period, double* partials, double* sums, int32_t accumulate,
+                                        int64_t planes, int32_t H, int32_t W, int32_t mask_div, void* stream);
+int32_t uclstm_loss_spec_bwd_pw(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                const float* plane_w, int32_t period, const float* coefs, float* grad, int64_t planes, int32_t H,
+                                int32_t W, int32_t mask_div, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
-/* Optimiser (main.py:106-108): global-norm clip + AdamW on flat f32 buffers            */
+/* Optimiser(main.py:106-108): global-norm clip + AdamW on flat f32 buffers            */
 /* ------------------------------------------------------------------------------------ */
 int32_t uclstm_sumsq(const float* g, int64_t n, double* out /* accumulates, caller zeroes */, void* stream);
 /* Ordered form (deterministic mode): partials f64 [uclstm_sumsq_ordered_rows] (1 .. 1024 rows, a function of n alone), one stored

@@ -233,6 +233,9 @@ _PROTOS = {
     "uclstm_loss_spec_fwd_bc": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _L, _I, _I, _I, _P],
     "uclstm_loss_spec_fwd_ordered_bc": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _P],
     "uclstm_loss_spec_bwd_bc": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _P, _L, _I, _I, _I, _P],
+    "uclstm_loss_spec_fwd_pw": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _I, _P, _L, _I, _I, _I, _P],
+    "uclstm_loss_spec_fwd_ordered_pw": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _I, _P, _P, _I, _L, _I, _I, _I, _P],
+    "uclstm_loss_spec_bwd_pw": [C.POINTER(LossSpecDesc), _P, _P, _P, _P, _I, _P, _P, _L, _I, _I, _I, _P],
     "uclstm_sumsq": [_P, _L, _P, _P],
     "uclstm_sumsq_ordered_rows": [_L],
     "uclstm_sumsq_ordered": [_P, _L, _P, _P, _I, _P],

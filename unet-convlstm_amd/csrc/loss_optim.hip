@@ -788,6 +788,7 @@ extern "C" int32_t uclstm_ordered_sum_f64(const double* partials, int32_t rows, 
 // host picks the instance, so no element branches on the spec.  Without the gradient term the planes are one flat array.
 namespace {
 
+enum { PW_OFF = 0, PW_MASK = 1, PW_NO_MASK = 2 };   // plane weights: none / with a mask / with mask == NULL
 constexpr int SPEC_GRID_CAP_V4 = 512;           // blocks of the V = 4 instances (fwd atomic form and bwd): 16 bytes per stream and thread
 
 template <int V>
@@ -847,29 +848,66 @@ __device__ __forceinline__ const float* load_mask_bc(const float* __restrict__ m
     return mk;
 }
 
+// The plane weights of the V elements at idx (the _pw entry points): plane p has weight plane_w[p mod period], dPer divides by the
+// period.  One plane per group under the conditions of load_mask_bc, otherwise every element finds its own plane.
+template <int V, bool GRAD>
+__device__ __forceinline__ void load_plane_w(const float* __restrict__ plane_w, int64_t idx, const FastDiv& dPl, const FastDiv& dPer,
+                                             float (&q)[V]) {
+    if (GRAD || V == 1 || dPl.d % V == 0) {
+        const uint32_t pl = fdiv((uint32_t)idx, dPl);
+        const float w = plane_w[pl - fdiv(pl, dPer) * dPer.d];
+#pragma unroll
+        for (int u = 0; u < V; ++u) q[u] = w;
+    } else {
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+            const uint32_t pl = fdiv((uint32_t)(idx + u), dPl);
+            q[u] = plane_w[pl - fdiv(pl, dPer) * dPer.d];
+        }
+    }
+}
+
 // items = total / V groups of V elements of one row; dHW / dW divide by the groups of a plane / of a row (GRAD only).
 // sums as loss_fwd_kernel; without GRAD columns 2 and 3 are the zeros acc starts with.
-template <int POINT, int POWER, bool GRAD, bool ORDERED, int V, bool BC = false>
+// PW (the _pw entry points, always with BC): every term of the four sums is multiplied by the weight of its plane,
+// plane_w[plane mod dPer.d].  mask may be NULL there, which is an instance of its own (PW_NO_MASK): a mask load under a run-time
+// branch makes the loads issued before it wait at the join.  Without PW neither plane_w nor dPer is read.
+template <int POINT, int POWER, bool GRAD, bool ORDERED, int V, bool BC = false, int PW = PW_OFF>
 __global__ void loss_spec_fwd_kernel(const float* __restrict__ yp, const float* __restrict__ y, const float* __restrict__ mask,
                                      double* __restrict__ sums, int64_t items, FastDiv dHW, FastDiv dW, int H, int W, float delta,
-                                     float gain, FastDiv dPl, FastDiv dMd) {
+                                     float gain, FastDiv dPl, FastDiv dMd, const float* __restrict__ plane_w, FastDiv dPer) {
     __shared__ double red[16];
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    // PW_NO_MASK: a one the compiler does not see (mask is NULL), so that the multiplications by m stay, and with them the
+    // contractions, and the bits, of the plain instances under a NULL mask
+    [[maybe_unused]] const float no_mask = mask ? 0.f : 1.f;
     for (int64_t it = (int64_t)blockIdx.x * NT + threadIdx.x; it < items; it += (int64_t)gridDim.x * NT) {
         const int64_t idx = it * V;
         float a[V], b[V], m[V];
+        [[maybe_unused]] float q[V];
+        if constexpr (PW != PW_OFF) load_plane_w<V, GRAD>(plane_w, idx, dPl, dPer, q);     // issued with the loads of the planes, not after them
         load_v<V>(yp + idx, a);
         load_v<V>(y + idx, b);
-        if constexpr (BC) load_mask_bc<V, GRAD>(mask, idx, dPl, dMd, m);
-        else if (mask) load_v<V>(mask + idx, m);
+        if constexpr (BC && PW != PW_NO_MASK) load_mask_bc<V, GRAD>(mask, idx, dPl, dMd, m);
+        else if (!BC && mask) load_v<V>(mask + idx, m);
         else
 #pragma unroll
-            for (int u = 0; u < V; ++u) m[u] = 1.f;
+            for (int u = 0; u < V; ++u) m[u] = PW == PW_NO_MASK ? no_mask : 1.f;
+        if constexpr (PW != PW_OFF) {
 #pragma unroll
-        for (int u = 0; u < V; ++u) {
-            const float w = spec_weight<POWER>(b[u], gain);
-            acc[0] += (double)(spec_rho<POINT>(a[u] - b[u], delta) * w * m[u]);
-            acc[1] += (double)(w * m[u]);
+            for (int u = 0; u < V; ++u) {
+                const float w = spec_weight<POWER>(b[u], gain);
+                acc[0] += (double)(spec_rho<POINT>(a[u] - b[u], delta) * w * m[u] * q[u]);
+                acc[1] += (double)(w * m[u] * q[u]);
+                m[u] *= q[u];                                    // the gradient term below sums gd * (mc * q) and mc * q
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < V; ++u) {
+                const float w = spec_weight<POWER>(b[u], gain);
+                acc[0] += (double)(spec_rho<POINT>(a[u] - b[u], delta) * w * m[u]);
+                acc[1] += (double)(w * m[u]);
+            }
         }
         if constexpr (GRAD) {
             const uint32_t pl = fdiv((uint32_t)it, dHW);
@@ -905,24 +943,32 @@ __global__ void loss_spec_fwd_kernel(const float* __restrict__ yp, const float* 
     }
 }
 
-template <int POINT, int POWER, bool GRAD, int V, bool BC = false>
+// PW as in the forward kernel: every neighbour of the gradient term lies in the element's own plane, so the weighted gradient is the
+// plain one times the weight of the plane.
+template <int POINT, int POWER, bool GRAD, int V, bool BC = false, int PW = PW_OFF>
 __global__ void loss_spec_bwd_kernel(const float* __restrict__ yp, const float* __restrict__ y, const float* __restrict__ mask,
                                      const float* __restrict__ coefs, float* __restrict__ grad, int64_t items, FastDiv dHW, FastDiv dW,
-                                     int H, int W, float delta, float gain, FastDiv dPl, FastDiv dMd) {
+                                     int H, int W, float delta, float gain, FastDiv dPl, FastDiv dMd, const float* __restrict__ plane_w,
+                                     FastDiv dPer) {
     const float c1 = coefs[0];
     float c2 = 0.f;
     if constexpr (GRAD) c2 = coefs[1];
+    // PW_NO_MASK: a one the compiler does not see (mask is NULL), so that the multiplications by m stay, and with them the
+    // contractions, and the bits, of the plain instances under a NULL mask
+    [[maybe_unused]] const float no_mask = mask ? 0.f : 1.f;
     for (int64_t it = (int64_t)blockIdx.x * NT + threadIdx.x; it < items; it += (int64_t)gridDim.x * NT) {
         const int64_t idx = it * V;
         float a[V], b[V], m[V], g[V];
+        [[maybe_unused]] float q[V];
+        if constexpr (PW != PW_OFF) load_plane_w<V, GRAD>(plane_w, idx, dPl, dPer, q);     // issued with the loads of the planes, not after them
         load_v<V>(yp + idx, a);
         load_v<V>(y + idx, b);
         const float* mk = mask;                                  // BC: shifted so that mk + idx is the mask of this plane
-        if constexpr (BC) mk = load_mask_bc<V, GRAD>(mask, idx, dPl, dMd, m);
-        else if (mask) load_v<V>(mask + idx, m);
+        if constexpr (BC && PW != PW_NO_MASK) mk = load_mask_bc<V, GRAD>(mask, idx, dPl, dMd, m);
+        else if (!BC && mask) load_v<V>(mask + idx, m);
         else
 #pragma unroll
-            for (int u = 0; u < V; ++u) m[u] = 1.f;
+            for (int u = 0; u < V; ++u) m[u] = PW == PW_NO_MASK ? no_mask : 1.f;
 #pragma unroll
         for (int u = 0; u < V; ++u) g[u] = c1 * spec_drho<POINT>(a[u] - b[u], delta) * spec_weight<POWER>(b[u], gain) * m[u];
         if constexpr (GRAD) {
@@ -978,6 +1024,9 @@ __global__ void loss_spec_bwd_kernel(const float* __restrict__ yp, const float* 
 #pragma unroll
             for (int u = 0; u < V; ++u) g[u] += c2 * gg[u];
         }
+        if constexpr (PW != PW_OFF)
+#pragma unroll
+            for (int u = 0; u < V; ++u) g[u] *= q[u];
         if constexpr (V == 4) *(float4*)(grad + idx) = make_float4(g[0], g[1], g[2], g[3]);
         else grad[idx] = g[0];
     }
@@ -1019,18 +1068,44 @@ bool loss_spec_vec(const uclstm_loss_spec* s, int64_t total, int W, const void* 
 }
 
 // BC: the mask is broadcast over channels, plane p reads mask plane p / mask_div (the _bc entry points); the grids, and so the
-// partition of the elements over blocks and threads, are those of the plain form.
-template <bool ORDERED, bool BC = false>
+// partition of the elements over blocks and threads, are those of the plain form.  PW: a weight per plane, plane_w[plane mod period]
+// (the _pw entry points, on the broadcast-mask indexing whatever mask_div is); the same grids again.
+template <bool ORDERED, bool BC = false, bool PW = false>
 int32_t loss_spec_fwd_launch(const uclstm_loss_spec* s, const float* y_pred, const float* y, const float* mask, double* out, int64_t total,
-                             int H, int W, int rows, hipStream_t stream, int mask_div = 1) {
+                             int H, int W, int rows, hipStream_t stream, int mask_div = 1, const float* plane_w = nullptr,
+                             int period = 1) {
     const bool vec = loss_spec_vec(s, total, W, y_pred, y, mask, nullptr);
     return loss_spec_dispatch(s, vec, [&](auto point, auto power, auto grad, auto v) -> int32_t {
         constexpr int V = decltype(v)::value;
         const int grid = ORDERED ? rows : grid_for(total / V, V == 4 ? SPEC_GRID_CAP_V4 : 1024);
-        UCLSTM_LAUNCH((loss_spec_fwd_kernel<decltype(point)::value, decltype(power)::value, decltype(grad)::value, ORDERED, V, BC>),
-                      dim3(grid), dim3(NT), 0, stream, y_pred, y, mask, out, total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H, W,
-                      s->delta, s->weight_gain, make_fastdiv(H * W), make_fastdiv(mask_div));
-        return UCLSTM_OK;
+        auto launch = [&](auto pw) -> int32_t {
+            UCLSTM_LAUNCH((loss_spec_fwd_kernel<decltype(point)::value, decltype(power)::value, decltype(grad)::value, ORDERED, V, BC,
+                                                decltype(pw)::value>),
+                          dim3(grid), dim3(NT), 0, stream, y_pred, y, mask, out, total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H,
+                          W, s->delta, s->weight_gain, make_fastdiv(H * W), make_fastdiv(mask_div), plane_w, make_fastdiv(period));
+            return UCLSTM_OK;
+        };
+        if constexpr (!PW) return launch(ic<int, PW_OFF>{});
+        else return mask ? launch(ic<int, PW_MASK>{}) : launch(ic<int, PW_NO_MASK>{});
+    });
+}
+
+template <bool BC = false, bool PW = false>
+int32_t loss_spec_bwd_launch(const uclstm_loss_spec* s, const float* y_pred, const float* y, const float* mask, const float* coefs,
+                             float* grad, int64_t total, int H, int W, hipStream_t stream, int mask_div = 1,
+                             const float* plane_w = nullptr, int period = 1) {
+    const bool vec = loss_spec_vec(s, total, W, y_pred, y, mask, grad);
+    return loss_spec_dispatch(s, vec, [&](auto point, auto power, auto grd, auto v) -> int32_t {
+        constexpr int V = decltype(v)::value;
+        auto launch = [&](auto pw) -> int32_t {
+            UCLSTM_LAUNCH((loss_spec_bwd_kernel<decltype(point)::value, decltype(power)::value, decltype(grd)::value, V, BC, decltype(pw)::value>),
+                          dim3(grid_for(total / V, V == 4 ? SPEC_GRID_CAP_V4 : 2048)), dim3(NT), 0, stream, y_pred, y, mask, coefs, grad,
+                          total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H, W, s->delta, s->weight_gain, make_fastdiv(H * W),
+                          make_fastdiv(mask_div), plane_w, make_fastdiv(period));
+            return UCLSTM_OK;
+        };
+        if constexpr (!PW) return launch(ic<int, PW_OFF>{});
+        else return mask ? launch(ic<int, PW_MASK>{}) : launch(ic<int, PW_NO_MASK>{});
     });
 }
 
@@ -1062,15 +1137,7 @@ extern "C" int32_t uclstm_loss_spec_bwd(const uclstm_loss_spec* spec, const floa
     if (!loss_spec_ok(spec) || !y_pred || !y || !grad || !coefs || planes <= 0 || H <= 0 || W <= 0) return UCLSTM_E_BADARG;
     const int64_t total = planes * H * W;
     if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
-    const bool vec = loss_spec_vec(spec, total, W, y_pred, y, mask, grad);
-    return loss_spec_dispatch(spec, vec, [&](auto point, auto power, auto grd, auto v) -> int32_t {
-        constexpr int V = decltype(v)::value;
-        UCLSTM_LAUNCH((loss_spec_bwd_kernel<decltype(point)::value, decltype(power)::value, decltype(grd)::value, V>),
-                      dim3(grid_for(total / V, V == 4 ? SPEC_GRID_CAP_V4 : 2048)), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, coefs,
-                      grad, total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H, W, spec->delta, spec->weight_gain,
-                      make_fastdiv(H * W), make_fastdiv(1));
-        return UCLSTM_OK;
-    });
+    return loss_spec_bwd_launch(spec, y_pred, y, mask, coefs, grad, total, H, W, (hipStream_t)stream);
 }
 
 // ---- the same three with the mask broadcast over channels: plane p reads mask plane p / mask_div ----
@@ -1103,15 +1170,51 @@ extern "C" int32_t uclstm_loss_spec_bwd_bc(const uclstm_loss_spec* spec, const f
         return UCLSTM_E_BADARG;
     const int64_t total = planes * H * W;
     if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
-    const bool vec = loss_spec_vec(spec, total, W, y_pred, y, mask, grad);
-    return loss_spec_dispatch(spec, vec, [&](auto point, auto power, auto grd, auto v) -> int32_t {
-        constexpr int V = decltype(v)::value;
-        UCLSTM_LAUNCH((loss_spec_bwd_kernel<decltype(point)::value, decltype(power)::value, decltype(grd)::value, V, true>),
-                      dim3(grid_for(total / V, V == 4 ? SPEC_GRID_CAP_V4 : 2048)), dim3(NT), 0, (hipStream_t)stream, y_pred, y, mask, coefs,
-                      grad, total / V, make_fastdiv(H * (W / V)), make_fastdiv(W / V), H, W, spec->delta, spec->weight_gain,
-                      make_fastdiv(H * W), make_fastdiv(mask_div));
-        return UCLSTM_OK;
-    });
+    return loss_spec_bwd_launch<true>(spec, y_pred, y, mask, coefs, grad, total, H, W, (hipStream_t)stream, mask_div);
+}
+
+// ---- the same three with a weight per plane: plane p counts plane_w[p mod period] times in each of the four sums ----
+namespace {
+bool loss_pw_ok(const float* mask, const float* plane_w, int32_t period, int64_t planes, int32_t mask_div) {
+    return plane_w && period >= 1 && planes > 0 && planes % period == 0 && mask_div >= 1 && (mask || mask_div == 1);
+}
+}  // namespace
+
+extern "C" int32_t uclstm_loss_spec_fwd_pw(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                           const float* plane_w, int32_t period, double* sums, int64_t planes, int32_t H, int32_t W,
+                                           int32_t mask_div, void* stream) {
+    if (!loss_spec_ok(spec) || !y_pred || !y || !sums || H <= 0 || W <= 0 || !loss_pw_ok(mask, plane_w, period, planes, mask_div))
+        return UCLSTM_E_BADARG;
+    const int64_t total = planes * H * W;
+    if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    return loss_spec_fwd_launch<false, true, true>(spec, y_pred, y, mask, sums, total, H, W, 0, (hipStream_t)stream, mask_div, plane_w, period);
+}
+
+extern "C" int32_t uclstm_loss_spec_fwd_ordered_pw(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                                   const float* plane_w, int32_t period, double* partials, double* sums,
+                                                   int32_t accumulate, int64_t planes, int32_t H, int32_t W, int32_t mask_div,
+                                                   void* stream) {
+    if (!loss_spec_ok(spec) || !y_pred || !y || !partials || !sums || H <= 0 || W <= 0 ||
+        !loss_pw_ok(mask, plane_w, period, planes, mask_div))
+        return UCLSTM_E_BADARG;
+    const int64_t total = planes * H * W;
+    if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    const int rows = grid_for(total, ORDERED_ROWS_CAP);          // = uclstm_loss_fwd_ordered_rows, whatever V is
+    const int32_t rc = loss_spec_fwd_launch<true, true, true>(spec, y_pred, y, mask, partials, total, H, W, rows, (hipStream_t)stream, mask_div,
+                                                              plane_w, period);
+    if (rc != UCLSTM_OK) return rc;
+    UCLSTM_LAUNCH(ordered_sum_f64_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, rows, 4, sums, accumulate);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_loss_spec_bwd_pw(const uclstm_loss_spec* spec, const float* y_pred, const float* y, const float* mask,
+                                           const float* plane_w, int32_t period, const float* coefs, float* grad, int64_t planes,
+                                           int32_t H, int32_t W, int32_t mask_div, void* stream) {
+    if (!loss_spec_ok(spec) || !y_pred || !y || !grad || !coefs || H <= 0 || W <= 0 || !loss_pw_ok(mask, plane_w, period, planes, mask_div))
+        return UCLSTM_E_BADARG;
+    const int64_t total = planes * H * W;
+    if (total >= ((int64_t)1 << 31)) return UCLSTM_E_BADARG;
+    return loss_spec_bwd_launch<true, true>(spec, y_pred, y, mask, coefs, grad, total, H, W, (hipStream_t)stream, mask_div, plane_w, period);
 }
 
 namespace {

@@ -1414,6 +1414,8 @@ class GraphedTrainStep:
         self._pack_batch = ops._PACK_BATCH if (ops.PREPACK and ops.PACK_BATCHED) else None
         if ops.PREPACK and ops.PACK_BATCHED and self._pack_batch is None:
             raise ops.L.UclstmError("GraphedTrainStep: look-ahead packing is on but the capture used no batch (no pack call in the step?)")
+        # likewise the plane-weight table of a WeightedLossSpec: built by the first warm-up step, its address is in the graph
+        self._plane_w = ops.plane_weight_table(self.loss_spec, self.y_pred)[0] if getattr(self.loss_spec, "weighted", False) else None
         self.replays = 0
 
     def __call__(self, x, y, mask=None):

@@ -2423,12 +2423,37 @@ def _mask_broadcast(y_pred, m) -> int:
     return 1
 
 
+# (frame_weights, channel_weights, T, Cy, device) -> (device f32 [T*Cy], the sum of that f32 table in f64).  Built once per key and
+# never evicted (T*Cy*4 bytes each): no step and no graph capture after the first use holds a host-to-device copy, and the pointer a
+# captured graph holds stays valid.
+_PLANE_W = {}
+
+
+def plane_weight_table(spec, y_pred):
+    """The per-plane weights of a loss.WeightedLossSpec for ``y_pred [B,T,Cy,H,W]``: ``q[t*Cy + c] = f32(fw[t] * cw[c])``, the
+    product formed in f64 and rounded once.  Returns ``(table on y_pred's device, sum(q) as a Python float)``."""
+    if y_pred.dim() != 5:
+        raise ValueError(f"a WeightedLossSpec with weights needs y_pred [B,T,Cy,H,W], got {y_pred.dim()} dimensions")
+    T, Cy, dev = int(y_pred.shape[1]), int(y_pred.shape[2]), y_pred.device
+    key = (spec.frame_weights, spec.channel_weights, T, Cy, dev.type, dev.index)
+    hit = _PLANE_W.get(key)
+    if hit is None:
+        q = torch.tensor(spec.plane_weights(T, Cy), dtype=torch.float64).float()
+        qsum = float(q.double().sum())
+        if not qsum > 0:
+            raise ValueError("WeightedLossSpec: every frame weight x channel weight product rounds to 0 in f32")
+        hit = _PLANE_W[key] = (q.to(dev), qsum)
+    return hit
+
+
 class LossFn(torch.autograd.Function):
     """``spec``: None = the reference's loss on uclstm_loss_fwd / _bwd; a loss.LossSpec = uclstm_loss_spec_fwd / _bwd (loss.py
     sends the default spec here as None).  Both are logged as the reduction they are, loss_fwd / loss_fwd_ordered.
     A mask with ONE channel over a ``y`` of several (``y [B,T,Cy,H,W]``, ``mask [B,T,1,H,W]``: a vector target under the loaders'
     mask) is broadcast over the channels as main.py:40-43 does: uclstm_loss_spec_fwd_bc / _fwd_ordered_bc / _bwd_bc, where the
-    reference's loss runs as ``LossSpec.reference()``.  Every other shape takes the entry points above."""
+    reference's loss runs as ``LossSpec.reference()``.  Every other shape takes the entry points above.
+    A loss.WeightedLossSpec with weights (``spec.weighted``) takes uclstm_loss_spec_fwd_pw / _fwd_ordered_pw / _bwd_pw with the
+    cached table of plane_weight_table, whatever the mask's shape (mask_div = 1 for a mask per plane or none)."""
 
     @staticmethod
     def forward(ctx, y_pred, y, mask, use_mask, spec=None):
@@ -2443,7 +2468,9 @@ class LossFn(torch.autograd.Function):
         Cy = _mask_broadcast(y_pred, m)
         if Cy > 1 and desc is None:
             desc = L.LossSpecDesc(L.LOSS_POINT_L1, 3, 1.0, 4.0, 1)
-        ctx.desc, ctx.mask_div = desc, Cy
+        ctx.desc, ctx.mask_div, ctx.plane_w = desc, Cy, None
+        if getattr(spec, "weighted", False):
+            return LossFn._forward_pw(ctx, y_pred, y, m, spec, desc, Cy)
         if Cy > 1:
             return LossFn._forward_bc(ctx, y_pred, y, m, spec, desc, Cy)
         if _DETERMINISTIC:
@@ -2484,12 +2511,33 @@ class LossFn(torch.autograd.Function):
         return LossFn._finish(ctx, y_pred, y, m, spec, sums)
 
     @staticmethod
-    def _finish(ctx, y_pred, y, m, spec, sums):
+    def _forward_pw(ctx, y_pred, y, m, spec, desc, mask_div):
+        q, qsum = plane_weight_table(spec, y_pred)
+        ctx.plane_w = q
+        H, W = y_pred.shape[-2], y_pred.shape[-1]
+        planes, period = y_pred.numel() // (H * W), q.numel()
+        if _DETERMINISTIC:
+            sums = torch.empty((4,), dtype=torch.float64, device=y_pred.device)
+            partials = torch.empty((int(L.lib.uclstm_loss_fwd_ordered_rows(planes, H, W)), 4), dtype=torch.float64, device=y_pred.device)
+            _log_reduce("loss_fwd_ordered")
+            L.check(L.lib.uclstm_loss_spec_fwd_ordered_pw(C.byref(desc), _p(y_pred), _p(y), _p(m), _p(q), period, _p(partials), _p(sums), 0,
+                                                          planes, H, W, mask_div, _stream()), "loss_spec_fwd_ordered_pw")
+        else:
+            sums = torch.zeros((4,), dtype=torch.float64, device=y_pred.device)
+            _log_reduce("loss_fwd")
+            L.check(L.lib.uclstm_loss_spec_fwd_pw(C.byref(desc), _p(y_pred), _p(y), _p(m), _p(q), period, _p(sums), planes, H, W, mask_div,
+                                                  _stream()), "loss_spec_fwd_pw")
+        # unmasked, every element of plane p counts q[p mod period] times: the denominators in f64 on the host, from the f32 table
+        return LossFn._finish(ctx, y_pred, y, m, spec, sums, (planes // period) * qsum)
+
+    @staticmethod
+    def _finish(ctx, y_pred, y, m, spec, sums, plane_mass=None):
+        """``plane_mass``: the summed weight of the planes (None: every plane counts once)."""
         H, W = y_pred.shape[-2], y_pred.shape[-1]
         planes = y_pred.numel() // (H * W)
         eps, gw = (1e-8, 0.005) if spec is None else (float(spec.eps), float(spec.grad_weight))
-        n1 = float(y_pred.numel())
-        n2 = float(planes * (H - 1) * (W - 1))
+        n1 = float(y_pred.numel()) if plane_mass is None else float(H * W) * plane_mass
+        n2 = float(planes * (H - 1) * (W - 1)) if plane_mass is None else float((H - 1) * (W - 1)) * plane_mass
         if m is not None:
             d1 = sums[1] + eps
             d2 = sums[3] + eps
@@ -2512,7 +2560,11 @@ class LossFn(torch.autograd.Function):
         planes = y_pred.numel() // (H * W)
         grad = torch.empty_like(y_pred)
         coefs = torch.stack((c1 * g, c2 * g)).float().contiguous()      # stays on device: no host sync in the step
-        if ctx.mask_div > 1:
+        if ctx.plane_w is not None:
+            q = ctx.plane_w
+            L.check(L.lib.uclstm_loss_spec_bwd_pw(C.byref(ctx.desc), _p(y_pred), _p(y), _p(m), _p(q), q.numel(), _p(coefs), _p(grad), planes,
+                                                  H, W, ctx.mask_div, _stream()), "loss_spec_bwd_pw")
+        elif ctx.mask_div > 1:
             L.check(L.lib.uclstm_loss_spec_bwd_bc(C.byref(ctx.desc), _p(y_pred), _p(y), _p(m), _p(coefs), _p(grad), planes, H, W,
                                                   ctx.mask_div, _stream()), "loss_spec_bwd_bc")
         elif ctx.desc is None:
