@@ -624,6 +624,22 @@ int32_t uclstm_adamw_step_scaled(float* p, float* m, float* v, const float* g, i
 int32_t uclstm_loss_scale_update(float* scale_state, const double* sumsq, float growth, float backoff, int32_t interval,
                                  void* stream);
 
+/* Exponential moving average of the weights, one sweep launched behind any of the AdamW entry points above: ema, p flat f32 [n].
+ * ema_state = DEVICE f32[8] {decay, warmup, every, steps_seen, updates_done, reserved x 3}: steps_seen counts the applied
+ * optimiser steps this average has seen, updates_done the updates of ema made; both exact up to 2^24.
+ *   sumsq != NULL and *sumsq NaN or infinite (the test of uclstm_adamw_step_scaled / uclstm_loss_scale_update on the same
+ *   value): the optimiser skipped that step, and NOTHING is touched, neither ema nor a count.  sumsq == NULL: never skipped.
+ *   Otherwise the step is seen, and ema is updated only if (steps_seen + 1) % every == 0, with the decay of update number
+ *   k = updates_done + 1: d = decay when warmup <= 0, else min(decay, (1 + k) / (warmup + k)), computed in double and rounded
+ *   to f32 once; ema[i] = fmaf(d, ema[i] - p[i], p[i]).
+ * The counts are advanced by a one-thread kernel launched behind the sweep in the same call, so every block of the sweep reads
+ * the old ones; the arguments never change, so the call can sit in a captured graph.  No atomics, no reductions.
+ * UCLSTM_E_BADARG before any launch for a NULL ema / p / ema_state or n <= 0. */
+int32_t uclstm_ema_update(float* ema, const float* p, int64_t n, const double* sumsq /* nullable */, float* ema_state, void* stream);
+/* Exchange the contents of two DISJOINT f32 buffers in place (no temporary): a[i] <-> b[i] for i in [0, n).  UCLSTM_E_BADARG and
+ * nothing written for a NULL a / b, n < 0, a == b or overlapping ranges; n == 0 is UCLSTM_OK without a launch. */
+int32_t uclstm_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* Data path around the step                              */
 /* ------------------------------------------------------------------------------------ */

@@ -12,6 +12,10 @@ Prints medians and min - max per arm and whether each B median exceeds A's media
 
     python tools/bench_adamw.py [--rounds 9] [--out profiles/adamw_groups_ab.txt]
     python tools/bench_adamw.py --step [--rounds 5]     # driver-form train_step, ConvLSTM weights frozen vs all trainable
+    python tools/bench_adamw.py --ema [--rounds 9] [--out profiles/ema_ab.txt]
+        # the weight EMA: the optimiser step (sum of squares + uclstm_adamw_step_dev) without / with / without the
+        # uclstm_ema_update sweep behind it (A/B/A), the sweep alone beside uclstm_adamw_step_groups (bytes per second of both
+        # in the same run), uclstm_swap_f32 alone, and the launch log of a training step without and with an EMA attached
 """
 import argparse
 import ctypes as C
@@ -30,6 +34,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=9)
 ap.add_argument("--out", default=None, help="also write the table to this file")
 ap.add_argument("--step", action="store_true", help="time the driver-form training step (batch 32, T 20, 64 x 64) instead")
+ap.add_argument("--ema", action="store_true", help="time the optimiser step without and with the weight-EMA sweep, and the swap, instead")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 st = torch.cuda.current_stream()
@@ -141,7 +146,90 @@ def step_ab():
     return True
 
 
-ok = step_ab() if a.step else optimiser_ab()
+def ema_ab():
+    with torch.device("meta"):
+        model = U.TemporalUNetDualView(1, 1, base_ch=64, lstm_layers=1, use_skip_lstm=True, use_attention=False)
+    n = sum(p.numel() for p in model.parameters())
+    say(f"{n} parameters (the benchmark model, BASELINE.json configs[1]); cold caches: a 1 GiB fill before every measurement")
+    torch.manual_seed(0)
+    p = torch.randn(n, device=dev) * 0.02
+    g = torch.randn(n, device=dev) * 1e-3
+    m, v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    shadow = p.clone()
+    sq = torch.zeros(1, dtype=torch.float64, device=dev)
+    hyper = torch.tensor([1e-4, 0.9, 0.999, 1e-8, 1e-4, 1.0, 0, 0], dtype=torch.float32, device=dev)
+    hyper_g = torch.tensor([[1.0, 0, 0, 0, 0, 0, 0, 0], [1e-4, 0.9, 0.999, 1e-8, 1e-4, 0, 0, 0]], dtype=torch.float32, device=dev)
+    runs = torch.tensor([[0, n, 0]], dtype=torch.int64, device=dev)
+    ema_state = torch.tensor([0.999, 10.0, 1.0, 0, 0, 0, 0, 0], dtype=torch.float32, device=dev)
+    s = C.c_void_p(st.cuda_stream)
+
+    def step():
+        sq.zero_()
+        L.check(L.lib.uclstm_sumsq(ptr(g), n, ptr(sq), s), "sumsq")
+        L.check(L.lib.uclstm_adamw_step_dev(ptr(p), ptr(m), ptr(v), ptr(g), n, ptr(sq), ptr(hyper), s), "dev")
+
+    def sweep():
+        L.check(L.lib.uclstm_ema_update(ptr(shadow), ptr(p), n, None, ptr(ema_state), s), "ema_update")
+
+    def step_ema():
+        step()
+        sweep()
+
+    arms = {
+        "A  step (sumsq + adamw_step_dev)": step,
+        "B  step + ema_update": step_ema,
+        "A' step again": step,
+        "G  adamw_step_groups, 1 group": lambda: L.check(L.lib.uclstm_adamw_step_groups(ptr(p), ptr(m), ptr(v), ptr(g), n, ptr(sq), ptr(runs), 1,
+                                                                                        ptr(hyper_g), 1, None, s), "groups"),
+        "E  ema_update alone": sweep,
+        "S  swap_f32 alone": lambda: L.check(L.lib.uclstm_swap_f32(ptr(p), ptr(shadow), n, s), "swap_f32"),
+    }
+    times = {k: [] for k in arms}
+    for r in range(a.rounds + 1):
+        for name, fn in arms.items():
+            t = timed(fn)
+            if r:
+                times[name].append(t)
+    report(arms, times)
+    med = {k: statistics.median(t) for k, t in times.items()}
+    names = list(arms)
+    a_med = 0.5 * (med[names[0]] + med[names[2]])
+    spread = max(max(times[names[0]]) - min(times[names[0]]), max(times[names[2]]) - min(times[names[2]]), abs(med[names[0]] - med[names[2]]))
+    bw_g, bw_e, bw_s = 28 * n / med[names[3]] / 1e3, 12 * n / med[names[4]] / 1e3, 16 * n / med[names[5]] / 1e3
+    say(f"A/B/A: step {a_med:.1f} us (A and A' medians {med[names[0]]:.1f} / {med[names[2]]:.1f}, spread {spread:.1f}), with the EMA sweep "
+        f"{med[names[1]]:.1f} us: +{med[names[1]] - a_med:.1f} us = {100 * (med[names[1]] - a_med) / a_med:.1f} % of the stand-alone step")
+    say(f"sweep alone / AdamW sweep alone (G): {med[names[4]]:.1f} / {med[names[3]]:.1f} us = {med[names[4]] / med[names[3]]:.3f} "
+        f"(by bytes 12 / 28 = {12 / 28:.3f})")
+    say(f"bytes per second: adamw_groups_kernel 28 B/parameter {bw_g:.0f} GB/s, ema_update_kernel 12 B/parameter {bw_e:.0f} GB/s, "
+        f"swap_f32_kernel 16 B/parameter {bw_s:.0f} GB/s")
+    if bw_e < bw_g:
+        say(f"NOTE: the EMA sweep moves its bytes at {100 * bw_e / bw_g:.0f} % of adamw_groups_kernel's rate in this run (not tuned further here)")
+    say(f"fusing the sweep into the AdamW kernels would save the 4 B/parameter re-read of p: at most {4 * n / (bw_e * 1e3):.1f} us of the "
+        f"{med[names[4]]:.1f} us above (not built; see DESIGN.md)")
+    # the launch log of a training step: what an attached EMA adds, and that nothing else moves
+    torch.manual_seed(0)
+    net = U.TemporalUNetDualView(1, 1, base_ch=64, lstm_layers=1, use_skip_lstm=True, use_attention=False).to(dev).train()
+    opt = U.FusedAdamW(net.parameters(), lr=1e-3, weight_decay=1e-4, max_grad_norm=1.0)
+    data = U.SyntheticSequences(4, 3, 64, 64, seed=1, kind="uniform", device=dev)
+    logs = []
+    for attach in (False, False, True):
+        if attach:
+            opt.attach_ema()
+        U.ops.LAUNCH_LOG = []
+        try:
+            U.train_step(net, opt, data.x, data.y, data.mask, True)
+            torch.cuda.synchronize()
+            logs.append(list(U.ops.LAUNCH_LOG))
+        finally:
+            U.ops.LAUNCH_LOG = None
+    extra = [e for e in logs[2] if e[0] == "ema"]
+    same = logs[0] == logs[1] == [e for e in logs[2] if e[0] != "ema"]
+    say(f"launch log of one train_step (base_ch 64, batch 4, T 3, 64 x 64): {len(logs[0])} entries without an EMA, none of kind 'ema'; with "
+        f"attach_ema() the same entries {'in the same order' if same else 'DIFFER'} plus {extra}")
+    return same and extra == [("ema", "update", False)] and not [e for e in logs[0] if e[0] == "ema"]
+
+
+ok = ema_ab() if a.ema else step_ab() if a.step else optimiser_ab()
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:

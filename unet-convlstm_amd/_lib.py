@@ -244,6 +244,8 @@ _PROTOS = {
     "uclstm_adamw_step_groups": [_P, _P, _P, _P, _L, _P, _P, _I, _P, _I, _P, _P],
     "uclstm_adamw_step_scaled": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _F, _P, _P],
     "uclstm_loss_scale_update": [_P, _P, _F, _F, _I, _P],
+    "uclstm_ema_update": [_P, _P, _L, _P, _P, _P],
+    "uclstm_swap_f32": [_P, _P, _L, _P],
     "uclstm_dataset_transform": [_P, _P, _P, _P, _P, _L, _I, _I, _F, _F, _F, _I, _F, _F, _F, _P],
     "uclstm_dataset_gather_transform": [_P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _I, _F, _F, _F, _P],
     "uclstm_dataset_gather_augment": [_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _I, _F, _F, _F, _P],

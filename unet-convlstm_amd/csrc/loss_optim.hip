@@ -366,6 +366,90 @@ __global__ void loss_scale_update_kernel(float* __restrict__ state, const double
     }
 }
 
+// Exponential moving average of the weights, one sweep behind the AdamW kernels: ema[i] = d * ema[i] + (1 - d) * p[i], written
+// as one rounded subtraction and one fma.  state = f32[8] {decay, warmup, every, steps seen, updates done, reserved x 3}; the two
+// counts are exact up to 2^24 and are bumped by ema_advance_kernel AFTER the sweep, so every block reads the old ones.  sumsq
+// (optional): the step this sweep follows was skipped where step_overflowed says so -- the predicate of the AdamW kernels and of
+// loss_scale_update_kernel on the same *sumsq -- and then nothing is touched (uniform over the grid).  Update number k uses
+// d = min(decay, (1 + k) / (warmup + k)) (warmup <= 0: decay), derived in double and rounded once as the bias corrections of
+// adamw_dev_kernel are.  ema_due / ema_decay are the one definition for the sweep and the count kernel.
+__device__ __forceinline__ bool ema_due(const float* __restrict__ state) {
+    const double every = fmax((double)state[2], 1.0);
+    return fmod((double)state[3] + 1.0, every) == 0.0;
+}
+__device__ __forceinline__ float ema_decay(const float* __restrict__ state) {
+    const double decay = (double)state[0], warmup = (double)state[1], k = (double)state[4] + 1.0;
+    return (float)(warmup > 0.0 ? fmin(decay, (1.0 + k) / (warmup + k)) : decay);
+}
+constexpr int EMA_U = 4;                                         // loads in flight per lane and stream, as adamw_groups_kernel's U
+constexpr int EMA_GRID_CAP = 2048;
+__global__ void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t n, const double* __restrict__ sumsq,
+                                  const float* __restrict__ state) {
+#pragma clang fp contract(off)
+    if (sumsq && step_overflowed(*sumsq)) return;
+    if (!ema_due(state)) return;
+    const float d = ema_decay(state);
+    constexpr int U = EMA_U;
+    for (int64_t c0 = (int64_t)blockIdx.x * (U * NT); c0 < n; c0 += (int64_t)gridDim.x * (U * NT)) {
+        const int64_t i0 = c0 + threadIdx.x;
+        if (c0 + U * NT <= n) {                                  // a full chunk (uniform): no bounds test on the loads
+            float e[U], w[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                e[u] = ema[i0 + u * NT];
+                w[u] = p[i0 + u * NT];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) ema[i0 + u * NT] = __builtin_fmaf(d, e[u] - w[u], w[u]);
+        } else {                                                 // the buffer's last, partial chunk
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = i0 + u * NT;
+                if (i < n) {
+                    const float w = p[i];
+                    ema[i] = __builtin_fmaf(d, ema[i] - w, w);
+                }
+            }
+        }
+    }
+}
+__global__ void ema_advance_kernel(float* __restrict__ state, const double* __restrict__ sumsq) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (sumsq && step_overflowed(*sumsq)) return;
+    const bool due = ema_due(state);
+    state[3] += 1.f;
+    if (due) state[4] += 1.f;
+}
+
+// a <-> b, element for element, the chunked walk of ema_update_kernel: the caller has checked that the ranges are disjoint
+__global__ void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+    constexpr int U = EMA_U;
+    for (int64_t c0 = (int64_t)blockIdx.x * (U * NT); c0 < n; c0 += (int64_t)gridDim.x * (U * NT)) {
+        const int64_t i0 = c0 + threadIdx.x;
+        if (c0 + U * NT <= n) {
+            float x[U], y[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                x[u] = a[i0 + u * NT];
+                y[u] = b[i0 + u * NT];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                a[i0 + u * NT] = y[u];
+                b[i0 + u * NT] = x[u];
+            }
+        } else {
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = i0 + u * NT;
+                if (i < n) {
+                    const float x = a[i], y = b[i];
+                    a[i] = y;
+                    b[i] = x;
+                }
+            }
+        }
+    }
+}
+
 // NPZSequenceDataset.__getitem__ for a batch (train/unet.py:273-304): mask from RAW channel 0 (> 1.1) before scaling,
 // x / norm_const, y clipped -> asinh(y / scale) -> [-1, 1]
 __global__ void dataset_transform_kernel(const float* __restrict__ xr, const float* __restrict__ yr, float* __restrict__ x,
@@ -599,6 +683,24 @@ extern "C" int32_t uclstm_loss_scale_update(float* scale_state, const double* su
                                             void* stream) {
     if (!scale_state || !sumsq || growth < 1.f || backoff <= 0.f || backoff > 1.f || interval < 1) return UCLSTM_E_BADARG;
     UCLSTM_LAUNCH(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scale_state, sumsq, growth, backoff, interval);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_ema_update(float* ema, const float* p, int64_t n, const double* sumsq, float* ema_state, void* stream) {
+    if (!ema || !p || n <= 0 || !ema_state) return UCLSTM_E_BADARG;
+    UCLSTM_LAUNCH(ema_update_kernel, dim3(grid_for((n + EMA_U - 1) / EMA_U, EMA_GRID_CAP)), dim3(NT), 0, (hipStream_t)stream, ema, p, n, sumsq,
+                  (const float*)ema_state);
+    UCLSTM_LAUNCH(ema_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ema_state, sumsq);
+    return UCLSTM_OK;
+}
+
+extern "C" int32_t uclstm_swap_f32(float* a, float* b, int64_t n, void* stream) {
+    if (!a || !b || n < 0 || a == b) return UCLSTM_E_BADARG;
+    if (n > (int64_t)(UINTPTR_MAX / sizeof(float))) return UCLSTM_E_BADARG;
+    const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
+    if (ua < ub ? ub - ua < bytes : ua - ub < bytes) return UCLSTM_E_BADARG;          // the ranges overlap
+    if (n == 0) return UCLSTM_OK;
+    UCLSTM_LAUNCH(swap_f32_kernel, dim3(grid_for((n + EMA_U - 1) / EMA_U, EMA_GRID_CAP)), dim3(NT), 0, (hipStream_t)stream, a, b, n);
     return UCLSTM_OK;
 }
 

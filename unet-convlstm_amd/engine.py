@@ -17,7 +17,7 @@ import torch
 
 from . import ops
 from .loss import compute_loss, check_spec, LossSpec
-from .optim import FusedAdamW
+from .optim import FusedAdamW, WeightEMA
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1326,6 +1326,8 @@ def train_step(model, optimizer, x, y, mask=None, use_mask=True, ddp=None, clip_
     (main.py:91-108).  Returns ``(loss, y_pred)`` as device tensors; nothing here waits for the GPU.  ``loss``: the
     ``LossSpec`` of ``compute_loss(spec=...)``; None is the reference's loss."""
     spec = check_spec(loss)
+    if getattr(getattr(optimizer, "ema", None), "_swapped", False):      # optimizer.step() would refuse: do so before BatchNorm's buffers move
+        raise RuntimeError("train_step inside WeightEMA.swapped(): the parameters hold the averaged weights there")
     optimizer.zero_grad(set_to_none=True)
     if ddp is not None:
         ddp.reset()
@@ -1427,6 +1429,8 @@ class GraphedTrainStep:
             self.mask.copy_(mask, non_blocking=True)
         self.optimizer.max_grad_norm = self.clip_norm
         self.optimizer.sync_hyper()
+        if self.optimizer.ema is not None and self.optimizer.ema._swapped:          # what optimizer.step() refuses in an eager step
+            raise RuntimeError("GraphedTrainStep inside WeightEMA.swapped(): the parameters hold the averaged weights there")
         self.graph.replay()
         self.replays += 1
         ops.weights_changed()          # what optimizer.step() tells the panel caches in an eager step
@@ -1568,13 +1572,23 @@ def _evaluate(model, loader, device, dataset_obj, use_mask, tta, spec, report=No
     return float(total) / max(n, 1), met
 
 
+def _ema_weights(ema: Optional[WeightEMA]):
+    """``ema.swapped()`` for the evaluation passes, or nothing when no EMA is given."""
+    if ema is None:
+        return contextlib.nullcontext()
+    if not isinstance(ema, WeightEMA):
+        raise TypeError(f"ema must be a WeightEMA (FusedAdamW.attach_ema) or None, got {type(ema).__name__}")
+    return ema.swapped()
+
+
 @torch.no_grad()
 def evaluate(model, loader, device, dataset_obj, use_mask=True, per_channel: bool = False, tta=None, loss: Optional[LossSpec] = None):
     """Reference main.py:150-205.  ``tta``: None, or the ``codes`` of ``predict_tta`` (``"flips"``, ``"d4"``, an iterable): the
     prediction is then the test-time-augmented mean.  ``loss``: the ``LossSpec`` whose value is averaged (None: the reference's).
     A ``VectorNPZDataset`` as ``dataset_obj``: the averaged outputs come back with their channels turned (``predict_tta(dataset=)``),
     the three metrics are pooled over the target channels, and ``per_channel=True`` appends
-    ``{"mae": [Cy], "rmse": [Cy], "me": [Cy]}``."""
+    ``{"mae": [Cy], "rmse": [Cy], "me": [Cy]}``.  On the averaged weights of ``FusedAdamW.attach_ema()``: call it inside
+    ``with ema.swapped():`` (the positional signature is pinned; the two report functions take ``ema=`` themselves)."""
     avg, met = _evaluate(model, loader, device, dataset_obj, use_mask, tta, check_spec(loss))
     return (avg,) + met.result() + ((met.per_channel(),) if per_channel else ())
 
@@ -1799,11 +1813,15 @@ def evaluate_report(model, loader, device, dataset_obj, use_mask=True, tta=None,
     of ``EvalReport.result``).  Against a SEPARATE ``evaluate()`` pass they agree as far as ``evaluate`` agrees with itself:
     its loss and metric kernels add block partials with f64 atomics in arrival order, so two passes can differ in the last
     bits (~1e-13 relative); the report's own sums do not have that freedom.  (In deterministic mode, ``ops.deterministic()``, those
-    kernels add their block partials in a fixed order and two passes are identical.)  ``tta`` and ``loss``: as in ``evaluate``."""
+    kernels add their block partials in a fixed order and two passes are identical.)  ``tta`` and ``loss``: as in ``evaluate``.
+    ``ema=`` (keyword, not passed on to the report): the ``WeightEMA`` of the model's optimiser; the pass then runs inside
+    ``ema.swapped()``, on the averaged weights (BatchNorm running statistics as they are), and leaves the weights as they were."""
+    averaged = _ema_weights(report_kwargs.pop("ema", None))          # a wrong type is refused here, before anything is built
     _refuse_vector(dataset_obj, "evaluate_report")
     spec = check_spec(loss)
     rep = EvalReport(dataset_obj, device=device, **report_kwargs)
-    avg, met = _evaluate(model, loader, device, dataset_obj, use_mask, tta, spec, rep)
+    with averaged:
+        avg, met = _evaluate(model, loader, device, dataset_obj, use_mask, tta, spec, rep)
     return (avg,) + met.result() + (rep.result(),)
 
 
@@ -1979,7 +1997,9 @@ def evaluate_vector_report(model, loader, device, dataset_obj, use_mask=True, tt
     """``evaluate()``'s loop for a ``VectorNPZDataset`` with a ``VectorEvalReport`` fed from the same ``y_pred``: returns
     ``(avg_loss, mae, rmse, me, report)``.  The first four are ``evaluate``'s (pooled over the target channels, computed from the same
     launches as the report); ``report`` is the dict of ``VectorEvalReport.result``.  With ``tta`` the averaged outputs come back with
-    their channels turned (``predict_tta(dataset=)``)."""
+    their channels turned (``predict_tta(dataset=)``).  ``ema=``: as in ``evaluate_report``."""
+    averaged = _ema_weights(report_kwargs.pop("ema", None))          # a wrong type is refused here, before anything is built
     rep = VectorEvalReport(dataset_obj, device=device, **report_kwargs)
-    avg, met = _evaluate(model, loader, device, dataset_obj, use_mask, tta, check_spec(loss), rep)
+    with averaged:
+        avg, met = _evaluate(model, loader, device, dataset_obj, use_mask, tta, check_spec(loss), rep)
     return (avg,) + met.result() + (rep.result(),)

@@ -7,7 +7,10 @@ reduction and one AdamW sweep that reads the clip coefficient on device, no host
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import math
+import numbers
 from typing import Iterable, List, Optional, Sequence, Tuple
 
 import torch
@@ -84,6 +87,103 @@ class FlatParams:
         self.attach_grads()
 
 
+def check_ema(decay, warmup, every) -> Tuple[float, float, int]:
+    """The arguments of ``FusedAdamW.attach_ema`` as ``(decay, warmup, every)``, or ``ValueError``: ``0 < decay < 1``, ``warmup``
+    finite and ``>= 0``, ``every`` an integer ``>= 1`` (below 2^24, where the device-side counts stay exact).  No device."""
+    if isinstance(decay, bool) or not isinstance(decay, numbers.Real) or not 0.0 < float(decay) < 1.0:
+        raise ValueError(f"attach_ema: decay must be a number with 0 < decay < 1, got {decay!r}")
+    if float(torch.tensor(float(decay), dtype=torch.float32)) >= 1.0:
+        raise ValueError(f"attach_ema: decay {decay!r} rounds to 1 in float32, the shadow would never move")
+    if isinstance(warmup, bool) or not isinstance(warmup, numbers.Real) or not math.isfinite(float(warmup)) or float(warmup) < 0.0:
+        raise ValueError(f"attach_ema: warmup must be a finite number >= 0, got {warmup!r}")
+    if isinstance(every, bool) or not isinstance(every, numbers.Integral) or not 1 <= every < (1 << 24):
+        raise ValueError(f"attach_ema: every must be an integer with 1 <= every < 2^24, got {every!r}")
+    return float(decay), float(warmup), int(every)
+
+
+class WeightEMA:
+    """Exponential moving average of an optimiser's weights, kept on the device (``FusedAdamW.attach_ema``).
+
+    ``shadow`` is a flat f32 tensor laid out as ``optimizer.flat.flat_p`` (trainable parameters only); ``state`` is the device
+    f32[8] of ``uclstm_ema_update``: ``{decay, warmup, every, steps_seen, updates_done, reserved x 3}``.  Every
+    ``optimizer.step()`` ends with one launch of that entry point on the step's stream, so the average follows eager steps,
+    captured steps (``engine.GraphedTrainStep``) and the skipped steps of fp16 loss scaling alike, without a host sync.
+    Update number ``k`` uses ``min(decay, (1 + k) / (warmup + k))`` (``warmup = 0``: ``decay``), and only every ``every``-th
+    applied step updates.  BatchNorm running statistics are not averaged (they are moving averages already)."""
+
+    def __init__(self, optimizer: "FusedAdamW", decay: float, warmup: float, every: int):
+        self.optimizer = optimizer
+        self.decay, self.warmup, self.every = decay, warmup, every
+        flat_p = optimizer.flat.flat_p
+        self.shadow = flat_p.detach().clone()
+        self.state = torch.tensor([decay, warmup, float(every), 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32).to(flat_p.device)
+        self._swapped = False
+
+    def steps_seen(self) -> int:
+        """Applied optimiser steps this average has seen (reads the device)."""
+        return int(self.state[3].item())
+
+    def updates_done(self) -> int:
+        """Updates of the shadow made so far (reads the device)."""
+        return int(self.state[4].item())
+
+    def _update(self, sumsq: Optional[torch.Tensor]) -> None:
+        from . import _lib as L
+        from . import ops
+        f = self.optimizer.flat
+        if ops.LAUNCH_LOG is not None:
+            ops.LAUNCH_LOG.append(("ema", "update", sumsq is not None))
+        L.check(L.lib.uclstm_ema_update(C.c_void_p(self.shadow.data_ptr()), C.c_void_p(f.flat_p.data_ptr()), f.numel,
+                                        None if sumsq is None else C.c_void_p(sumsq.data_ptr()), C.c_void_p(self.state.data_ptr()),
+                                        ops._stream()), "ema_update")
+
+    def _exchange(self) -> None:
+        from . import _lib as L
+        from . import ops
+        f = self.optimizer.flat
+        L.check(L.lib.uclstm_swap_f32(C.c_void_p(f.flat_p.data_ptr()), C.c_void_p(self.shadow.data_ptr()), f.numel, ops._stream()),
+                "swap_f32")
+        ops.weights_changed()          # raw-pointer rewrite of the parameters: the panel caches must be told
+
+    @contextlib.contextmanager
+    def swapped(self):
+        """Inside the block the model computes with the averaged weights: the CONTENTS of ``flat_p`` and ``shadow`` are
+        exchanged in place (``uclstm_swap_f32``, no copy the size of the model) and the panel caches are told
+        (``ops.weights_changed()``), on entry and again on exit, also when the block raises.  No address changes, so ``p.data``
+        views, gradient views, weight panels and captured graphs stay valid; after the block the weights and the shadow are bit
+        for bit what they were.  Not under a graph capture, not nested, and no ``optimizer.step()`` inside."""
+        if self._swapped:
+            raise RuntimeError("WeightEMA.swapped(): already inside swapped() (it does not nest)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("WeightEMA.swapped() inside a graph capture: exchange the weights outside the captured region")
+        self._exchange()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._swapped = False
+            self._exchange()
+
+    @torch.no_grad()
+    def model_state_dict(self, model: torch.nn.Module):
+        """``model.state_dict()`` with every trainable parameter of the optimiser replaced by its averaged value; everything
+        else (frozen parameters, buffers such as the BatchNorm running statistics) as it is.  All entries are clones: the
+        result stays valid after the next step, and loads wherever a checkpoint of ``model`` loads."""
+        if self._swapped:
+            raise RuntimeError("WeightEMA.model_state_dict() inside swapped(): the shadow holds the live weights there")
+        f = self.optimizer.flat
+        where = {id(p): (o, p.numel()) for p, o in zip(f.params, f.offsets)}
+        sd = model.state_dict()
+        out = type(sd)((k, v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in sd.items())
+        if hasattr(sd, "_metadata"):
+            out._metadata = sd._metadata
+        for name, p in model.named_parameters(remove_duplicate=False):
+            if id(p) in where and name in out:
+                o, n = where[id(p)]
+                out[name] = self.shadow[o:o + n].view(p.shape).clone()
+        return out
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """AdamW(lr, betas, eps, weight_decay) + optional ``clip_grad_norm_(max_grad_norm)`` in two HIP kernels.
 
@@ -127,6 +227,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=self.flat.flat_p.device)
         self.max_grad_norm = max_grad_norm
         self.step_count = 0
+        self.ema: Optional[WeightEMA] = None        # attach_ema()
         # fp16 compute (ops.compute_dtype(torch.float16)): dynamic loss scaling, all on the device.  ``scale_state`` =
         # [scale, growth tracker, successful steps]; the training step multiplies the loss by scale_state[0] before backward.
         self.scale_state = None
@@ -161,6 +262,19 @@ class FusedAdamW(torch.optim.Optimizer):
         if getattr(self, "_laid_out", False):
             raise RuntimeError("FusedAdamW.add_param_group: the flat buffers are laid out once, in __init__; build a new optimiser")
         super().add_param_group(param_group)
+
+    def attach_ema(self, decay: float = 0.999, warmup: float = 10.0, every: int = 1) -> WeightEMA:
+        """Keep an exponential moving average of the weights on the device (``WeightEMA``): from now on every ``step()`` ends
+        with one ``uclstm_ema_update`` sweep on its stream.  Called once, after construction; the shadow starts as a copy of the
+        current weights.  Update number ``k`` uses the decay ``min(decay, (1 + k) / (warmup + k))`` (``warmup=0``: always
+        ``decay``), and only every ``every``-th applied step updates.  A step that fp16 loss scaling skips is not seen."""
+        decay, warmup, every = check_ema(decay, warmup, every)
+        if getattr(self, "ema", None) is not None:
+            raise RuntimeError("FusedAdamW.attach_ema: an EMA is attached already")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdamW.attach_ema() inside a graph capture")
+        self.ema = WeightEMA(self, decay, warmup, every)
+        return self.ema
 
     def _group_values(self):
         return tuple((float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
@@ -219,6 +333,10 @@ class FusedAdamW(torch.optim.Optimizer):
                        "scale_state": None if self.scale_state is None else self.scale_state.detach().clone(),
                        # the layout of the flat buffers: a state saved with another grouping or order must not be loaded
                        "sizes": [int(p.numel()) for p in self.flat.params], "tensor_groups": list(self._tensor_groups)}
+        if self.ema is not None:
+            if self.ema._swapped:
+                raise RuntimeError("FusedAdamW.state_dict() inside WeightEMA.swapped(): the shadow holds the live weights there")
+            sd["fused"]["ema"] = {"shadow": self.ema.shadow.detach().clone(), "state": self.ema.state.detach().clone()}
         return sd
 
     def load_state_dict(self, state_dict) -> None:
@@ -243,6 +361,24 @@ class FusedAdamW(torch.optim.Optimizer):
             self.hyper[6] = float(self.step_count)
         if fused.get("scale_state") is not None and self.scale_state is not None:
             self.scale_state.copy_(fused["scale_state"])
+        # The weight EMA.  A state with "ema" restores the shadow and all of its device state (decay, warm-up, period and both
+        # counts); a state WITHOUT it re-seeds the shadow from the weights as they are at this moment (load the model first)
+        # and zeroes the counts, so the warm-up starts over.  An "ema" entry is ignored by an optimiser that has none attached.
+        if self.ema is not None:
+            ema = self.ema
+            if ema._swapped:
+                raise RuntimeError("FusedAdamW.load_state_dict() inside WeightEMA.swapped()")
+            saved = fused.get("ema")
+            if saved is not None:
+                if saved["shadow"].numel() != self.flat.numel or saved["state"].numel() != ema.state.numel():
+                    raise ValueError("FusedAdamW.load_state_dict: the saved EMA does not fit this optimiser's flat buffer")
+                ema.shadow.copy_(saved["shadow"])
+                ema.state.copy_(saved["state"])
+                decay, warmup, every = (float(v) for v in ema.state[:3].tolist())
+                ema.decay, ema.warmup, ema.every = decay, warmup, int(every)
+            else:
+                ema.shadow.copy_(self.flat.flat_p)
+                ema.state[3:5] = 0.0
 
     @torch.no_grad()
     def grad_norm(self) -> torch.Tensor:
@@ -275,6 +411,9 @@ class FusedAdamW(torch.optim.Optimizer):
         from . import _lib as L
         from .ops import _stream
         assert closure is None
+        ema = self.ema
+        if ema is not None and ema._swapped:
+            raise RuntimeError("FusedAdamW.step() inside WeightEMA.swapped(): the parameters hold the averaged weights there")
         g = self.param_groups[0]
         f = self.flat
         f.attach_grads()
@@ -295,6 +434,8 @@ class FusedAdamW(torch.optim.Optimizer):
             if state is not None:
                 gr, bo, it = self._scale_cfg
                 L.check(L.lib.uclstm_loss_scale_update(state, C.c_void_p(self.sumsq.data_ptr()), gr, bo, it, _stream()), "loss_scale_update")
+            if ema is not None:
+                ema._update(self.sumsq if state is not None else None)          # only a scaled step can have been skipped
             from . import ops
             ops.weights_changed()
             return None
@@ -309,6 +450,8 @@ class FusedAdamW(torch.optim.Optimizer):
             gr, bo, it = self._scale_cfg
             L.check(L.lib.uclstm_loss_scale_update(C.c_void_p(self.scale_state.data_ptr()), C.c_void_p(self.sumsq.data_ptr()), gr, bo, it,
                                                    _stream()), "loss_scale_update")
+            if ema is not None:
+                ema._update(self.sumsq)
             from . import ops
             ops.weights_changed()
             return None
@@ -319,6 +462,8 @@ class FusedAdamW(torch.optim.Optimizer):
             L.check(L.lib.uclstm_adamw_step_dev(C.c_void_p(f.flat_p.data_ptr()), C.c_void_p(self.m.data_ptr()), C.c_void_p(self.v.data_ptr()),
                                                 C.c_void_p(f.flat_g.data_ptr()), f.numel, C.c_void_p(self.sumsq.data_ptr()),
                                                 C.c_void_p(self.hyper.data_ptr()), _stream()), "adamw_step_dev")
+            if ema is not None:
+                ema._update(None)
             from . import ops
             ops.weights_changed()
             return None
@@ -330,6 +475,8 @@ class FusedAdamW(torch.optim.Optimizer):
                                         C.c_void_p(f.flat_g.data_ptr()), f.numel, sq,
                                         float(self.max_grad_norm or 0.0), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
                                         float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream()), "adamw_step")
+        if ema is not None:
+            ema._update(None)
         from . import ops
         ops.weights_changed()          # raw-pointer update: tensor versions do not move, panel caches must be told
         return None
