@@ -640,6 +640,38 @@ int32_t uclstm_ema_update(float* ema, const float* p, int64_t n, const double* s
  * nothing written for a NULL a / b, n < 0, a == b or overlapping ranges; n == 0 is UCLSTM_OK without a launch. */
 int32_t uclstm_swap_f32(float* a, float* b, int64_t n, void* stream);
 
+/* Per-tensor statistics of the optimiser's flat buffers, one call behind any of the AdamW entry points above (and behind
+ * uclstm_ema_update): p = the parameters after the step, g = the gradients as the step read them, prev (nullable) = the
+ * parameters at the previous record, all flat f32 [n] and 16-byte aligned (as is partials).  Two launches, no atomics: the numbers are a function
+ * of the inputs alone.
+ *   blocks         DEVICE int64 [n_blocks][3]  {tensor, start, count}: the elements one block reduces, count <=
+ *                  uclstm_param_stats_chunk(), never across two tensors, ordered by tensor and then by start
+ *   tensor_blocks  DEVICE int64 [n_tensors][2] {first_block, n_blocks_of_tensor}
+ *   partials       DEVICE f64 [n_blocks][8]    scratch of the caller
+ *   ring           DEVICE f64 [history][n_tensors][8], meta DEVICE f64 [history][4]
+ *   state          DEVICE int64 [8] {every, steps_seen, records_done, due, slot, reserved x 3}: the caller sets every (>= 1) and
+ *                  zeroes the rest; due and slot are scratch between the two launches of one call
+ * Every call adds 1 to steps_seen.  It records iff the new steps_seen % every == 0; otherwise every block returns after
+ * reading the state: nothing else is read or written, prev included.  A record goes to slot = records_done % history, then
+ * records_done += 1.  Row ring[slot][tensor], over the elements of the tensor, everything widened to f64:
+ *   [0] sum g^2 over finite g        [1] max |g| over finite g (0: none)   [2] non-finite g       [3] g == 0 (+0 and -0)
+ *   [4] sum p^2 over finite p        [5] max |p| over finite p             [6] non-finite p
+ *   [7] sum (p - prev)^2 where both are finite; 0 without prev
+ * and with prev the same pass then writes prev[i] = p[i]: column 7 is the change since the previous record.  Sums are added
+ * within a block by a fixed tree and across a tensor's blocks in block order.
+ * Row meta[slot] = {steps_seen, *scale or 1, *sumsq or NaN, skipped}; skipped = 1 iff sumsq != NULL and *sumsq is NaN or
+ * infinite, the test of uclstm_adamw_step_scaled / uclstm_adamw_step_groups / uclstm_loss_scale_update on the same value.
+ * sumsq, scale: nullable DEVICE scalars, read only.  Slot and counts are read from the device, the arguments never change: the
+ * call can sit in a captured graph and advances the ring on every replay.  The counts are int64.
+ * UCLSTM_E_BADARG before any launch for a NULL p / g / blocks / tensor_blocks / partials / ring / meta / state, a misaligned
+ * p / g / prev / partials, n <= 0, n_blocks <= 0, n_tensors <= 0, history <= 0.  The tables live on the device and are not checked here
+ * (the host mirror does); a row that points outside [0, n) or is longer than the chunk reads and writes nothing. */
+int64_t uclstm_param_stats_chunk(void);
+int32_t uclstm_param_stats(const float* p, const float* g, float* prev /* nullable */, int64_t n, const int64_t* blocks, int64_t n_blocks,
+                           const int64_t* tensor_blocks, int32_t n_tensors, double* partials, double* ring, double* meta,
+                           int32_t history, const double* sumsq /* nullable */, const float* scale /* nullable */, int64_t* state,
+                           void* stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* Data path around the step                              */
 /* ------------------------------------------------------------------------------------ */

@@ -16,6 +16,10 @@ Prints medians and min - max per arm and whether each B median exceeds A's media
         # the weight EMA: the optimiser step (sum of squares + uclstm_adamw_step_dev) without / with / without the
         # uclstm_ema_update sweep behind it (A/B/A), the sweep alone beside uclstm_adamw_step_groups (bytes per second of both
         # in the same run), uclstm_swap_f32 alone, and the launch log of a training step without and with an EMA attached
+    python tools/bench_adamw.py --monitor [--rounds 9] [--out profiles/monitor_ab.txt]
+        # the step monitor: the optimiser step without / with / without uclstm_param_stats behind it at every = 1 (A/B/A), the
+        # recording call alone with and without the update column, a call that does not record alone, and the launch log of a
+        # training step without and with a monitor attached
 """
 import argparse
 import ctypes as C
@@ -27,7 +31,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import unet_convlstm_amd as U   # noqa: E402
-from unet_convlstm_amd.optim import build_run_table, check_run_table   # noqa: E402
+from unet_convlstm_amd.optim import build_run_table, build_stat_blocks, check_run_table, check_stat_blocks   # noqa: E402
 
 L = U._lib
 ap = argparse.ArgumentParser()
@@ -35,6 +39,7 @@ ap.add_argument("--rounds", type=int, default=9)
 ap.add_argument("--out", default=None, help="also write the table to this file")
 ap.add_argument("--step", action="store_true", help="time the driver-form training step (batch 32, T 20, 64 x 64) instead")
 ap.add_argument("--ema", action="store_true", help="time the optimiser step without and with the weight-EMA sweep, and the swap, instead")
+ap.add_argument("--monitor", action="store_true", help="time the optimiser step without and with the per-tensor statistics call instead")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 st = torch.cuda.current_stream()
@@ -229,7 +234,103 @@ def ema_ab():
     return same and extra == [("ema", "update", False)] and not [e for e in logs[0] if e[0] == "ema"]
 
 
-ok = ema_ab() if a.ema else step_ab() if a.step else optimiser_ab()
+
+def monitor_ab():
+    with torch.device("meta"):
+        model = U.TemporalUNetDualView(1, 1, base_ch=64, lstm_layers=1, use_skip_lstm=True, use_attention=False)
+    sizes = [p.numel() for p in model.parameters()]
+    n = sum(sizes)
+    chunk = int(L.lib.uclstm_param_stats_chunk())
+    blocks_h, tensors_h = build_stat_blocks(sizes, chunk)
+    check_stat_blocks(blocks_h, tensors_h, n, chunk)
+    say(f"{n} parameters in {len(sizes)} tensors (the benchmark model, BASELINE.json configs[1]): {blocks_h.shape[0]} blocks of up to {chunk} "
+        f"elements; cold caches: a 1 GiB fill before every measurement")
+    torch.manual_seed(0)
+    p = torch.randn(n, device=dev) * 0.02
+    g = torch.randn(n, device=dev) * 1e-3
+    m, v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    prev = p.clone()
+    sq = torch.zeros(1, dtype=torch.float64, device=dev)
+    hyper = torch.tensor([1e-4, 0.9, 0.999, 1e-8, 1e-4, 1.0, 0, 0], dtype=torch.float32, device=dev)
+    blocks, tensors = torch.from_numpy(blocks_h).to(dev), torch.from_numpy(tensors_h).to(dev)
+    history = 8
+    partials = torch.zeros((blocks_h.shape[0], 8), dtype=torch.float64, device=dev)
+    ring = torch.zeros((history, len(sizes), 8), dtype=torch.float64, device=dev)
+    meta = torch.zeros((history, 4), dtype=torch.float64, device=dev)
+    state_1 = torch.tensor([1, 0, 0, 0, 0, 0, 0, 0], dtype=torch.int64, device=dev)
+    state_0 = torch.tensor([1, 0, 0, 0, 0, 0, 0, 0], dtype=torch.int64, device=dev)
+    state_never = torch.tensor([(1 << 24) - 1, 0, 0, 0, 0, 0, 0, 0], dtype=torch.int64, device=dev)
+    s = C.c_void_p(st.cuda_stream)
+
+    def step():
+        sq.zero_()
+        L.check(L.lib.uclstm_sumsq(ptr(g), n, ptr(sq), s), "sumsq")
+        L.check(L.lib.uclstm_adamw_step_dev(ptr(p), ptr(m), ptr(v), ptr(g), n, ptr(sq), ptr(hyper), s), "dev")
+
+    def stats(prev_t, state):
+        return lambda: L.check(L.lib.uclstm_param_stats(ptr(p), ptr(g), None if prev_t is None else ptr(prev_t), n, ptr(blocks),
+                                                        int(blocks_h.shape[0]), ptr(tensors), len(sizes), ptr(partials), ptr(ring), ptr(meta),
+                                                        history, ptr(sq), None, ptr(state), s), "param_stats")
+
+    record = stats(prev, state_1)
+
+    def step_monitor():
+        step()
+        record()
+
+    arms = {
+        "A  step (sumsq + adamw_step_dev)": step,
+        "B  step + param_stats, every 1": step_monitor,
+        "A' step again": step,
+        "M1 param_stats alone, updates": record,
+        "M0 param_stats alone, no updates": stats(None, state_0),
+        "N  param_stats, not recording": stats(prev, state_never),
+    }
+    times = {k: [] for k in arms}
+    for r in range(a.rounds + 1):
+        for name, fn in arms.items():
+            t = timed(fn)
+            if r:
+                times[name].append(t)
+    report(arms, times)
+    med = {k: statistics.median(t) for k, t in times.items()}
+    names = list(arms)
+    a_med = 0.5 * (med[names[0]] + med[names[2]])
+    spread = max(max(times[names[0]]) - min(times[names[0]]), max(times[names[2]]) - min(times[names[2]]), abs(med[names[0]] - med[names[2]]))
+    say(f"A/B/A: step {a_med:.1f} us (A and A' medians {med[names[0]]:.1f} / {med[names[2]]:.1f}, spread {spread:.1f}), with the record "
+        f"{med[names[1]]:.1f} us: +{med[names[1]] - a_med:.1f} us = {100 * (med[names[1]] - a_med) / a_med:.1f} % of the stand-alone step")
+    say(f"bytes per second: recording sweep with updates 16 B/parameter {16 * n / med[names[3]] / 1e3:.0f} GB/s, without 8 B/parameter "
+        f"{8 * n / med[names[4]] / 1e3:.0f} GB/s (both launches of the call in the time); a call that does not record: "
+        f"{med[names[5]]:.1f} us for its two launches")
+    torch.cuda.synchronize()
+    counts = [int(x[1]) for x in (state_1.cpu(), state_0.cpu(), state_never.cpu())], [int(x[2]) for x in (state_1.cpu(), state_0.cpu(), state_never.cpu())]
+    say(f"calls seen / records made by the three states: {counts[0]} / {counts[1]}")
+    # the launch log of a training step: what an attached monitor adds, and that nothing else moves
+    torch.manual_seed(0)
+    net = U.TemporalUNetDualView(1, 1, base_ch=64, lstm_layers=1, use_skip_lstm=True, use_attention=False).to(dev).train()
+    opt = U.FusedAdamW(net.parameters(), lr=1e-3, weight_decay=1e-4, max_grad_norm=1.0)
+    data = U.SyntheticSequences(4, 3, 64, 64, seed=1, kind="uniform", device=dev)
+    logs = []
+    for attach in (False, False, True):
+        if attach:
+            opt.attach_monitor(names=net.named_parameters())
+        U.ops.LAUNCH_LOG = []
+        try:
+            U.train_step(net, opt, data.x, data.y, data.mask, True)
+            torch.cuda.synchronize()
+            logs.append(list(U.ops.LAUNCH_LOG))
+        finally:
+            U.ops.LAUNCH_LOG = None
+    extra = [e for e in logs[2] if e[0] == "monitor"]
+    same = logs[0] == logs[1] == [e for e in logs[2] if e[0] != "monitor"]
+    say(f"launch log of one train_step (base_ch 64, batch 4, T 3, 64 x 64): {len(logs[0])} entries without a monitor, none of kind 'monitor'; "
+        f"with attach_monitor() the same entries {'in the same order' if same else 'DIFFER'} plus {extra}")
+    say(opt.monitor.report(top=3))
+    return same and extra == [("monitor", "stats", True, False)] and not [e for e in logs[0] if e[0] == "monitor"] \
+        and counts[1][2] == 0 and counts[1][0] == counts[0][0]
+
+
+ok = monitor_ab() if a.monitor else ema_ab() if a.ema else step_ab() if a.step else optimiser_ab()
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:

@@ -9,7 +9,10 @@ the built-in procedural bank otherwise; nothing is downloaded.
 ``--burn-in K`` gives the first K frames of every sequence the weight 0 in the training and the validation loss
 (``WeightedLossSpec.burn_in``: a ConvLSTM has no history at t = 0); the error columns still cover all frames.
 
-    python tools/train_sprites.py [--epochs 4] [--steps 16] [--batch 32] [--burn-in 0] [--idx PATH] [--out profiles/sprites_train.txt]
+``--monitor`` attaches a ``StepMonitor`` with the model's parameter names (``FusedAdamW.attach_monitor``, one record per epoch: the
+update columns are the change over the epoch) and prints its ``report()`` after every epoch.
+
+    python tools/train_sprites.py [--epochs 4] [--steps 16] [--batch 32] [--burn-in 0] [--monitor] [--idx PATH] [--out profiles/sprites_train.txt]
 """
 import argparse
 import os
@@ -33,6 +36,7 @@ ap.add_argument("--base-ch", type=int, default=64)
 ap.add_argument("--lr", type=float, default=1e-3)
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--burn-in", type=int, default=0, help="frames at the start of every sequence that do not count in the loss")
+ap.add_argument("--monitor", action="store_true", help="per-tensor gradient / weight / update statistics, reported once per epoch")
 ap.add_argument("--idx", default=None, help="an MNIST IDX image file; default: procedural glyphs")
 ap.add_argument("--out", default=None, help="also append the log to this file")
 a = ap.parse_args()
@@ -56,6 +60,7 @@ val = U.DeviceSpriteLoader(bank, a.batch, a.val_steps, generator=torch.Generator
 torch.manual_seed(a.seed)
 model = U.TemporalUNetDualView(1, 1, base_ch=a.base_ch, lstm_layers=1, use_skip_lstm=True, use_attention=False).to(dev)
 opt = U.FusedAdamW(model.parameters(), lr=a.lr, weight_decay=1e-4, max_grad_norm=1.0)
+monitor = opt.attach_monitor(every=a.steps, history=max(1, a.epochs), names=model.named_parameters()) if a.monitor else None
 loss = U.WeightedLossSpec.burn_in(a.frames, a.burn_in) if a.burn_in else None
 say(f"tools/train_sprites.py on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
 say(f"{'MNIST ' + os.path.basename(a.idx) if a.idx else 'procedural'} bank of {len(bank)} glyphs; [{a.batch},{a.frames},2,{a.size},{a.size}], "
@@ -68,6 +73,8 @@ for epoch in range(a.epochs):
     ev = U.evaluate(model, val, dev, val, use_mask=True, loss=loss)
     say(f"{epoch:5d}  {tr[0]:10.5f} {tr[1]:7.4f} {tr[2]:7.4f} {tr[3]:8.4f}   {ev[0]:10.5f} {ev[1]:7.4f} {ev[2]:7.4f} {ev[3]:8.4f}   "
         f"{time.perf_counter() - t0:6.2f}")
+    if monitor is not None:
+        say(monitor.report())
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:

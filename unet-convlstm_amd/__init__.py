@@ -14,7 +14,7 @@ from .modules import (ConvLSTMCell, ConvLSTM, DoubleConv, Down, Up, OutConv, Spa
                       TemporalUNetDualView, UNet)
 from .resnet import PretrainedTemporalUNet
 from .loss import compute_loss, LossSpec, WeightedLossSpec
-from .optim import FusedAdamW, WeightEMA
+from .optim import FusedAdamW, WeightEMA, StepMonitor
 from .engine import train_one_epoch, evaluate, train_step, GraphedTrainStep, quiesce_host_gc, SyntheticSequences, NPZSequenceDataset, device_transform, EvalReport, evaluate_report, DeviceSequenceLoader, epoch_rows, Augment, epoch_augment, plane_d4, predict_tta, d4_inverse
 from .engine import (DeviceSpriteLoader, render_sprites_host, epoch_sprites, check_sprite_table, load_idx_images,
                      procedural_glyphs)
@@ -27,7 +27,7 @@ from .ops import deterministic, set_deterministic, is_deterministic
 from .ops import sync_batchnorm, set_sync_batchnorm, get_sync_batchnorm
 
 __all__ = ["ConvLSTMCell", "ConvLSTM", "DoubleConv", "Down", "Up", "OutConv", "SpatialAttention",
-           "TemporalUNetDualView", "UNet", "PretrainedTemporalUNet", "compute_loss", "LossSpec", "WeightedLossSpec", "FusedAdamW", "WeightEMA", "train_one_epoch", "evaluate",
+           "TemporalUNetDualView", "UNet", "PretrainedTemporalUNet", "compute_loss", "LossSpec", "WeightedLossSpec", "FusedAdamW", "WeightEMA", "StepMonitor", "train_one_epoch", "evaluate",
            "train_step", "GraphedTrainStep", "quiesce_host_gc", "SyntheticSequences", "NPZSequenceDataset", "device_transform", "EvalReport", "evaluate_report", "DeviceSequenceLoader", "epoch_rows", "Augment", "epoch_augment", "plane_d4", "predict_tta", "d4_inverse", "DeviceSpriteLoader", "render_sprites_host", "epoch_sprites", "check_sprite_table",
            "load_idx_images", "procedural_glyphs", "VectorNPZDataset", "plane_d4_vec", "VectorEvalReport", "evaluate_vector_report", "DeviceNPZDataset", "device_order_statistics", "device_percentile", "device_extremes",
            "percentile_ranks", "percentile_lerp", "FlatDDP", "StreamingPredictor", "PretrainedStreamingPredictor", "UclstmError", "ops",

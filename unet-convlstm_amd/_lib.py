@@ -246,6 +246,8 @@ _PROTOS = {
     "uclstm_loss_scale_update": [_P, _P, _F, _F, _I, _P],
     "uclstm_ema_update": [_P, _P, _L, _P, _P, _P],
     "uclstm_swap_f32": [_P, _P, _L, _P],
+    "uclstm_param_stats_chunk": [],
+    "uclstm_param_stats": [_P, _P, _P, _L, _P, _L, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
     "uclstm_dataset_transform": [_P, _P, _P, _P, _P, _L, _I, _I, _F, _F, _F, _I, _F, _F, _F, _P],
     "uclstm_dataset_gather_transform": [_P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _I, _F, _F, _F, _P],
     "uclstm_dataset_gather_augment": [_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _F, _I, _F, _F, _F, _P],
@@ -277,7 +279,8 @@ _PROTOS = {
 _RESTYPES = {"uclstm_igemm_wgrad_walk": C.c_int64, "uclstm_build_arch": C.c_char_p, "uclstm_source_hash": C.c_char_p, "uclstm_last_error_string": C.c_char_p, "uclstm_bn_bwd_reduce_rows": C.c_int64, "uclstm_bn_pool_bwd_rows": C.c_int64,
              "uclstm_eval_stats_rows": C.c_int64, "uclstm_colsum_ordered_rows": C.c_int64, "uclstm_outconv_bwd_ordered_rows": C.c_int64, "uclstm_head3x3_bwd_ordered_rows": C.c_int64,
              "uclstm_loss_fwd_ordered_rows": C.c_int64, "uclstm_sumsq_ordered_rows": C.c_int64, "uclstm_metric_sums_ordered_rows": C.c_int64, "uclstm_metric_sums_vec_rows": C.c_int64,
-             "uclstm_bn_add_relu_bwd_rows": C.c_int64, "uclstm_select_workspace_bytes": C.c_int64}
+             "uclstm_bn_add_relu_bwd_rows": C.c_int64, "uclstm_select_workspace_bytes": C.c_int64,
+             "uclstm_param_stats_chunk": C.c_int64}
 
 
 # entry points that exist twice: name (bfloat16) and name_f16 (IEEE binary16), identical signatures (include/uclstm.h)

@@ -23,7 +23,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 HEADER = os.path.join(HERE, "..", "include", "uclstm.h")
 LIB = os.path.join(HERE, "libuclstm.so")
-SOURCES = ["igemm_fwd.hip", "igemm_wgrad.hip", "pointwise.hip", "pack.hip", "loss_optim.hip", "eval_stats.hip", "augment.hip", "sprites.hip", "resnet.hip", "resnet_bwd.hip", "dataset_stats.hip"]
+SOURCES = ["igemm_fwd.hip", "igemm_wgrad.hip", "pointwise.hip", "pack.hip", "loss_optim.hip", "eval_stats.hip", "augment.hip", "sprites.hip", "resnet.hip", "resnet_bwd.hip", "dataset_stats.hip", "param_stats.hip"]
 # the sources that touch 16-bit activations / panels are compiled a second time for IEEE binary16 (entry points *_f16)
 F16_SOURCES = ["igemm_fwd.hip", "igemm_wgrad.hip", "pointwise.hip", "pack.hip", "resnet.hip", "resnet_bwd.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]

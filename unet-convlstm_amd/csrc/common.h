@@ -114,6 +114,10 @@ __device__ __forceinline__ float target_fwd(float v, int transform, float inv_ys
     return v;
 }
 
+// An OVERFLOWED step of fp16 training: the sum of squares of the scaled gradients is NaN or infinite.  ONE definition for every
+// kernel that acts on it (loss_optim.hip, param_stats.hip): a step is never skipped and counted, or applied and backed off.
+__device__ __forceinline__ bool step_overflowed(double ss) { return !(fabs(ss) <= 1.7976931348623157e308); }
+
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int32_t round_up32(int32_t a, int32_t b) { return (a + b - 1) / b * b; }
 

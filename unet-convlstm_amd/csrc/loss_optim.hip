@@ -140,10 +140,9 @@ __global__ void sumsq_kernel(const float* __restrict__ g, int64_t n, double* __r
     }
 }
 
-// An OVERFLOWED step of fp16 training: the sum of squares of the scaled gradients is NaN or infinite.  The one predicate of the
-// kernels that skip such a step (adamw_scaled_kernel, adamw_groups_kernel with state) and of the one that backs the scale off
-// and does not count it (loss_scale_update_kernel): a step is never skipped and counted, or applied and backed off.
-__device__ __forceinline__ bool step_overflowed(double ss) { return !(fabs(ss) <= 1.7976931348623157e308); }
+// step_overflowed (common.h): the one predicate of the kernels that skip an overflowed fp16 step (adamw_scaled_kernel,
+// adamw_groups_kernel with state), of the one that backs the scale off and does not count it (loss_scale_update_kernel), of the
+// EMA sweep and of the statistics record (param_stats.hip).
 
 __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g,
                              int64_t n, const double* __restrict__ sumsq, float max_norm, float lr, float b1, float b2, float eps,

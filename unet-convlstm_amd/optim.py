@@ -13,6 +13,7 @@ import math
 import numbers
 from typing import Iterable, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 
@@ -184,6 +185,216 @@ class WeightEMA:
         return out
 
 
+def build_stat_blocks(sizes: Sequence[int], chunk: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The two tables of ``uclstm_param_stats`` for tensors of ``sizes`` elements laid out one after the other: ``blocks`` int64
+    ``[n_blocks, 3]`` rows ``{tensor, start, count}`` (``count <= chunk``, no block across two tensors, ordered by tensor and then
+    by start) and ``tensor_blocks`` int64 ``[n_tensors, 2]`` rows ``{first_block, n_blocks_of_tensor}``.  Pure bookkeeping, no device."""
+    chunk = int(chunk)
+    if chunk <= 0:
+        raise ValueError("build_stat_blocks: chunk must be positive")
+    if len(sizes) == 0:
+        raise ValueError("build_stat_blocks: no tensors")
+    blocks: List[Tuple[int, int, int]] = []
+    tensors: List[Tuple[int, int]] = []
+    off = 0
+    for t, n in enumerate(sizes):
+        n = int(n)
+        if n <= 0:
+            raise ValueError(f"build_stat_blocks: tensor {t} has {n} elements (sizes must be positive)")
+        first = len(blocks)
+        for b in range(0, n, chunk):
+            blocks.append((t, off + b, min(chunk, n - b)))
+        tensors.append((first, len(blocks) - first))
+        off += n
+    return np.asarray(blocks, dtype=np.int64).reshape(-1, 3), np.asarray(tensors, dtype=np.int64).reshape(-1, 2)
+
+
+def check_stat_blocks(blocks, tensor_blocks, n: int, chunk: int) -> None:
+    """Raise ``ValueError`` unless the tables are what ``uclstm_param_stats`` may walk: blocks of ``1..chunk`` elements that cover
+    ``[0, n)`` in order without a gap, tensor indices that count up from 0 without skipping one, and for every tensor the row
+    ``{first_block, n_blocks}`` naming exactly its blocks.  The library cannot check a device table, so this runs on the host
+    before the tables are uploaded."""
+    blocks, tensor_blocks = np.asarray(blocks), np.asarray(tensor_blocks)
+    if blocks.ndim != 2 or blocks.shape[1] != 3 or blocks.shape[0] == 0 or blocks.dtype != np.int64:
+        raise ValueError("stat blocks: the block table must be a non-empty int64 [n_blocks, 3]")
+    if tensor_blocks.ndim != 2 or tensor_blocks.shape[1] != 2 or tensor_blocks.shape[0] == 0 or tensor_blocks.dtype != np.int64:
+        raise ValueError("stat blocks: the tensor table must be a non-empty int64 [n_tensors, 2]")
+    at, owner = 0, []
+    for i, (t, start, count) in enumerate(blocks.tolist()):
+        if not 1 <= count <= chunk:
+            raise ValueError(f"stat blocks: block {i} has {count} elements, a block reduces 1..{chunk}")
+        if start != at:
+            raise ValueError(f"stat blocks: block {i} starts at {start}, not at {at} (blocks must be ordered and gap-free)")
+        last = owner[-1] if owner else -1
+        if t != last and t != last + 1:
+            raise ValueError(f"stat blocks: block {i} names tensor {t} after tensor {last} (ordered by tensor, none skipped)")
+        owner.append(t)
+        at = start + count
+    if at != n:
+        raise ValueError(f"stat blocks: the blocks cover [0, {at}), the buffer has {n} elements")
+    if owner[-1] + 1 != tensor_blocks.shape[0]:
+        raise ValueError(f"stat blocks: the blocks name {owner[-1] + 1} tensors, the tensor table has {tensor_blocks.shape[0]}")
+    for t, (first, nb) in enumerate(tensor_blocks.tolist()):
+        if nb < 1 or first < 0 or first + nb > len(owner) or any(o != t for o in owner[first:first + nb]) \
+                or (first > 0 and owner[first - 1] == t) or (first + nb < len(owner) and owner[first + nb] == t):
+            raise ValueError(f"stat blocks: tensor {t}: row {{{first}, {nb}}} does not name exactly its blocks")
+
+
+def check_monitor(every, history, updates) -> Tuple[int, int, bool]:
+    """The arguments of ``FusedAdamW.attach_monitor`` as ``(every, history, updates)``, or ``ValueError``: ``every`` an integer with
+    ``1 <= every < 2^24``, ``history`` an integer in ``1..65536``, ``updates`` a bool.  No device."""
+    if isinstance(every, bool) or not isinstance(every, numbers.Integral) or not 1 <= every < (1 << 24):
+        raise ValueError(f"attach_monitor: every must be an integer with 1 <= every < 2^24, got {every!r}")
+    if isinstance(history, bool) or not isinstance(history, numbers.Integral) or not 1 <= history <= 65536:
+        raise ValueError(f"attach_monitor: history must be an integer in 1..65536, got {history!r}")
+    if not isinstance(updates, bool):
+        raise ValueError(f"attach_monitor: updates must be a bool, got {updates!r}")
+    return int(every), int(history), updates
+
+
+class StepMonitor:
+    """Per-tensor gradient, weight and update statistics of every ``every``-th ``optimizer.step()``, kept in a ring of ``history``
+    records on the device (``FusedAdamW.attach_monitor``).
+
+    Every ``step()`` ends with one call of ``uclstm_param_stats`` on the step's stream: a sweep over ``flat_p``, ``flat_g`` (still
+    as the step read it) and ``prev``, the weights at the previous record, which it then overwrites.  Nothing is allocated, copied
+    to the host or synchronised, and slot and counts are read from the device, so it records under eager steps, under every
+    replay of ``engine.GraphedTrainStep`` and on the skipped steps of fp16 loss scaling alike.  ``read()`` brings the ring to the
+    host.  ``state`` is the device int64[8] ``{every, steps_seen, records_done, due, slot, reserved x 3}`` of include/uclstm.h.
+    With ``updates=True`` the monitor holds ``prev``, one more f32 copy of the trainable weights (what the EMA's shadow costs);
+    with ``updates=False`` it holds none and the update columns read NaN.  A diagnostic: not part of ``optimizer.state_dict()``.
+    ``optimizer.load_state_dict`` calls ``reseed()``; after a ``model.load_state_dict`` with a monitor attached, call
+    ``reseed()`` yourself, or the next record shows the restore as one huge update."""
+
+    COLS = 8
+    PER_TENSOR = ("grad_norm", "grad_max", "grad_nonfinite", "grad_zero_frac", "weight_norm", "weight_max", "weight_nonfinite",
+                  "update_norm", "update_ratio")
+
+    def __init__(self, optimizer: "FusedAdamW", every: int, history: int, updates: bool, names: Sequence[str]):
+        from . import _lib as L
+        self.optimizer = optimizer
+        self.every, self.history, self.updates = every, history, updates
+        f = optimizer.flat
+        dev = f.flat_p.device
+        self.names = list(names)
+        self.numel = np.asarray([p.numel() for p in f.params], dtype=np.int64)
+        self.group = np.asarray(optimizer._tensor_groups, dtype=np.int64)
+        self.chunk = int(L.lib.uclstm_param_stats_chunk())
+        blocks, tensor_blocks = build_stat_blocks(self.numel.tolist(), self.chunk)
+        check_stat_blocks(blocks, tensor_blocks, f.numel, self.chunk)
+        self.blocks, self.tensor_blocks = torch.from_numpy(blocks).to(dev), torch.from_numpy(tensor_blocks).to(dev)
+        self.partials = torch.zeros((blocks.shape[0], self.COLS), dtype=torch.float64, device=dev)
+        self.ring = torch.zeros((history, len(self.names), self.COLS), dtype=torch.float64, device=dev)
+        self.meta = torch.zeros((history, 4), dtype=torch.float64, device=dev)
+        self.state = torch.tensor([every, 0, 0, 0, 0, 0, 0, 0], dtype=torch.int64).to(dev)
+        self.prev = f.flat_p.detach().clone() if updates else None
+
+    def steps_seen(self) -> int:
+        """Calls of ``optimizer.step()`` this monitor has seen, skipped ones included (reads the device)."""
+        return int(self.state[1].item())
+
+    def records_done(self) -> int:
+        """Records made so far; the ring holds the last ``history`` of them (reads the device)."""
+        return int(self.state[2].item())
+
+    def reseed(self) -> None:
+        """``prev = flat_p``: the next record's update column counts from the weights as they are now."""
+        if self.prev is not None:
+            self.prev.copy_(self.optimizer.flat.flat_p)
+
+    def _record(self, sumsq: Optional[torch.Tensor], scale: Optional[torch.Tensor]) -> None:
+        from . import _lib as L
+        from . import ops
+        f = self.optimizer.flat
+        if ops.LAUNCH_LOG is not None:
+            ops.LAUNCH_LOG.append(("monitor", "stats", sumsq is not None, scale is not None))
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())          # noqa: E731
+        L.check(L.lib.uclstm_param_stats(ptr(f.flat_p), ptr(f.flat_g), ptr(self.prev), f.numel, ptr(self.blocks), int(self.blocks.shape[0]),
+                                         ptr(self.tensor_blocks), len(self.names), ptr(self.partials), ptr(self.ring), ptr(self.meta),
+                                         self.history, ptr(sumsq), ptr(scale), ptr(self.state), ops._stream()), "param_stats")
+
+    @staticmethod
+    def reduce(ring, meta, records_done: int, history: int, updates: bool = True, names: Optional[Sequence[str]] = None,
+               numel=None, group=None) -> dict:
+        """The report of ``read()`` from host copies of the raw ring f64 ``[history, n, 8]``, meta f64 ``[history, 4]`` and the record
+        count: numpy only, no device.  The ``R = min(records_done, history)`` surviving records in chronological order; gradient
+        norms and maxima divided by the record's loss scale in f64; ``update_norm`` / ``update_ratio`` NaN without ``updates``."""
+        ring = np.asarray(ring, dtype=np.float64).reshape(history, -1, StepMonitor.COLS)
+        meta = np.asarray(meta, dtype=np.float64).reshape(history, 4)
+        n = ring.shape[1]
+        records_done = int(records_done)
+        R = max(0, min(records_done, history))
+        slots = (records_done - R + np.arange(R)) % history
+        rows, m = ring[slots], meta[slots]
+        numel = np.ones(n, dtype=np.int64) if numel is None else np.asarray(numel, dtype=np.int64)
+        scale = m[:, 1].copy()
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            weight_norm = np.sqrt(rows[:, :, 4])
+            update_norm = np.sqrt(rows[:, :, 7]) if updates else np.full((R, n), np.nan)
+            out = {
+                "step": m[:, 0].astype(np.int64), "skipped": m[:, 3] != 0.0, "scale": scale,
+                "global_grad_norm": np.sqrt(m[:, 2]) / scale,
+                "names": list(names) if names is not None else [f"param{i}" for i in range(n)],
+                "numel": numel, "group": np.zeros(n, dtype=np.int64) if group is None else np.asarray(group, dtype=np.int64),
+                "grad_norm": np.sqrt(rows[:, :, 0]) / scale[:, None], "grad_max": rows[:, :, 1] / scale[:, None],
+                "grad_nonfinite": rows[:, :, 2].astype(np.int64), "grad_zero_frac": rows[:, :, 3] / numel[None, :].astype(np.float64),
+                "weight_norm": weight_norm, "weight_max": rows[:, :, 5].copy(), "weight_nonfinite": rows[:, :, 6].astype(np.int64),
+                "update_norm": update_norm, "update_ratio": update_norm / np.maximum(weight_norm, np.finfo(np.float64).tiny),
+            }
+        return out
+
+    def read(self) -> dict:
+        """The surviving records as numpy arrays, oldest first (one copy of ring, meta and state to the host, then numpy only):
+        ``step [R]``, ``skipped [R]`` (bool), ``scale [R]``, ``global_grad_norm [R]`` (NaN where the step computed no global norm),
+        ``names``, ``numel [n]``, ``group [n]`` and, ``[R, n]`` each, ``grad_norm``, ``grad_max``, ``grad_nonfinite``, ``grad_zero_frac``,
+        ``weight_norm``, ``weight_max``, ``weight_nonfinite``, ``update_norm`` and ``update_ratio = update_norm / max(weight_norm,
+        tiny)``.  Gradient norms and maxima are unscaled (divided by the record's loss scale); norms skip non-finite elements,
+        which the ``*_nonfinite`` columns count.  ``update_norm`` is the change since the previous record: exactly 0 over
+        skipped steps.  ``skipped``: the step's global sum of squares was NaN or infinite, on which the loss-scaling steps skip."""
+        state = self.state.cpu().numpy()
+        return StepMonitor.reduce(self.ring.cpu().numpy(), self.meta.cpu().numpy(), int(state[2]), self.history, self.updates,
+                                  self.names, self.numel, self.group)
+
+    def nonfinite(self, last: int = 1) -> List[Tuple[int, str, int]]:
+        """``(step, name, count)`` of every tensor whose gradient held NaN or infinite elements in one of the ``last`` latest
+        records: which tensor overflowed an fp16 step."""
+        r = self.read()
+        out = []
+        for k in range(max(0, len(r["step"]) - int(last)), len(r["step"])):
+            for i in np.flatnonzero(r["grad_nonfinite"][k] > 0):
+                out.append((int(r["step"][k]), r["names"][i], int(r["grad_nonfinite"][k, i])))
+        return out
+
+    def report(self, top: int = 8) -> str:
+        """A few lines on the latest record: tensors with non-finite gradients, the largest and the smallest ``update_ratio``,
+        gradients that are zero in a whole tensor, and per parameter group the pooled ``|dw| / |w|``."""
+        r = self.read()
+        if len(r["step"]) == 0:
+            return "StepMonitor: no record yet"
+        k, names = len(r["step"]) - 1, r["names"]
+        lines = [f"StepMonitor: step {int(r['step'][k])}{' (skipped)' if r['skipped'][k] else ''}, loss scale {r['scale'][k]:g}, "
+                 f"global grad norm {r['global_grad_norm'][k]:.4g}, {len(names)} tensors"]
+        bad = np.flatnonzero(r["grad_nonfinite"][k] > 0)
+        lines.append(f"  non-finite gradients: {len(bad)} tensors" + "".join(
+            f"\n    {names[i]}: {int(r['grad_nonfinite'][k, i])} of {int(r['numel'][i])}" for i in bad[:top]))
+        if self.updates:
+            ratio = r["update_ratio"][k]
+            order = np.argsort(ratio, kind="stable")
+            for title, pick in (("largest", order[::-1][:top]), ("smallest", order[:top])):
+                lines.append(f"  {title} |dw| / |w| since the previous record:" + "".join(
+                    f"\n    {names[i]}: {ratio[i]:.3e}" for i in pick))
+        dead = np.flatnonzero(r["grad_zero_frac"][k] == 1.0)
+        lines.append(f"  all-zero gradients: {len(dead)} tensors" + "".join(f"\n    {names[i]}" for i in dead[:top]))
+        for gi in sorted(set(r["group"].tolist())):
+            sel = r["group"] == gi
+            w = math.sqrt(float(np.sum(r["weight_norm"][k, sel] ** 2)))
+            line = f"  group {gi}: {int(sel.sum())} tensors, {int(r['numel'][sel].sum())} elements, |w| {w:.4g}"
+            if self.updates:
+                line += f", pooled |dw| / |w| {math.sqrt(float(np.sum(r['update_norm'][k, sel] ** 2))) / max(w, np.finfo(np.float64).tiny):.3e}"
+            lines.append(line)
+        return "\n".join(lines)
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """AdamW(lr, betas, eps, weight_decay) + optional ``clip_grad_norm_(max_grad_norm)`` in two HIP kernels.
 
@@ -228,6 +439,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self.max_grad_norm = max_grad_norm
         self.step_count = 0
         self.ema: Optional[WeightEMA] = None        # attach_ema()
+        self.monitor: Optional[StepMonitor] = None  # attach_monitor()
         # fp16 compute (ops.compute_dtype(torch.float16)): dynamic loss scaling, all on the device.  ``scale_state`` =
         # [scale, growth tracker, successful steps]; the training step multiplies the loss by scale_state[0] before backward.
         self.scale_state = None
@@ -275,6 +487,23 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError("FusedAdamW.attach_ema() inside a graph capture")
         self.ema = WeightEMA(self, decay, warmup, every)
         return self.ema
+
+    def attach_monitor(self, every: int = 1, history: int = 128, updates: bool = True, names=None) -> StepMonitor:
+        """Record per-tensor statistics of the gradients, the weights and the update on the device (``StepMonitor``): from now on
+        every ``step()`` ends with one ``uclstm_param_stats`` call on its stream, which records every ``every``-th step into a ring
+        of ``history`` records.  Called once, after construction.  ``names``: ``model.named_parameters()`` or any iterable of
+        ``(name, parameter)``, matched by identity against the optimiser's trainable tensors; a tensor without a name is
+        ``param{i}``.  ``updates=True`` holds one more f32 copy of the trainable weights (``prev``, the memory of an EMA shadow) for
+        the ``|dw| / |w|`` columns; ``updates=False`` holds none and those columns read NaN.  Tables, scratch, ring and state are
+        allocated here, nothing in ``step()``."""
+        every, history, updates = check_monitor(every, history, updates)
+        if getattr(self, "monitor", None) is not None:
+            raise RuntimeError("FusedAdamW.attach_monitor: a monitor is attached already")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdamW.attach_monitor() inside a graph capture")
+        given = {id(p): str(n) for n, p in names} if names is not None else {}
+        self.monitor = StepMonitor(self, every, history, updates, [given.get(id(p), f"param{i}") for i, p in enumerate(self.flat.params)])
+        return self.monitor
 
     def _group_values(self):
         return tuple((float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
@@ -379,6 +608,8 @@ class FusedAdamW(torch.optim.Optimizer):
             else:
                 ema.shadow.copy_(self.flat.flat_p)
                 ema.state[3:5] = 0.0
+        if getattr(self, "monitor", None) is not None:      # a restore is not an update: the next record counts from here
+            self.monitor.reseed()
 
     @torch.no_grad()
     def grad_norm(self) -> torch.Tensor:
@@ -414,6 +645,7 @@ class FusedAdamW(torch.optim.Optimizer):
         ema = self.ema
         if ema is not None and ema._swapped:
             raise RuntimeError("FusedAdamW.step() inside WeightEMA.swapped(): the parameters hold the averaged weights there")
+        monitor = self.monitor
         g = self.param_groups[0]
         f = self.flat
         f.attach_grads()
@@ -436,6 +668,8 @@ class FusedAdamW(torch.optim.Optimizer):
                 L.check(L.lib.uclstm_loss_scale_update(state, C.c_void_p(self.sumsq.data_ptr()), gr, bo, it, _stream()), "loss_scale_update")
             if ema is not None:
                 ema._update(self.sumsq if state is not None else None)          # only a scaled step can have been skipped
+            if monitor is not None:
+                monitor._record(self.sumsq, self._last_scale if state is not None else None)
             from . import ops
             ops.weights_changed()
             return None
@@ -452,6 +686,8 @@ class FusedAdamW(torch.optim.Optimizer):
                                                    _stream()), "loss_scale_update")
             if ema is not None:
                 ema._update(self.sumsq)
+            if monitor is not None:
+                monitor._record(self.sumsq, self._last_scale)
             from . import ops
             ops.weights_changed()
             return None
@@ -464,6 +700,8 @@ class FusedAdamW(torch.optim.Optimizer):
                                                 C.c_void_p(self.hyper.data_ptr()), _stream()), "adamw_step_dev")
             if ema is not None:
                 ema._update(None)
+            if monitor is not None:
+                monitor._record(self.sumsq, None)
             from . import ops
             ops.weights_changed()
             return None
@@ -477,6 +715,8 @@ class FusedAdamW(torch.optim.Optimizer):
                                         float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream()), "adamw_step")
         if ema is not None:
             ema._update(None)
+        if monitor is not None:
+            monitor._record(self.sumsq if sq is not None else None, None)
         from . import ops
         ops.weights_changed()          # raw-pointer update: tensor versions do not move, panel caches must be told
         return None
