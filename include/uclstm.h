@@ -119,7 +119,26 @@ int32_t uclstm_igemm_tiles_per_group(int32_t n_img, int32_t H, int32_t W, int32_
  *   nn.Conv2d 3x3 of DoubleConv (train/unet.py:70-71) incl. the cat([skip, up]) of :98,
  *   its input gradient (flipped/transposed panel), ConvTranspose2d forward and input
  *   gradient (:90,:94), and with UCLSTM_EPI_LSTM the whole ConvLSTMCell.forward (:21-36:
- *   cat + conv + chunk + sigmoid/tanh + cell update in one kernel). */
+ *   cat + conv + chunk + sigmoid/tanh + cell update in one kernel).
+ *
+ * Size limits of ONE launch.  Sources and the panel are read through 32-bit buffer descriptors in which bit 31 of the byte
+ * offset means "outside the tensor" (that is how padding costs nothing), so:
+ *   refused (UCLSTM_E_BADARG, nothing is launched):
+ *     - a source with  n_img*Hs*Ws*C*2 + 2*(max(pad+offY, 0)*Ws + max(pad+offX, 0) + 1)*C  >=  2^31 - 2^22  bytes (the second
+ *       term is the descriptor's bias: the base address lies that far before the tensor so that tap offsets stay positive);
+ *     - a panel with  N*Ktot*2 >= 2^31 - 2^22  bytes;  n_img*H*W >= 2^31 output pixels;  more than 2^31 - 1 blocks.
+ *   re-routed (same result, another kernel; uclstm_igemm_fwd_shape tells which):
+ *     - the flat kernel (4) indexes destination pixels with 32 bits: a destination of n_img*Hd*Wd >= 2^31 pixels sends the
+ *       descriptor to shape 0 / 1;
+ *     - the ring kernel (3) asks n_img*(W/64)*(H+1) < 2^30 and the patch loop (2) n_img*(H+1)*(W+1) < 2^30 of their padded
+ *       index spaces, else shape 1 / 0.  Their sources have 64 channels and more, so the byte limit above (2^24 pixels at 64
+ *       channels) is always reached first: a descriptor at the byte limit still runs the kernel of its shape, and one image
+ *       more is refused, whichever kernel it was.
+ *   not limited: destinations (seg[].ptr), stats, c_prev / c_out / h_out / gates_out / pre_add and acc_out are addressed with
+ *     64-bit offsets and may exceed 2 GiB and 4 GiB (a 64 -> 160-channel launch at the source limit stores 5 GiB).
+ * Callers with larger tensors cut the launch into image ranges (ops.py: LAUNCH_BYTES_LIMIT = 2^31 - 2^23 bytes per tensor and
+ * launch, whole BatchNorm groups when `stats` is set).  tests/test_high_offset_cases_host.py pins every figure above,
+ * tests/test_gpu_high_offset.py runs every kernel at its limit. */
 int32_t uclstm_igemm_fwd(const uclstm_igemm_desc* d, void* stream);
 /* Which kernel uclstm_igemm_fwd would run for this descriptor (same validation, nothing is launched): 0 = per-tap loop,
  * 128 x 128 tile; 1 = per-tap loop, 64 rows x 256 pixels (C_out <= 64); 2 = patch loop, 128 rows x 256 pixels (3x3 / pad 1 /
@@ -139,7 +158,9 @@ int32_t uclstm_igemm_ksplit_used(int32_t Ktot, int32_t ktap, int32_t ksplit);
  * blocks only; as one grid -- members ordered longest block first -- their drains and fills overlap.  Every member must be a
  * descriptor uclstm_igemm_fwd would run on the patch shape (uclstm_igemm_fwd_shape == 2) with UCLSTM_EPI_LSTM or UCLSTM_EPI_ATOMIC
  * (slab mode), all with the same nsrc; anything else is UCLSTM_E_BADARG and the caller launches the members one by one.
- * Results are bit-identical to n separate uclstm_igemm_fwd launches. */
+ * Results are bit-identical to n separate uclstm_igemm_fwd launches.  Every member is validated as uclstm_igemm_fwd validates
+ * it: the size limits stated there hold per member, and one member beyond them refuses the whole group (likewise for
+ * uclstm_igemm_fwd_group_tap below). */
 int32_t uclstm_igemm_fwd_group(const uclstm_igemm_desc* descs, int32_t n, void* stream);
 /* Validation only: the block count of the launch uclstm_igemm_fwd_group would make (>= 1), or UCLSTM_E_*. */
 int32_t uclstm_igemm_fwd_group_blocks(const uclstm_igemm_desc* descs, int32_t n);
@@ -180,6 +201,18 @@ typedef struct {
                        * STORES its partial panel to dwp + r*slab (floats), nothing needs zeroing, and uclstm_unpack_wgrad adds
                        * the uclstm_igemm_wgrad_splits() slabs (float atomics ~1.3 TB/s, stores ~6 TB/s on MI355X). */
 } uclstm_wgrad_desc;
+/* Size limits of ONE launch (tests/test_high_offset_cases_host.py pins them, tests/test_gpu_high_offset.py runs every kernel at
+ * its limit):
+ *   refused (UCLSTM_E_BADARG): a source or a dY tensor of  n_img*H*W*C >= 2^31 - 2^20  ELEMENTS (just under 4 GiB);
+ *     n_img*H*W >= 2^31 - 4096 pixels.
+ *   re-routed to generic addressing (0, 64-bit pointers, same result): the buffer-addressed kernels (1, 2, 3) take dY of
+ *     n_img*H*W*C*2 < 2^31 - 2^22  bytes and sources of  n_img*H*W*C*2 + (Ws+1)*C*2 < 2^31 - 2^22  bytes (32-bit descriptors,
+ *     bit 31 = "outside the tensor"); the ring kernel (4) takes  n_img*H*W*128 < 2^31 - 2^22  and  n_img*(W/64)*(H+1) < 2^30
+ *     and otherwise leaves the descriptor to kernels 1 / 0.  Operands between 2 GiB and the element limit therefore run, on
+ *     generic addressing.
+ *   The valid-pixel walk of the 256 x 256 kernel is used below 2^24 - 4096 pixels; its dY rows are at least 512 bytes, so the
+ *     byte limit above (about 2^22 pixels) is always reached first.
+ * dwp is addressed with 64-bit offsets. */
 int32_t uclstm_igemm_wgrad(const uclstm_wgrad_desc* d, void* stream);
 /* Pixel ranges (= slabs in slab mode) the launch above will use for this descriptor; d->dwp may be NULL.  Call it with
  * splits = 0, size dwp as [result][N][Ktot], then launch with splits = result. */
